@@ -9,12 +9,17 @@ the same number of samples (weak scaling); the only collective is one all-gather
 the reduction of the per-row filter statistics (ska.rust_amd/dist.py).
 
 Prints ONE JSON line (rank 0).  `value` is that device-resident rate (inputs in HBM when the clock starts, as the bench
-contract asks; the line says so in `value_is`) -- NOT what a user of the executable times: that is `end_to_end.genomes_per_s`,
+contract asks; the line says so in `value_is`) -- NOT what a user of the executable times: that is `end_to_end.genomes_per_s` (--full),
 ~70 x lower (files in and out, not kernels).  `roofline` is for the split-k-mer extraction+scatter kernel (HBM bound): algorithmic bytes = 10 B per
 input base (1 B ASCII read + 9 B (key, middle base) written) over the kernel's launch duration measured with
 HIP events on the engine's stream.
 
-At N=1 three more objects ride on the line:
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs).  Everything else runs only with --full: the end-to-end leg, the CPU baseline and the oracle check, the
+distance stage, the unfiltered form, the rocprofv3 --pmc passes (roofline.traffic measured in the run, traffic_by_kernel, dominant,
+other_kernels) and, at N > 1, the `ska selftest` pre-flight.
+
+With --full at N=1 three more objects ride on the line:
   `end_to_end`   the metric as a user of the reference would time it: the same assemblies as FASTA files on tmpfs through the
                  `ska` executable -- `ska build` -> .skf -> `ska align` (two processes) and the single `ska align *.fa` form
                  (io_utils.rs:60-93) -- wall clock around each process plus the engine's own phase table (file reading +
@@ -55,6 +60,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run the legs outside the headline figure (end-to-end, CPU baseline, oracle check, "
+                                                        "distance, unfiltered form, --pmc passes, N > 1 selftest); the --no-* options below choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--genomes", type=int, default=1000, help="samples per GPU")
     ap.add_argument("--genome-len", type=int, default=5_000_000)
     ap.add_argument("-k", type=int, default=31)
@@ -475,10 +483,62 @@ def measure_traffic(args, lens):
     return res, n, bases
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs writes at most this much of the kept rows (float32 cells) -- under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, arr, shape):
+    """--dump-outputs: what the last timed step handed its caller -- the filtered MergeSkaArray (its split k-mers, the samples x kept-rows
+    matrix and the per-row counts) and the step's (rows, rows kept, removed) -- as .npy files, float64 / float32 (exact for every value
+    written).  The kept rows are ~5 GB at the default size and their order is the engine's (the reference leaves it to its hash map, and
+    apply_filters keeps the unfiltered key list), so every file is independent of row and key order: rows and keys are ranked by a hash
+    of their content with fixed seeded constants and a fixed stride of that ranking is written, next to order-free digests of all of them.
+      step_shape.npy         [rows before the filter, rows kept, rows removed, samples]
+      kept_rows_sample.npy   float32 [<= m, samples]: the ASCII codes of the kept rows whose hash is a multiple of ceil(rows kept / m),
+                             in hash order (m = DUMP_BYTES / 4 / samples)
+      kept_counts_sample.npy float64 [<= m]: those rows' counts
+      kept_rows_digest.npy   float64 [2]: the 64-bit wrapping sum of the hashes of all kept rows, as two 32-bit halves
+      keys_sample.npy        float64 [<= 4096, 4]: the 32-bit words (lo, hi) of the split k-mers chosen by the same rule
+      keys_digest.npy        float64 [2]: the wrapping sum of the hashes of all split k-mers, as two 32-bit halves"""
+    os.makedirs(out_dir, exist_ok=True)
+    keys, var, counts = arr.export()
+    U, S = var.shape
+    W = (S + 7) // 8
+    mult = np.random.default_rng(2024).integers(1, 1 << 63, size=W + 2, dtype=np.uint64) | np.uint64(1)
+    row_hash = np.empty(U, np.uint64)
+    blk = np.zeros((max(1, min(U, 1 << 15)), W * 8), np.uint8)
+    for a in range(0, U, len(blk)):
+        b = min(U, a + len(blk))
+        blk[:b - a, :S] = var[a:b]
+        row_hash[a:b] = (blk[:b - a].view("<u8") * mult[:W]).sum(axis=1)
+    key_hash = keys["lo"] * mult[W] + keys["hi"] * mult[W + 1]
+    for h in (row_hash, key_hash):                       # (the low bits of a product with odd constants follow the input's low bits)
+        h ^= h >> np.uint64(29)
+
+    def halves(h):
+        s = int(h.sum(dtype=np.uint64)) if len(h) else 0
+        return np.array([s & 0xFFFFFFFF, s >> 32], np.float64)
+
+    def every(h, m):                                     # ~m of them, at most m: those whose hash is a multiple of a stride, by hash
+        sel = np.flatnonzero(h % np.uint64(max(1, -(-len(h) // m))) == 0)
+        return sel[np.argsort(h[sel], kind="stable")][:m]
+
+    rows = every(row_hash, max(1, DUMP_BYTES // (4 * max(S, 1))))
+    ks = keys[every(key_hash, 4096)]
+    files = {"step_shape": np.array([shape[0], shape[1], shape[2], S], np.float64),
+             "kept_rows_sample": var[rows].astype(np.float32), "kept_counts_sample": counts[rows].astype(np.float64),
+             "kept_rows_digest": halves(row_hash),
+             "keys_sample": np.stack([ks["lo"] & 0xFFFFFFFF, ks["lo"] >> 32, ks["hi"] & 0xFFFFFFFF, ks["hi"] >> 32], axis=1).astype(np.float64),
+             "keys_digest": halves(key_hash)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.pmc_child > 0:
         return pmc_child(args)
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs --steps of at least 1")
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -492,7 +552,7 @@ def main():
         raise SystemExit("bench.py needs a gfx950 GPU: the engine has no CPU path")
     sharded = world > 1 or os.environ.get("SKX_BENCH_FORCE_SHARDED") == "1"     # the override runs the exchange path at world size 1
     selftest = None
-    if world > 1 and rank == 0 and not args.no_selftest and os.environ.get("SKX_BENCH_BACKEND", "nccl") == "nccl":
+    if args.full and world > 1 and rank == 0 and not args.no_selftest and os.environ.get("SKX_BENCH_BACKEND", "nccl") == "nccl":
         selftest = preflight(args, world)      # (the other ranks wait in init_process_group below)
     import synth
 
@@ -503,8 +563,8 @@ def main():
     # ---- inputs -> HBM (not timed): one 16-B aligned record stream per sample
     lens, offs, tot = [], [], 0
     streams = []
-    # N = 1: the same assemblies also go to tmpfs as 60-column FASTA files for the end-to-end, CPU-baseline and check legs
-    want_files = rank == 0 and world == 1 and not (args.no_e2e and args.no_check and args.cpu_genomes <= 0)
+    # N = 1, --full: the same assemblies also go to tmpfs as 60-column FASTA files for the end-to-end, CPU-baseline and check legs
+    want_files = args.full and rank == 0 and world == 1 and not (args.no_e2e and args.no_check and args.cpu_genomes <= 0)
     td = tempfile.mkdtemp(prefix="skx_bench_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None) if want_files else None
     files = []
     for i in range(G):
@@ -643,7 +703,9 @@ def main():
     distance_stage = None
     unfiltered = None
     pieces_info, merge_path = (0, 0, 0), ctx.merge_path()
-    if rank == 0 and world == 1:       # the unfiltered rows x samples matrix (what a .skf holds), produced from the merge's pieces: outside `value`
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, shape)
+    if args.full and rank == 0 and world == 1:       # the unfiltered rows x samples matrix (what a .skf holds), produced from the merge's pieces: outside `value`
         ds = E.DictSet.build_device(ptrs, lens, args.k, True, ctx=ctx)
         arr_u = ds.merge(names)
         ctx.sync()
@@ -659,7 +721,7 @@ def main():
                               "(pieces_rows_kernel<all rows>); `ska build` streams it window by window into the .skf, `ska align` never writes it"}
         arr_u.free()
         ds.free()
-    if rank == 0:                      # sum of the per-sample dictionary sizes (untimed): the D of SURVEY.md 8d's per-stage bytes
+    if args.full and rank == 0:        # sum of the per-sample dictionary sizes (untimed): the D of SURVEY.md 8d's per-stage bytes
         # (counted from the merged array's cells -- a sample's split k-mers are its cells: no dictionary is sorted for it)
         ds = E.DictSet.build_device(ptrs, lens, args.k, True, ctx=ctx)
         arr_d = ds.merge(names)
@@ -713,7 +775,7 @@ def main():
             "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u64" if args.k <= 31 else "u128", "data": "synthetic",
             "value_is": "the device-resident step (inputs in HBM when the clock starts, no file in or out: the bench contract's `value`); the metric as a user times it -- "
-                        "FASTA files in, .skf and alignment out, through the ska executable -- is end_to_end.genomes_per_s (N = 1), ~70 x lower: files, not kernels",
+                        "FASTA files in, .skf and alignment out, through the ska executable -- is end_to_end.genomes_per_s (N = 1, --full), ~70 x lower: files, not kernels",
             "config": {"workload": f"ska build + ska align, {G} synthetic {args.genome_len} bp assemblies per GPU, k={args.k}, "
                                    f"inputs resident in HBM (BASELINE.json configs[2])",
                        "samples_per_gpu": G, "private_snps": private_snps(n_total), "genome_len": args.genome_len, "k": args.k,
@@ -721,7 +783,7 @@ def main():
             "roofline": {"bound": "hbm", "kernel": ("extract_kernel<true>" if args.k <= 31 else "extract_wide_kernel<true>") + " (split k-mer extraction + bucket scatter)",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "algorithmic_bytes_per_launch": algo_bytes, "launch_ms": scatter_ms,
-                         "largest_kernel_of_step": "extraction" if scatter_ms >= tm["append"] / steps else "append (see dominant)"},
+                         "largest_kernel_of_step": "extraction" if scatter_ms >= tm["append"] / steps else "append (see dominant, --full)"},
             "kernel_pipeline": {"genomes_per_s": n_total * steps / dt, "what": "= value: extraction -> dictionaries -> merge -> filter with the record streams resident in HBM"},
             "stage_ms_per_step": {k: v / steps for k, v in tm.items()},
             "merge_path": merge_path,
@@ -744,7 +806,7 @@ def main():
                                               "what": "skx_keyset_allgather (one ncclAllGather of the per-rank key tables, then their union) + skx_array_reduce_stats "
                                                       "(one ncclAllReduce + one ncclAllGather of the per-row filter statistics), issued by the engine; nothing else crosses xGMI"}
         res["roofline"]["traffic_source"] = traffic_src
-        if world > 1:
+        if args.full and world > 1:
             res["other_kernels"] = other_kernels(tm, steps, total_bases, n_distinct, shape[0], shape[1], G, key_bytes)
         try:                                     # measurement builds (-DSKX_PHASE_PROF=n, tools/mkvariant.sh): cycle shares per phase of the instrumented kernel
             import ctypes
@@ -754,7 +816,7 @@ def main():
             sys.stderr.write("phases (share of cycles): %s cycles in all: %d raw: %s\n" % ([round(x / tot, 3) for x in buf[:10]], tot, list(buf)))
         except AttributeError:
             pass
-        if world == 1:
+        if args.full and world == 1:
             # the legs below run outside the timed region; the bench's own device buffers go first (the ska executable gets the GPU)
             if last is not None:
                 last.free()

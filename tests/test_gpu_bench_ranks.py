@@ -65,7 +65,33 @@ def test_bench_refuses_a_world_that_is_not_gpus():
 def test_bench_measures_the_extraction_kernels_traffic_in_the_run():
     """roofline.traffic comes from rocprofv3 --pmc passes of this very run (FETCH_SIZE x 2 + WRITE_SIZE of the extraction kernel's launches over a
     child process), not from a file under profiles/: at least the W + 1 bytes a base leaves in the regions, and no more than a few times that"""
-    line = _bench(["--gpus", "1", "--pmc-genomes", "12", "--no-check", "--no-distance"])
+    line = _bench(["--gpus", "1", "--full", "--pmc-genomes", "12", "--no-check", "--no-distance"])
     rl = line["roofline"]
     assert rl["traffic_source"].startswith("measured in this run"), rl["traffic_source"]
     assert 0.3 * rl["algorithmic_bytes_per_launch"] < rl["traffic"] < 6.0 * rl["algorithmic_bytes_per_launch"], rl
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain run times --steps steps and prints the line, with no leg of --full; --dump-outputs writes the last timed step's outputs as
+    float .npy files, the same ones run after run (the inputs are seeded)"""
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--genomes", "24", "--genome-len", "300000", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 24) < 1e-6 * 24
+    for k in ("end_to_end", "cpu_baseline", "check", "distance", "unfiltered_form", "traffic_by_kernel", "other_kernels"):
+        assert k not in line, k
+    import numpy as np
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names and names == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    shape = np.load(tmp_path / "a" / "step_shape.npy").tolist()
+    assert shape[:2] == [line["config"]["rows_U"], line["config"]["rows_kept"]] and shape[3] == 24
+    rows = np.load(tmp_path / "a" / "kept_rows_sample.npy")
+    assert rows.shape[1] == 24 and len(rows) > 0 and set(np.unique(rows).astype(int).tolist()) <= set(b"ACGTRYSWKMBDHVN-")

@@ -278,7 +278,7 @@ def test_bench_two_gpus_over_rccl_reports_its_ranks(tmp_path):
     common = ["--genomes", "24", "--genome-len", "300000", "--steps", "2", "--warmup", "1", "--cpu-genomes", "0", "--no-e2e", "--no-pmc"]
     env = {k: v for k, v in os.environ.items() if not k.startswith("SKX_") and k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(29700 + os.getpid() % 200), bench, "--gpus", "2", *common]
+           str(29700 + os.getpid() % 200), bench, "--gpus", "2", "--full", *common]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     two = json.loads([x for x in r.stdout.strip().splitlines() if x.startswith("{")][-1])
