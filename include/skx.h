@@ -294,6 +294,30 @@ int  skx_skf_peek_k(const char *path);
 skx_ctx *skx_array_ctx(const skx_array *a);
 void skx_set_last_error(const char *msg);
 
+/* ---- `ska lo` (generic_modes.rs:286-306, src/skalo) ----
+ * read_graph.rs:build_graph + extremities.rs:identify_good_kmers on the device: the coloured de Bruijn graph of the array (every sample on
+ * this device; at most 65 535 samples, the reference's u16 sample index), in CSR form with (k-1)-mer nodes in the reference's 2-bit code
+ * (A=0, C=1, T=2, G=3, first base high; words_per_node 64-bit words each, little-endian: 1 for k <= 31, 2 above).  Nodes ascending,
+ * each node's neighbours ascending with repeated edges kept, entry nodes ascending, exit nodes (their reverse complements) ascending.
+ * The colours (sample bitsets, colour_words 64-bit words, bit s = sample s) of the full k-mers stay on the device: skx_lo_gather looks
+ * up a batch of them (found[i] = 0: not a k-mer of the graph).  A k-mer two (row, base) pairs write keeps the colour of the lowest
+ * (split k-mer, base code). */
+typedef struct skx_lo_graph skx_lo_graph;
+typedef struct {
+    int32_t  k, words_per_node;
+    uint64_t n_samples, colour_words;
+    uint64_t n_nodes, n_edges, n_entries;   /* n_exits == n_entries */
+    uint64_t n_colours;                     /* present (row, base) pairs */
+    uint64_t n_kmers;                       /* distinct full k-mers */
+} skx_lo_info;
+int  skx_array_lo_graph(skx_array *a, skx_lo_graph **out);
+int  skx_lo_graph_info(const skx_lo_graph *g, skx_lo_info *info);
+/* copy-out; any pointer may be NULL: nodes[n_nodes * wpn], offsets[n_nodes + 1], neighbours[n_edges * wpn], entries / exits[n_entries * wpn] */
+int  skx_lo_graph_export(const skx_lo_graph *g, uint64_t *nodes, uint64_t *offsets, uint64_t *neighbours, uint64_t *entries, uint64_t *exits);
+/* kmers[n * wpn] full k-mers -> colours[n * colour_words], found[n] */
+int  skx_lo_gather(skx_lo_graph *g, const uint64_t *kmers, uint64_t n, uint64_t *colours, uint8_t *found);
+void skx_lo_graph_free(skx_lo_graph *g);
+
 /* wall-clock phases of the host-side path (file reading + upload, .skf codec, FASTA writer ...), accumulated per name since the
  * last reset: a JSON object {"phase": seconds, ...} in first-use order (malloc'd, skx_free).  The reference has no counterpart;
  * bench.py's end_to_end leg and SKX_DEBUG read them.  skx_phase_add lets host glue above the ABI record its own phases. */

@@ -77,14 +77,21 @@ int skh_build_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job);
 int skh_align_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job);
 /* `ska distance`: generic_modes::distance's two filters on the reduced statistics, then skx_array_distance_sharded; rank 0 writes the table */
 int skh_distance_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job);
-/* the `ska` command line (build | align | map | distance | nk | merge | delete | weed | cov); returns the process exit code.
+/* generic_modes.rs:286-306 skalo (`ska lo`): the array of skf_file on the device (skx_array_lo_graph), then compaction, the DFS of depth
+ * `depth` from every entry node on `threads` host threads, indels and SNPs on the host.  Writes <out_prefix>_indels.vcf and _snps.fas, and
+ * with a single-record `reference` (NULL: none) also _pseudo_genomes.fas and _snps.vcf.  `missing`: the largest fraction of missing samples
+ * (f32, as cli.rs declares it); `indel_kmers`: the most indel k-mers a path may hold.  SKX_EEMPTY (after the reference's log line) when the
+ * graph has no entry node; SKX_EINVAL with the reference's panic text when the reference file holds more than one record. */
+int skh_lo(skx_ctx *ctx, const char *skf_file, const char *reference, const char *out_prefix, float missing, size_t depth, size_t indel_kmers,
+           int threads);
+/* the `ska` command line (build | align | map | distance | nk | merge | delete | weed | cov | lo); returns the process exit code.
  * `--gpus N` on build / align / distance starts one process per GPU (this executable again, SKX_RANK / SKX_WORLD / SKX_COMM_ID_FILE in
  * their environment) and runs the sharded bodies above; a launcher of one's own sets the same variables. */
 int skh_main(int argc, char **argv);
 /* `ska --help | -h | help [cmd] | <cmd> --help | --version | -V` (cli.rs:154 `#[command(author, version, about)]`, propagate_version; per-flag
  * help cli.rs:168-459): 1 = answered on stdout (exit code 0), 0 = not a help / version request, 2 = `ska help <unknown>`.  skh_main calls it first. */
 int skh_help(int argc, char **argv);
-/* a line of the reference's logger (simple_logger: lib.rs:559-563, Warn by default, Info with -v) on stderr: level 1 = WARN, 2 = INFO;
+/* a line of the reference's logger (simple_logger: lib.rs:559-563, Warn by default, Info with -v) on stderr: level 0 = ERROR, 1 = WARN, 2 = INFO;
  * target = the Rust module the reference logs it from ("ska::io_utils" ...) */
 void skh_log(int level, const char *target, const char *message);
 

@@ -17,6 +17,7 @@ struct Opt { const char *flag; const char *value; const char *help; };
 struct Cmd {
     const char *name, *about, *usage;
     std::vector<Opt> args, opts;
+    std::vector<std::pair<const char *, std::vector<Opt>>> sections;   // clap's help_heading groups, after Options
 };
 
 const char *const THREADS = "Number of CPU threads [default: 1]";
@@ -85,6 +86,14 @@ const std::vector<Cmd> &commands()
          {{"<FASTQ_FWD>", "", "FASTQ file (or .fastq.gz) with forward reads"}, {"<FASTQ_REV>", "", "FASTQ file (or .fastq.gz) with reverse reads"}},
          {{"-k", "<K>", "K-mer size [default: 31]"},
           {"--single-strand", "", "Ignore reverse complement (all reads are oriented along same strand)"}}},
+        {"lo", "Finds 'left out' SNPs and INDELs using a graph", "ska lo [OPTIONS] <INPUT_SKF> <OUTPUT>",
+         {{"<INPUT_SKF>", "", "input SKA2 file"}, {"<OUTPUT>", "", "prefix of output files"}},
+         {},
+         {{"input", {{"-r, --reference", "<REFERENCE>", "reference genome for SNP positioning"}}},
+          {"output", {{"-m, --missing", "<MISSING>", "maximum fraction of missing data [default: 0.1]"}}},
+          {"graph traversal", {{"-d, --depth", "<DEPTH>", "maximum depth of recursive paths [default: 4]"}}},
+          {"other", {{"-n, --indel-kmers", "<INDEL_KMERS>", "maximum number of internal indel k-mers [default: 2]"},
+                     {"--threads", "<THREADS>", THREADS}}}}},
     };
     return C;
 }
@@ -115,6 +124,7 @@ void command_help(FILE *out, const Cmd &c)
     o.push_back({"-h, --help", "", "Print help"});
     o.push_back({"-V, --version", "", "Print version"});
     table(out, "Options", o);
+    for (auto &sec : c.sections) table(out, sec.first, sec.second);
 }
 void top_help(FILE *out)
 {

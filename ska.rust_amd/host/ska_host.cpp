@@ -3,6 +3,7 @@
 // get_input_list / load_array / set_ostream; cli.rs + lib.rs:557-727,808-827 for build | align | distance | nk).
 // Written in C++ because the image has no Rust toolchain; it only talks to the engine through include/skx.h.
 #include "../../include/skx_host.h"
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -661,7 +662,8 @@ struct Args {
     std::string get(const std::string &k, const std::string &d = "") const { for (auto &o : opt) if (o.first == k) return o.second; return d; }
 };
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
-                            "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus", nullptr};
+                            "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
+                            "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -674,7 +676,7 @@ extern "C" void skh_log(int level, const char *target, const char *message)     
     struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
     struct tm tmv; gmtime_r(&ts.tv_sec, &tmv);
     char tb[40]; strftime(tb, sizeof tb, "%Y-%m-%dT%H:%M:%S", &tmv);
-    fprintf(stderr, "%s.%03ldZ %-5s [%s] %s\n", tb, ts.tv_nsec / 1000000, level == 1 ? "WARN" : "INFO", target, message);
+    fprintf(stderr, "%s.%03ldZ %-5s [%s] %s\n", tb, ts.tv_nsec / 1000000, level <= 0 ? "ERROR" : level == 1 ? "WARN" : "INFO", target, message);
 }
 namespace {
 // clap's wording for what its derive macros refuse (cli.rs: value_parser / value_enum / required): exit code 2, the reason, the hint
@@ -993,6 +995,23 @@ int emit(const std::string &out_path, const char *buf, uint64_t len)            
 namespace {
 // What clap refuses before lib.rs::main runs (cli.rs: required arguments, the argument groups of build / delete, value_parser and value_enum
 // of every option): the same refusals in clap's wording, before the banner and before a device is touched.  0: the command line stands.
+// what Rust's f32::from_str takes: decimal with optional sign / exponent, "inf", "infinity", "nan" (any case)
+bool lo_float(const std::string &v)
+{
+    std::string l; for (char c : v) l.push_back((char)tolower((unsigned char)c));
+    const std::string u = (!l.empty() && (l[0] == '+' || l[0] == '-')) ? l.substr(1) : l;
+    if (u == "inf" || u == "infinity" || u == "nan") return true;
+    size_t i = 0, digits = 0;
+    while (i < u.size() && isdigit((unsigned char)u[i])) { i++; digits++; }
+    if (i < u.size() && u[i] == '.') { i++; while (i < u.size() && isdigit((unsigned char)u[i])) { i++; digits++; } }
+    if (!digits) return false;
+    if (i < u.size() && u[i] == 'e') {
+        i++; if (i < u.size() && (u[i] == '+' || u[i] == '-')) i++;
+        const size_t e0 = i; while (i < u.size() && isdigit((unsigned char)u[i])) i++;
+        if (i == e0) return false;
+    }
+    return i == u.size();
+}
 int validate_cli(const std::string &cmd, const Args &a, bool multi)
 {
     auto number = [](const std::string &v) { if (v.empty()) return false; char *e; (void)strtod(v.c_str(), &e); return *e == 0; };
@@ -1043,7 +1062,23 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (!a.pos.empty() && a.has("-f")) { fprintf(stderr, "error: the argument '[NAMES]...' cannot be used with '-f <FILE_LIST>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("delete")); return 2; }
     }
     else if (cmd == "weed") { if (a.pos.empty()) return clap_missing("weed", "<SKF_FILE>"); if (int e = filter()) return e; if (int e = freq()) return e; }
-    else if (cmd == "lo") return fail("`ska lo` is not part of this engine (build, align, map, distance, nk, merge, delete, weed, cov are)");
+    else if (cmd == "lo") {                                                                                       // cli.rs:395-425
+        if (a.pos.size() < 2) return clap_missing("lo", a.pos.empty() ? "<INPUT_SKF>\n  <OUTPUT>" : "<OUTPUT>");
+        if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("lo")); return 2; }
+        if (a.has("-m") || a.has("--missing")) {
+            const std::string v = a.has("--missing") ? a.get("--missing") : a.get("-m");
+            if (!lo_float(v)) return clap_invalid(v, "--missing <MISSING>", v.empty() ? "cannot parse float from empty string" : "invalid float literal");
+        }
+        for (auto names : {std::make_pair("-d", "--depth <DEPTH>"), std::make_pair("-n", "--indel-kmers <INDEL_KMERS>")}) {
+            const std::string lng = std::string(names.second).substr(0, std::string(names.second).find(' '));
+            if (!a.has(names.first) && !a.has(lng)) continue;
+            const std::string v = a.has(lng) ? a.get(lng) : a.get(names.first);
+            if (v.empty()) return clap_invalid(v, names.second, "cannot parse integer from empty string");
+            if (v.find_first_not_of("0123456789") != std::string::npos && !(v[0] == '+' && v.size() > 1 && v.find_first_not_of("0123456789", 1) == std::string::npos))
+                return clap_invalid(v, names.second, "invalid digit found in string");
+            if (v.size() > 19 && strtoull(v.c_str(), nullptr, 10) == ULLONG_MAX) return clap_invalid(v, names.second, "number too large to fit in target type");
+        }
+    }
     else if (cmd != "build" && cmd != "selftest") {
         fprintf(stderr, "error: unrecognized subcommand '%s'\n\nUsage: ska [OPTIONS] <COMMAND>\n\nFor more information, try '--help'.\n", cmd.c_str());
         return 2;
@@ -1082,7 +1117,8 @@ extern "C" int skh_main(int argc, char **argv)
             {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
-            {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "}};
+            {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
+            {"lo", " -r --reference -m --missing -d --depth -n --indel-kmers --threads "}};
         for (auto &kc : KNOWN)
             if (cmd == kc.cmd)
                 for (auto &o : a.opt)
@@ -1224,8 +1260,15 @@ extern "C" int skh_main(int argc, char **argv)
             skh_weed(arr, a.pos.size() == 2 ? a.pos[1].c_str() : nullptr, a.has("--reverse"), mf, a.has("--filter-ambig-as-missing"), filter,
                      a.has("--ambig-mask"), a.has("--no-gap-only-sites"), out.c_str()) != SKX_OK)
             rcode = engine_fail();
+    } else if (cmd == "lo") {                                                                                     // cli.rs Lo, generic_modes.rs:286-306
+        auto opt = [&](const char *s, const char *l, const char *d) { return a.has(l) ? a.get(l) : a.has(s) ? a.get(s) : std::string(d); };
+        const std::string ref = opt("-r", "--reference", "");
+        const int r = skh_lo(ctx, a.pos[0].c_str(), ref.empty() ? nullptr : ref.c_str(), a.pos[1].c_str(), strtof(opt("-m", "--missing", "0.1").c_str(), nullptr),
+                             (size_t)strtoull(opt("-d", "--depth", "4").c_str(), nullptr, 10), (size_t)strtoull(opt("-n", "--indel-kmers", "2").c_str(), nullptr, 10), threads);
+        if (r == SKX_EEMPTY) rcode = 1;                                                                          // extremities.rs: std::process::exit(1)
+        else if (r != SKX_OK) rcode = engine_fail();
     } else {
-        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov)");
+        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo)");
     }
     const double t_done = since();
     if (dbg) fprintf(stderr, "[skx] main: %s done after %.2f s\n", cmd.c_str(), t_done);

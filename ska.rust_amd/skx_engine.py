@@ -71,7 +71,8 @@ skx_array_merge skx_array_delete_samples skx_array_weed skx_keyset_from_fasta sk
 skx_comm_unique_id skx_comm_create skx_comm_create_local skx_comm_destroy skx_comm_rank skx_comm_world skx_comm_bytes_received skx_comm_transport skx_comm_barrier
 skx_comm_allgather skx_comm_allreduce_u32 skx_comm_gather_root skx_shard_range skx_pair_bands skx_keyset_allgather skx_array_reduce_stats skx_array_distance_sharded
 skh_build_sharded skh_align_sharded skh_distance_sharded
-skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf skh_load_array skh_sample_name skh_main skh_merge skh_delete skh_weed skh_cov skh_cov_fit skh_align_inputs_fd skh_distance_skf_tsv skh_help skh_log""".split()
+skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf skh_load_array skh_sample_name skh_main skh_merge skh_delete skh_weed skh_cov skh_cov_fit skh_align_inputs_fd skh_distance_skf_tsv skh_help skh_log
+skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo""".split()
 
 _lib = None
 
@@ -90,6 +91,12 @@ def load_library():
     lib.skx_last_error.restype = cp
     lib.skx_version.restype = cp
     lib.skx_ctx_create.argtypes = [i, pp]
+    lib.skx_array_lo_graph.argtypes = [vp, pp]
+    lib.skx_lo_graph_info.argtypes = [vp, C.POINTER(LoInfo)]
+    lib.skx_lo_graph_export.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.skx_lo_gather.argtypes = [vp, vp, u64, vp, vp]
+    lib.skx_lo_graph_free.argtypes = [vp]
+    lib.skh_lo.argtypes = [vp, cp, cp, cp, C.c_float, C.c_size_t, C.c_size_t, i]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -277,6 +284,65 @@ def sample_name(path):
     return s
 
 
+class LoInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("words_per_node", C.c_int32), ("n_samples", C.c_uint64), ("colour_words", C.c_uint64),
+                ("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("n_entries", C.c_uint64), ("n_colours", C.c_uint64), ("n_kmers", C.c_uint64)]
+
+
+def _to_ints(words, wpn):
+    """[n * wpn] little-endian 64-bit words -> list of Python ints"""
+    if wpn == 1:
+        return [int(x) for x in words]
+    return [int(words[2 * i]) | (int(words[2 * i + 1]) << 64) for i in range(len(words) // 2)]
+
+
+class LoGraph:
+    """`ska lo`'s device graph (skx_array_lo_graph): CSR arrays as numpy (wpn 64-bit words per node), colours on demand"""
+
+    def __init__(self, h):
+        self.h = h
+        inf = LoInfo()
+        _check(_lib.skx_lo_graph_info(h, C.byref(inf)))
+        self.info = {n: getattr(inf, n) for n, _ in LoInfo._fields_}
+        w, N, E, X = inf.words_per_node, inf.n_nodes, inf.n_edges, inf.n_entries
+        self.wpn = w
+        self.nodes = np.zeros(N * w, np.uint64)
+        self.offsets = np.zeros(N + 1, np.uint64)
+        self.neighbours = np.zeros(E * w, np.uint64)
+        self.entries = np.zeros(X * w, np.uint64)
+        self.exits = np.zeros(X * w, np.uint64)
+        _check(_lib.skx_lo_graph_export(h, self.nodes.ctypes.data, self.offsets.ctypes.data, self.neighbours.ctypes.data,
+                                        self.entries.ctypes.data, self.exits.ctypes.data))
+
+    def adjacency(self):
+        """{node: [neighbours]} as Python ints"""
+        nodes, nb = _to_ints(self.nodes, self.wpn), _to_ints(self.neighbours, self.wpn)
+        off = [int(x) for x in self.offsets]
+        return {n: nb[off[i]:off[i + 1]] for i, n in enumerate(nodes)}
+
+    def gather(self, kmers):
+        """full k-mers (Python ints) -> (colours as Python int bitsets, found flags)"""
+        n, w = len(kmers), self.wpn
+        q = np.zeros(max(1, n * w), np.uint64)
+        for i, x in enumerate(kmers):
+            for j in range(w):
+                q[i * w + j] = (x >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        W = self.info["colour_words"]
+        out = np.zeros(max(1, n * W), np.uint64)
+        found = np.zeros(max(1, n), np.uint8)
+        _check(_lib.skx_lo_gather(self.h, q.ctypes.data, n, out.ctypes.data, found.ctypes.data))
+        cols = [sum(int(out[i * W + t]) << (64 * t) for t in range(W)) for i in range(n)]
+        return cols, [bool(found[i]) for i in range(n)]
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.skx_lo_graph_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Context:
     def __init__(self, device=0):
         lib = load_library()
@@ -299,6 +365,12 @@ class Context:
     def merge_path(self):
         """'append64' / 'append128' / 'sorted: <why>': the kernels the last merge on this context went through"""
         return _lib.skx_ctx_merge_path(self.h).decode()
+
+    def lo_graph(self, array):
+        """skx_array_lo_graph: `ska lo`'s coloured de Bruijn graph of `array` (a device Array on this context)"""
+        h = C.c_void_p()
+        _check(_lib.skx_array_lo_graph(array.h, C.byref(h)))
+        return LoGraph(h)
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
