@@ -25,11 +25,21 @@ def enc_base(c):
     return (ord(c) >> 1) & 3
 
 
+BASE4 = str.maketrans({chr(c): str((c >> 1) & 3) for c in range(256)})     # enc_base as a base-4 digit
+
+
 def encode(s):
-    v = 0
-    for c in s:
-        v = (v << 2) | enc_base(c)
-    return v
+    return int(s.translate(BASE4), 4) if s else 0
+
+
+def windows(s, n):
+    """[encode(s[i:i + n]) for i in range(len(s) - n + 1)], cut from encode(s) as one integer"""
+    L = len(s)
+    if n > L:
+        return []
+    v = encode(s)
+    mask = (1 << (2 * n)) - 1
+    return [(v >> (2 * (L - n - i))) & mask for i in range(L - n + 1)]
 
 
 def decode(v, n):
@@ -163,7 +173,7 @@ def traverse(entry, edges, compacted, entries, exits, kg, max_depth):
             keep = paths if len(paths) == 2 else [p for p in paths if len(p) == mcl]
             group = []
             for p in keep:
-                seq = decode(entry, kg) + "".join(CODE[n & 3] for n in p[1:])
+                seq = decode(entry, kg) + "".join([CODE[n & 3] for n in p[1:]])
                 snps = []
                 for i, n in enumerate(p):
                     if n in entries and (len(p) < kg or i <= len(p) - kg):
@@ -281,8 +291,8 @@ def scan_variants(seqs, kg, kmap):
     fwd, rev = [], []
     for seq in seqs:
         for s, out in ((seq, fwd), (rev_compl(seq), rev)):
-            for pos in range(len(s) - kg + 1):
-                for p in kmap.get(encode(s[pos:pos + kg]), ()):
+            for pos, w in enumerate(windows(s, kg)):
+                for p in kmap.get(w, ()):
                     out.append((p - pos) & 0xFFFFFFFF)
     f = most_frequent_position(fwd) if fwd else (0, 0)
     r = most_frequent_position(rev) if rev else (0, 0)
@@ -335,7 +345,7 @@ def run(keys, variants, k, names, reference=None, missing=0.1, depth=4, indel_km
     out["_indels.vcf"], entries_indels, counts["indels"] = process_indels(indels, colours, names, kg, missing)
     for key in final_groups:
         final_groups[key] = [(s, p) for s, p in final_groups[key]
-                             if sum(1 for i in range(len(s) - kg) if encode(s[i:i + kg]) in entries_indels) <= indel_kmers]
+                             if sum(1 for w in windows(s, kg)[:-1] if w in entries_indels) <= indel_kmers]
     order = sorted(((key, len(v) / len(v[0][0])) for key, v in final_groups.items() if v), key=lambda t: (-t[1], t[0]))
     done, snps, not_positioned, counter = set(), {}, 0, 0
     for key, _ in order:

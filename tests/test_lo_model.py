@@ -1,6 +1,7 @@
 """tests/lo_model.py (the test-only restatement of `ska lo` with the engine's fixed orders) against the reference's own goldens
 (tests/skalo.rs), byte for byte -- on the CPU oracle's reader, before anything on the device is compared with it."""
 import os
+import random
 
 import pytest
 
@@ -35,6 +36,18 @@ def test_encoding_matches_the_reference():
     assert M.encode("ACTG") == 0b00011011
     assert M.decode(M.encode("GATTACA"), 7) == "GATTACA"
     assert M.rc(M.encode("AACG"), 4) == M.encode("CGTT")
+
+
+def test_windows_equals_encode_of_every_window():
+    rnd = random.Random(3)
+    # n = 32 and 62: the (k - 1)-windows of k = 33 and k = 63; 'N' and '-' encode like the reference's (c >> 1) & 3
+    for n in (1, 2, 4, 30, 31, 32, 40, 62, 63):
+        for length in (0, n - 1, n, n + 1, 3 * n + 7):
+            s = "".join(rnd.choice("ACGTACGTN-") for _ in range(max(length, 0)))
+            assert M.windows(s, n) == [M.encode(s[i:i + n]) for i in range(len(s) - n + 1)], (n, length)
+    assert M.windows("ACG", 4) == [] and M.windows("", 3) == []
+    assert M.windows("ACGT", 4) == [M.encode("ACGT")]
+    assert M.windows("ACG", 0) == [0, 0, 0, 0]
 
 
 def test_single_sample_has_no_entry_node():
