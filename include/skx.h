@@ -318,6 +318,19 @@ int  skx_lo_graph_export(const skx_lo_graph *g, uint64_t *nodes, uint64_t *offse
 int  skx_lo_gather(skx_lo_graph *g, const uint64_t *kmers, uint64_t n, uint64_t *colours, uint8_t *found);
 void skx_lo_graph_free(skx_lo_graph *g);
 
+/* ---- `ska distance --tree` (the reference has no call site: replaces scripts/cluster_dists.py --rapidnj) ----
+ * Neighbour joining (Saitou-Nei, Studier-Keppler Q) in float64 on the device.  Leaves are the nodes 0 .. n-1 in sample order, join t
+ * (0-based) makes node n + t.  With n nodes active and r[x] the sum of D[x][y] over them, a step joins the active pair that minimises
+ * Q(x, y) = (n-2) D[x][y] - r[x] - r[y], ties to the lowest (min id, max id); a < b by id, len_a = D[a][b]/2 + (r[a] - r[b]) / (2(n-2)),
+ * len_b = D[a][b] - len_a (raw: they may be negative on non-additive data); the new node is (D[a][k] + D[b][k] - D[a][b]) / 2 from k.
+ * The last record joins the two nodes left with len_a = D[a][b], len_b = 0; n = 2 has that record only.  The same input gives the same
+ * records bit for bit.  SKX_EINVAL with a message for n < 2, SKX_ENOMEM with one when the 8 n^2 byte matrix does not fit the device. */
+typedef struct { uint32_t a, b; double len_a, len_b; } skx_nj_join;
+/* joins: n_samples - 1 records.  d: upper triangle, pairs (i<j) row-major, as skx_array_distance writes it (its `distance` field is used) */
+int  skx_dist_nj(skx_ctx *ctx, const skx_dist *d, int n_samples, skx_nj_join *joins);
+/* the same on a full row-major n x n host matrix of doubles (symmetric, zero diagonal, finite; refused otherwise) */
+int  skx_matrix_nj(skx_ctx *ctx, const double *m, int n, skx_nj_join *joins);
+
 /* wall-clock phases of the host-side path (file reading + upload, .skf codec, FASTA writer ...), accumulated per name since the
  * last reset: a JSON object {"phase": seconds, ...} in first-use order (malloc'd, skx_free).  The reference has no counterpart;
  * bench.py's end_to_end leg and SKX_DEBUG read them.  skx_phase_add lets host glue above the ABI record its own phases. */

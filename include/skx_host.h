@@ -25,6 +25,25 @@ int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, i
                         double min_freq, int filter_ambig_as_missing, int fd);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
+/* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of
+ * the midpoint-rooted neighbour-joining tree (skx_dist_nj + skh_nj_newick), `clusters` = the prefix of <prefix>.clusters.csv and
+ * <prefix>.graph.dot (skh_distance_clusters at the two thresholds).  The reference leaves both to scripts/cluster_dists.py. */
+typedef struct { const char *tree, *clusters; double cluster_snps, cluster_mismatches; } skh_dist_extras;
+/* skh_distance_skf_tsv, and the extras from the same table */
+int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *extras, char **buf, uint64_t *len);
+/* the joins of skx_dist_nj / skx_matrix_nj over n leaves as one line of Newick (host only).  A negative raw length is written as 0 and the
+ * difference moved to the sibling branch of the same join, so the distance between the two joined nodes is kept (Kuhner-Felsenstein).
+ * Midpoint root: the two leaves with the largest path distance in the corrected tree (ties to the lowest (id, id)), the root half way
+ * along the path between them, on the first edge that reaches the half.  Children ordered by the lowest leaf id below them, lengths
+ * %.5f, ";" and a newline at the end; a name holding any of ()[]':;, or white space in single quotes with inner quotes doubled. */
+int skh_nj_newick(const char *const *names, const skx_nj_join *joins, int n, char **buf, uint64_t *len);
+/* single-linkage clusters of a distance table (host only; names[n], d = the n(n-1)/2 pairs of skx_array_distance).  A pair is an edge when
+ * its values as the TSV prints them (%.2f, %.5f, parsed back) satisfy snps <= max_snps && mismatches <= max_mismatches.  csv: header
+ * "id,Cluster__autocolour", clusters numbered from 1 by size descending (ties: lowest sample index), rows by cluster then sample index,
+ * names RFC 4180-quoted where they hold , " or a line break.  dot: "strict graph {", one node line per sample in sample order, one edge
+ * line per edge in table order, "}"; " and \ in a name escaped with \.  Either output pointer pair may be NULL. */
+int skh_distance_clusters(const char *const *names, const skx_dist *d, int n, double max_snps, double max_mismatches,
+                          char **csv, uint64_t *csv_len, char **dot, uint64_t *dot_len);
 /* generic_modes::distance (generic_modes.rs:136-189): two-stage filter, then the long-form TSV with the
  * VariantDist Display format "{:.2}\t{:.5}\t{}\t{}" (merge_ska_array.rs:57-65) */
 int skh_distance_tsv(skx_array *a, double min_freq, int filt_ambig, char **buf, uint64_t *len);
@@ -68,6 +87,7 @@ typedef struct {
     double min_freq;
     int filter_type, mask_ambig, ignore_const_gaps, filter_ambig_as_missing;    /* align (generic_modes.rs:112-131) */
     int filt_ambig;                                            /* distance: !--allow-ambiguous */
+    const skh_dist_extras *extras;                             /* distance: rank 0, which holds the table, also writes these (NULL: none) */
 } skh_job;
 /* `ska build`: one .skf per rank, <output>.part<r>of<N>.skf = the global rows x that rank's samples (each a valid MergeSkaArray;
  * `ska merge` joins them), or with merge_parts the one file generic_modes::save_skf would write */

@@ -61,7 +61,11 @@ const std::vector<Cmd> &commands()
           {"-m, --min-freq", "<MIN_FREQ>", "Minimum fraction of samples a k-mer has to appear in across the entire alignment [default: 0]"},
           {"--allow-ambiguous", "", "Don't filter out ambiguous bases and compute fractional distances"},
           {"--threads", "<THREADS>", THREADS},
-          {"--gpus", "<GPUS>", "(MI355X engine) Number of GPUs (with sequence files or -f and the build options)"}}},
+          {"--gpus", "<GPUS>", "(MI355X engine) Number of GPUs (with sequence files or -f and the build options)"},
+          {"--tree", "<FILE>", "(MI355X engine) Write the midpoint-rooted neighbour-joining tree of the distances (Newick) to this file"},
+          {"--clusters", "<PREFIX>", "(MI355X engine) Write single-linkage clusters to <PREFIX>.clusters.csv and their graph to <PREFIX>.graph.dot"},
+          {"--cluster-snps", "<N>", "(MI355X engine) Largest SNP distance that links two samples (with --clusters) [default: 10]"},
+          {"--cluster-mismatches", "<P>", "(MI355X engine) Largest mismatch proportion that links two samples (with --clusters) [default: 1.0]"}}},
         {"merge", "Combine multiple split k-mer files", "ska merge -o <OUTPUT> [SKF_FILES]...",
          {{"[SKF_FILES]...", "", "List of input split-kmer (.skf) files"}},
          {{"-o", "<OUTPUT>", "Output prefix"}}},

@@ -186,17 +186,61 @@ static int distance_text_names(const std::vector<const char *> &names, const skx
     for (auto &x : part) out += x;
     return to_buf(out, buf, len);
 }
-static int distance_table(skx_array *a, double constant, int filt_ambig, char **buf, uint64_t *len)
+static int write_text_file(const std::string &path, const char *buf, uint64_t len)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { skx_set_error("cannot create %s", path.c_str()); return SKX_EIO; }
+    const bool ok = fwrite(buf, 1, len, f) == len;
+    if (fclose(f) != 0 || !ok) { skx_set_error("cannot write %s", path.c_str()); return SKX_EIO; }
+    return SKX_OK;
+}
+// `ska distance --tree / --clusters`: the tree and the clusters of the table the command has just computed (x may be NULL)
+static int distance_extras(skx_ctx *ctx, const std::vector<const char *> &names, const skx_dist *d, const skh_dist_extras *x)
+{
+    if (!x) return SKX_OK;
+    const int S = (int)names.size();
+    int r = SKX_OK;
+    if (x->tree) {
+        std::vector<skx_nj_join> joins((size_t)std::max(S - 1, 1));
+        { Phase pn("distance.nj"); if ((r = skx_dist_nj(ctx, d, S, joins.data())) != SKX_OK) return r; }
+        Phase pt("distance.tree_text");
+        char *buf = nullptr; uint64_t len = 0;
+        if ((r = skh_nj_newick(names.data(), joins.data(), S, &buf, &len)) != SKX_OK) return r;
+        r = write_text_file(x->tree, buf, len);
+        skx_free(buf);
+        if (r != SKX_OK) return r;
+    }
+    if (x->clusters) {
+        Phase pc("distance.clusters");
+        char *csv = nullptr, *dot = nullptr; uint64_t nc = 0, nd = 0;
+        if ((r = skh_distance_clusters(names.data(), d, S, x->cluster_snps, x->cluster_mismatches, &csv, &nc, &dot, &nd)) != SKX_OK) return r;
+        r = write_text_file(std::string(x->clusters) + ".clusters.csv", csv, nc);
+        if (r == SKX_OK) r = write_text_file(std::string(x->clusters) + ".graph.dot", dot, nd);
+        skx_free(csv); skx_free(dot);
+    }
+    return r;
+}
+static int distance_table(skx_array *a, double constant, int filt_ambig, const skh_dist_extras *x, char **buf, uint64_t *len)
 {
     skx_array_info_t info; skx_array_info(a, &info);
     const uint64_t S = info.n_samples;
     std::vector<skx_dist> d(S * (S - 1) / 2 + 1);
     int r;
     { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance(a, constant, filt_ambig, d.data())) != SKX_OK) return r; }
+    if (x) {
+        std::vector<const char *> names(S);
+        for (uint64_t i = 0; i < S; i++) names[i] = skx_array_name(a, i);
+        if ((r = distance_extras(skx_array_ctx(a), names, d.data(), x)) != SKX_OK) return r;
+    }
     return distance_text(a, d, buf, len);
 }
 
 extern "C" int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len)
+{
+    return skh_distance_skf_tsv_extras(ctx, skf_file, min_freq, filt_ambig, nullptr, buf, len);
+}
+extern "C" int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *extras, char **buf,
+                                           uint64_t *len)
 {
     return skx_guarded([&]() -> int {
     skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
@@ -204,7 +248,7 @@ extern "C" int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double m
     skx_array *a = nullptr; int64_t removed = 0, constant = 0;
     int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
     if (r != SKX_OK) return r;
-    r = distance_table(a, (double)constant, filt_ambig, buf, len);
+    r = distance_table(a, (double)constant, filt_ambig, extras, buf, len);
     skx_array_free(a);
     return r;
     });
@@ -640,6 +684,7 @@ extern "C" int skh_distance_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job 
     if ((r = skx_array_distance_sharded(comm, arr, job->filt_ambig, (double)constant, d.data(), d.size())) != SKX_OK) return done(r);
     if (rank == 0) {
         std::vector<const char *> names(job->names, job->names + S);
+        if ((r = distance_extras(ctx, names, d.data(), job->extras)) != SKX_OK) return done(r);
         char *buf = nullptr; uint64_t len = 0;
         if ((r = distance_text_names(names, d.data(), &buf, &len)) != SKX_OK) return done(r);
         FILE *f = job->output ? fopen(job->output, "wb") : stdout;
@@ -663,7 +708,8 @@ struct Args {
 };
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
-                            "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers", nullptr};
+                            "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -766,6 +812,16 @@ int open_comm(skx_ctx *ctx, int rank, int world, skx_comm **out)
     }
     return skx_comm_create(ctx, rank, world, id, out);
 }
+// --tree / --clusters / --cluster-snps / --cluster-mismatches of `ska distance`
+struct DistExtras {
+    std::string tree, clusters; skh_dist_extras x{};
+    explicit DistExtras(const Args &a) : tree(a.get("--tree")), clusters(a.get("--clusters"))
+    {
+        x.tree = a.has("--tree") ? tree.c_str() : nullptr; x.clusters = a.has("--clusters") ? clusters.c_str() : nullptr;
+        x.cluster_snps = atof(a.get("--cluster-snps", "10").c_str()); x.cluster_mismatches = atof(a.get("--cluster-mismatches", "1.0").c_str());
+    }
+    const skh_dist_extras *get() const { return x.tree || x.clusters ? &x : nullptr; }
+};
 struct BuildOpts { int k = 31; skx_qual q{5, 20, SKX_QUAL_STRICT}; bool auto_count = false; double prop = 0.0; };
 int parse_build_opts(const Args &a, BuildOpts &o)                                      // cli.rs:27-108 (Build)
 {
@@ -975,6 +1031,8 @@ int main_sharded(skx_ctx *ctx, const std::string &cmd, const Args &a, int rank, 
     } else {
         job.min_freq = atof(a.get("--min-freq", a.get("-m", "0")).c_str());
         job.filt_ambig = !a.has("--allow-ambiguous");
+        const DistExtras dx(a);
+        job.extras = dx.get();
         r = skh_distance_sharded(ctx, comm, &job);
     }
     const int rcode = r == SKX_OK ? 0 : engine_fail();
@@ -1047,7 +1105,22 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (int e = parse_build_opts(a, bo)) return e;
     }
     if (cmd == "align") { if (!multi && a.pos.empty()) return clap_missing("align", "<INPUT>..."); if (int e = filter()) return e; if (int e = freq()) return e; }
-    else if (cmd == "distance") { if (!multi && a.pos.size() != 1) return a.pos.empty() ? clap_missing("distance", "<SKF_FILE>") : fail("one .skf file required"); if (int e = freq()) return e; }
+    else if (cmd == "distance") { if (!multi && a.pos.size() != 1) return a.pos.empty() ? clap_missing("distance", "<SKF_FILE>") : fail("one .skf file required"); if (int e = freq()) return e;
+        // the engine's own options (the reference's scripts/cluster_dists.py: --snps, --mismatches), refused the way clap refuses the others
+        for (auto names : {std::make_pair("--cluster-snps", "--cluster-snps <N>"), std::make_pair("--cluster-mismatches", "--cluster-mismatches <P>")}) {
+            if (!a.has(names.first)) continue;
+            const std::string v = a.get(names.first);
+            if (!a.has("--clusters")) {
+                fprintf(stderr, "error: the following required arguments were not provided:\n  --clusters <PREFIX>\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
+                return 2;
+            }
+            if (!lo_float(v)) return clap_invalid(v, names.second, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
+            const double t = strtod(v.c_str(), nullptr);
+            if (!(t >= 0.0)) return clap_invalid(v, names.second, "Threshold must be zero or higher");
+        }
+        for (const char *o : {"--tree", "--clusters"})
+            if (a.has(o) && a.get(o).empty()) return clap_invalid("", o[2] == 't' ? "--tree <FILE>" : "--clusters <PREFIX>", "a value is required");
+    }
     else if (cmd == "nk") { if (a.pos.empty()) return clap_missing("nk", "<SKF_FILE>"); }
     else if (cmd == "cov") { if (a.pos.size() < 2) return clap_missing("cov", a.pos.empty() ? "<FASTQ_FWD>\n  <FASTQ_REV>" : "<FASTQ_REV>"); if (int e = kmer("-k <K>")) return e; }
     else if (cmd == "map") {
@@ -1114,7 +1187,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1203,7 +1276,8 @@ extern "C" int skh_main(int argc, char **argv)
         const double mf = atof(a.get("--min-freq", a.get("-m", "0")).c_str());
         char *buf = nullptr; uint64_t len = 0;
         (void)in;
-        if (skh_distance_skf_tsv(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), &buf, &len) != SKX_OK)
+        const DistExtras dx(a);
+        if (skh_distance_skf_tsv_extras(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get(), &buf, &len) != SKX_OK)
             rcode = engine_fail();
         else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
     } else if (cmd == "nk") {

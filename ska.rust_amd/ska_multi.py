@@ -4,7 +4,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \\
         ska.rust_amd/ska_multi.py build    -f file_list.txt -o out -k 31 [--threads T] [--min-count C ...]
         ska.rust_amd/ska_multi.py align    -f file_list.txt -o aln.fa [-k 31] [--min-freq 0.9] [--filter no-const] ...
-        ska.rust_amd/ska_multi.py distance -f file_list.txt -o dists.tsv [-k 31] [--min-freq 0] [--allow-ambiguous]
+        ska.rust_amd/ska_multi.py distance -f file_list.txt -o dists.tsv [-k 31] [--min-freq 0] [--allow-ambiguous] [--tree F] [--clusters P]
 
 Samples are dealt to the ranks in contiguous shards (input order is kept, so names come out in CLI order, cf. the offset
 handling of merge_ska_dict.rs:243-253,277-291).  Nothing on the data path is collective; the exchanges are:
@@ -55,6 +55,10 @@ def parse():
     ap.add_argument("--ambig-mask", action="store_true")
     ap.add_argument("--no-gap-only-sites", action="store_true")
     ap.add_argument("--allow-ambiguous", action="store_true")
+    ap.add_argument("--tree", help="distance: rank 0 writes the midpoint-rooted neighbour-joining tree here")
+    ap.add_argument("--clusters", help="distance: rank 0 writes <prefix>.clusters.csv and <prefix>.graph.dot")
+    ap.add_argument("--cluster-snps", type=float, default=10.0)
+    ap.add_argument("--cluster-mismatches", type=float, default=1.0)
     ap.add_argument("--merge", action="store_true", help="build: rank 0 joins the per-rank files into <out>.skf")
     ap.add_argument("--report", help="rank 0 writes exchange sizes / times as JSON here")
     return ap.parse_args()
@@ -119,7 +123,8 @@ def main():
         comm.align(names, inputs, args.output, min_freq=0.9 if args.min_freq is None else args.min_freq, filter_type=FILTERS[args.filter],
                    mask_ambig=args.ambig_mask, ignore_const_gaps=args.no_gap_only_sites, filter_ambig_as_missing=args.filter_ambig_as_missing, **common)
     else:
-        comm.distance(names, inputs, args.output, min_freq=0.0 if args.min_freq is None else args.min_freq, filt_ambig=not args.allow_ambiguous, **common)
+        comm.distance(names, inputs, args.output, min_freq=0.0 if args.min_freq is None else args.min_freq, filt_ambig=not args.allow_ambiguous,
+                      tree=args.tree, clusters=args.clusters, cluster_snps=args.cluster_snps, cluster_mismatches=args.cluster_mismatches, **common)
     rep["total_s"] = time.perf_counter() - t0
     rep["bytes_received_rank0"] = comm.bytes_received
     rep["phases_rank0"] = E.phases()

@@ -20,6 +20,7 @@ OK, EINVAL, EIO, ENODEV, ENOMEM, EEMPTY, EUNSUP, EFORMAT = range(8)
 
 KEY_DT = np.dtype([("lo", "<u8"), ("hi", "<u8")])
 DIST_DT = np.dtype([("distance", "<f8"), ("mismatch_prop", "<f8"), ("match_count", "<u8"), ("mismatch_count", "<u8")])
+NJ_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("len_a", "<f8"), ("len_b", "<f8")])      # skx_nj_join
 
 
 class Qual(C.Structure):
@@ -51,7 +52,12 @@ class Job(C.Structure):
                 ("k", C.c_int), ("rc", C.c_int), ("qual", Qual), ("threads", C.c_int), ("proportion_reads", C.c_double),
                 ("output", C.c_char_p), ("merge_parts", C.c_int), ("min_freq", C.c_double),
                 ("filter_type", C.c_int), ("mask_ambig", C.c_int), ("ignore_const_gaps", C.c_int), ("filter_ambig_as_missing", C.c_int),
-                ("filt_ambig", C.c_int)]
+                ("filt_ambig", C.c_int), ("extras", C.c_void_p)]
+
+
+class DistExtras(C.Structure):
+    """skh_dist_extras (include/skx_host.h): what `ska distance` writes besides its table"""
+    _fields_ = [("tree", C.c_char_p), ("clusters", C.c_char_p), ("cluster_snps", C.c_double), ("cluster_mismatches", C.c_double)]
 
 
 class EngineError(RuntimeError):
@@ -72,7 +78,8 @@ skx_comm_unique_id skx_comm_create skx_comm_create_local skx_comm_destroy skx_co
 skx_comm_allgather skx_comm_allreduce_u32 skx_comm_gather_root skx_shard_range skx_pair_bands skx_keyset_allgather skx_array_reduce_stats skx_array_distance_sharded
 skh_build_sharded skh_align_sharded skh_distance_sharded
 skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf skh_load_array skh_sample_name skh_main skh_merge skh_delete skh_weed skh_cov skh_cov_fit skh_align_inputs_fd skh_distance_skf_tsv skh_help skh_log
-skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo""".split()
+skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo
+skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras""".split()
 
 _lib = None
 
@@ -97,6 +104,11 @@ def load_library():
     lib.skx_lo_gather.argtypes = [vp, vp, u64, vp, vp]
     lib.skx_lo_graph_free.argtypes = [vp]
     lib.skh_lo.argtypes = [vp, cp, cp, cp, C.c_float, C.c_size_t, C.c_size_t, i]
+    lib.skx_dist_nj.argtypes = [vp, vp, i, vp]
+    lib.skx_matrix_nj.argtypes = [vp, vp, i, vp]
+    lib.skh_nj_newick.argtypes = [C.POINTER(cp), vp, i, pp, C.POINTER(u64)]
+    lib.skh_distance_clusters.argtypes = [C.POINTER(cp), vp, i, d, d, pp, C.POINTER(u64), pp, C.POINTER(u64)]
+    lib.skh_distance_skf_tsv_extras.argtypes = [vp, cp, d, i, C.POINTER(DistExtras), pp, C.POINTER(u64)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -372,6 +384,33 @@ class Context:
         _check(_lib.skx_array_lo_graph(array.h, C.byref(h)))
         return LoGraph(h)
 
+    def dist_nj(self, dist, n_samples):
+        """skx_dist_nj: neighbour joining on the `distance` field of a pair table (DIST_DT, n(n-1)/2 pairs) -> n - 1 join records (NJ_DT)"""
+        dist = np.ascontiguousarray(dist, DIST_DT)
+        if n_samples >= 2 and dist.size != n_samples * (n_samples - 1) // 2:
+            raise ValueError("the table does not hold n(n-1)/2 pairs")
+        joins = np.zeros(max(n_samples - 1, 1), NJ_DT)
+        _check(_lib.skx_dist_nj(self.h, _np_ptr(dist), n_samples, _np_ptr(joins)))
+        return joins[: n_samples - 1]
+
+    def matrix_nj(self, matrix):
+        """skx_matrix_nj: the same on a full symmetric n x n float64 matrix with a zero diagonal"""
+        m = np.ascontiguousarray(matrix, np.float64)
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError("a square matrix is required")
+        n = m.shape[0]
+        joins = np.zeros(max(n - 1, 1), NJ_DT)
+        _check(_lib.skx_matrix_nj(self.h, _np_ptr(m), n, _np_ptr(joins)))
+        return joins[: n - 1]
+
+    def distance_skf_tsv(self, skf_file, min_freq=0.0, filt_ambig=True, tree=None, clusters=None, cluster_snps=10.0, cluster_mismatches=1.0):
+        """`ska distance <skf> [--tree FILE] [--clusters PREFIX ...]` (skh_distance_skf_tsv_extras) -> the table's text"""
+        x = DistExtras(tree.encode() if tree else None, clusters.encode() if clusters else None, cluster_snps, cluster_mismatches)
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.skh_distance_skf_tsv_extras(self.h, skf_file.encode(), min_freq, int(filt_ambig), C.byref(x) if tree or clusters else None,
+                                                C.byref(p), C.byref(n)))
+        return _take(p, n)
+
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.skx_ctx_destroy(self.h)
@@ -389,6 +428,32 @@ def default_context():
     if _default_ctx is None:
         _default_ctx = Context(int(os.environ.get("LOCAL_RANK", "0")) if os.environ.get("SKX_USE_LOCAL_RANK") else 0)
     return _default_ctx
+
+
+def nj_newick(names, joins):
+    """skh_nj_newick: the joins of Context.dist_nj / matrix_nj as one line of midpoint-rooted Newick (host only)"""
+    load_library()
+    n = len(names)
+    j = np.ascontiguousarray(joins, NJ_DT)
+    if j.size != n - 1:
+        raise ValueError("n - 1 join records are required")
+    arr = (C.c_char_p * n)(*[x.encode() for x in names])
+    p, ln = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_nj_newick(arr, _np_ptr(j), n, C.byref(p), C.byref(ln)))
+    return _take(p, ln).decode()
+
+
+def distance_clusters(names, dist, max_snps=10.0, max_mismatches=1.0):
+    """skh_distance_clusters: single-linkage clusters of a pair table -> (clusters.csv text, graph.dot text) (host only)"""
+    load_library()
+    n = len(names)
+    d = np.ascontiguousarray(dist, DIST_DT)
+    if d.size != n * (n - 1) // 2:
+        raise ValueError("the table does not hold n(n-1)/2 pairs")
+    arr = (C.c_char_p * n)(*[x.encode() for x in names])
+    pc, nc, pd, nd = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_distance_clusters(arr, _np_ptr(d) if d.size else None, n, max_snps, max_mismatches, C.byref(pc), C.byref(nc), C.byref(pd), C.byref(nd)))
+    return _take(pc, nc).decode(), _take(pd, nd).decode()
 
 
 def record_stream(records):
@@ -523,9 +588,13 @@ class Comm:
         j.min_freq, j.filter_type, j.mask_ambig, j.ignore_const_gaps, j.filter_ambig_as_missing = min_freq, filter_type, int(mask_ambig), int(ignore_const_gaps), int(filter_ambig_as_missing)
         _check(_lib.skh_align_sharded(self.ctx.h, self.h, C.byref(j)))
 
-    def distance(self, names, inputs, output, k=31, rc=True, q=None, threads=1, proportion_reads=0.0, min_freq=0.0, filt_ambig=True):
+    def distance(self, names, inputs, output, k=31, rc=True, q=None, threads=1, proportion_reads=0.0, min_freq=0.0, filt_ambig=True,
+                 tree=None, clusters=None, cluster_snps=10.0, cluster_mismatches=1.0):
         j, keep = self._job(names, inputs, k, rc, q, threads, proportion_reads, output)
         j.min_freq, j.filt_ambig = min_freq, int(filt_ambig)
+        if tree or clusters:                             # rank 0, which holds the table, writes them
+            x = DistExtras(tree.encode() if tree else None, clusters.encode() if clusters else None, cluster_snps, cluster_mismatches)
+            j.extras = C.cast(C.pointer(x), C.c_void_p)
         _check(_lib.skh_distance_sharded(self.ctx.h, self.h, C.byref(j)))
 
     def free(self):
