@@ -1,13 +1,11 @@
 // skx_api.cpp -- the C ABI (include/skx.h): host orchestration of the gfx950 kernels for build -> merge -> filter -> distance and the
-// .skf life-cycle operations (cov / map / .skf files: skx_api_io.cpp).
+// .skf life-cycle operations (cov / map / .skf files: skx_api_io.cpp; sequence files onto the device: skx_build_files.cpp).
 // No CPU fallback exists: without a usable HIP device every compute entry point fails with SKX_ENODEV.
 #include "skx_internal.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <deque>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -295,8 +293,8 @@ extern "C" int skx_dictset_key_bits(const skx_dictset *d) { return d->key_bits; 
 // The passing windows' packed words of every sample (reads_sample_words) -> (sample, bucket) regions like an assembly's -> the same dedupe
 // kernel: sorted, folded, sub-indexed regions, so union / assemble treat reads and assemblies alike.  SKF_NOT_TAKEN: regions the LDS
 // sort cannot hold (the sort-based form takes the batch).
-static int reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std::vector<DevBuf<uint64_t>> &wh2, const std::vector<uint64_t> &cnt,
-                                  int k, int rc, skx_dictset **out)
+int skx::reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std::vector<DevBuf<uint64_t>> &wh2, const std::vector<uint64_t> &cnt,
+                                int k, int rc, skx_dictset **out)
 {
     const int n = (int)wl.size();
     hipStream_t st = ctx->stream;
@@ -466,6 +464,35 @@ int skx::dictset_sort(skx_dictset *d)
     return SKX_OK;
 }
 
+// The region layout of an assembly batch from its longest sample: how many buckets a sample's words are split into, and the fixed capacity of a region.
+uint32_t skx::region_capacity(uint64_t maxlen, int logB)
+{
+    // hashed buckets are Poisson around len/B: 20 % + 256 words of head-room covers ordinary repeat content
+    const uint64_t mean = (maxlen >> logB) + 1;
+    return (uint32_t)std::min<uint64_t>(((mean + mean / 5 + 256) + 63) / 64 * 64, 0x7FFFFFFFull);
+}
+RegionLayout skx::region_layout(uint64_t maxlen, int k)
+{
+    const bool wide = k > 31;
+    // windows per bucket (upper bound): the 64-bit dedupe sorts up to 6 144 words per region in LDS and the regions get 20 % + 256
+    // words of head-room, so 4 900 is the largest mean that fits -- and the largest buckets give the scatter its widest chunks
+    // (128-bit keys: 3 200, so that a region's fixed capacity -- 20 % + 256 above the mean -- stays within the 4 096 words of the wide counting sort
+    // and the samples can stay as extracted for the append pass whatever their length)
+    uint64_t per_region = wide ? 3200 : 4900;
+    if (knob("per_region") > 0) per_region = (uint64_t)knob("per_region");       // (measurements: 9800 = 2^9 regions for 5 Mbp samples, 2450 = 2^11)
+    // Longer samples (round 6): the bucket count stops growing at the 5 Mbp shape (2^10 regions; 2^11 for 128-bit keys) and the regions grow
+    // instead -- the extraction kernel's (tile, bucket) chunks stay whole lines (with regions capped at 4 900 words a 20 Mbp sample took 13 ps per
+    // base against 2.5, a 40 Mbp one 43, and beyond that the assembly kernels were left altogether), the append pass reads regions of any
+    // size unsorted (2^(logQ - logB) row blocks per region: up to 32 readers a region), and who asks for sorted dictionaries of such samples
+    // gets the flat sorted form (dictset_sort_flat).  Beyond 32 row blocks per region the buckets grow again (to 2^13: ~1.3 Gbp).
+    const int need = std::max(0, ilog2_ceil((maxlen + per_region - 1) / per_region));
+    const int base_logB = knob("per_region") > 0 ? std::min(need, MAX_LOGB) : (wide ? 11 : 10);
+    const bool grow_regions = !knob("small_regions");
+    if ((grow_regions ? need - 5 : need) > MAX_LOGB) return {-1, 0};
+    const int logB = std::max(0, std::min({grow_regions && need > base_logB ? std::max(base_logB, need - 5) : need, 2 * (k - 1), MAX_LOGB}));
+    return {logB, region_capacity(maxlen, logB)};
+}
+
 static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *> &seqs, const std::vector<const uint8_t *> &quals,
                                 const std::vector<uint64_t> &lens, int k, int rc, const skx_qual *q, skx_dictset **out)
 {
@@ -535,24 +562,9 @@ static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *>
     HashParams hp = make_hash_params(std::min(k, 31));
     WideHash wh = make_wide_hash(k);
     const int key_bits_used = 2 * (k - 1);
-    // windows per bucket (upper bound): the 64-bit dedupe sorts up to 6 144 words per region in LDS and the regions get 20 % + 256
-    // words of head-room, so 4 900 is the largest mean that fits -- and the largest buckets give the scatter its widest chunks
-    // (128-bit keys: 3 200, so that a region's fixed capacity -- 20 % + 256 above the mean -- stays within the 4 096 words of the wide counting sort
-    // and the samples can stay as extracted for the append pass whatever their length)
-    uint64_t per_region = wide ? 3200 : 4900;
-    if (knob("per_region") > 0) per_region = (uint64_t)knob("per_region");       // (measurements: 9800 = 2^9 regions for 5 Mbp samples, 2450 = 2^11)
     if (any_qual) return build_reads();
-    // Longer samples (round 6): the bucket count stops growing at the 5 Mbp shape (2^10 regions; 2^11 for 128-bit keys) and the regions grow
-    // instead -- the extraction kernel's (tile, bucket) chunks stay whole lines (with regions capped at 4 900 words a 20 Mbp sample took 13 ps per
-    // base against 2.5, a 40 Mbp one 43, and beyond that the assembly kernels were left altogether), the append pass reads regions of any
-    // size unsorted (2^(logQ - logB) row blocks per region: up to 32 readers a region), and who asks for sorted dictionaries of such samples
-    // gets the flat sorted form (dictset_sort_flat).  Beyond 32 row blocks per region the buckets grow again (to 2^13: ~1.3 Gbp).
-    const int need = std::max(0, ilog2_ceil((maxlen + per_region - 1) / per_region));
-    const int base_logB = knob("per_region") > 0 ? std::min(need, MAX_LOGB) : (wide ? 11 : 10);
-    const bool grow_regions = !knob("small_regions");
-    if ((grow_regions ? need - 5 : need) > MAX_LOGB) return build_reads();
-    int logB = std::min({grow_regions && need > base_logB ? std::max(base_logB, need - 5) : need, key_bits_used, MAX_LOGB});
-    if (logB < 0) logB = 0;
+    int logB = region_layout(maxlen, k).logB;
+    if (logB < 0) return build_reads();
 
     DevBuf<const uint8_t *> d_seqs, d_quals;
     DevBuf<uint64_t> d_lens;
@@ -581,9 +593,7 @@ static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *>
         a.logB = logB; a.hp = hp; a.wh = wh; a.overflow = d_flag.p;
         uint32_t lds_cap;
         if (!exact) {
-            // hashed buckets are Poisson around len/B: 20 % + 256 words of head-room covers ordinary repeat content
-            const uint64_t mean = (maxlen >> logB) + 1;
-            const uint32_t region_cap = (uint32_t)std::min<uint64_t>(((mean + mean / 5 + 256) + 63) / 64 * 64, 0x7FFFFFFFull);
+            const uint32_t region_cap = region_capacity(maxlen, logB);
             launch_fill_offsets(d->off.p, nreg, region_cap, st);
             SKX_TRY(d->words.alloc(nreg * (uint64_t)region_cap * wpk + 2048));      // (+ slack: the append pass reads whole chunks of up to 12 KB)
             { StageTimer t(ctx, &ctx->tm.scatter); a.hist = d->raw.p; a.off = d->off.p; a.words = d->words.p; a.capacity = region_cap;
@@ -686,627 +696,6 @@ extern "C" int skx_dictset_build(skx_ctx *ctx, const skx_stream *samples, int n,
     });
 }
 
-
-// A read set's records -> the five bit planes (groups of 64 positions x 5 words: two code bits, the bytes valid_base rejects, line ends,
-// quality verdicts), fed line by line from stream_fastq_file; `push` takes a finished group.  Used by the reader threads that pack on the
-// host and by the consumer when the device's framing calls a sample irregular (then it is this code that accepts or refuses the file).
-namespace {
-struct PlanePacker {
-    std::vector<uint64_t> pl;                                           // a record's four planes (sequence line, then its quality line)
-    size_t line_n = 0;
-    uint64_t cur[5] = {0, 0, 0, 0, 0}, pos = 0, cap = 0;                // the group being filled; positions so far; the most that may come
-    int min_qual = 20; bool gz = false;
-    std::function<int(const uint64_t *)> push;
-    static constexpr int OVER_BOUND = -1002;                            // a gzip file longer than its trailer says: not an error of the input
-    int emit(int which, const uint8_t *p, size_t nb)
-    {
-        const size_t words = (nb + 1 + 63) / 64;                        // the line and its end
-        if (which == 0) {
-            if (pos + nb + 1 > cap) { if (gz) return OVER_BOUND; skx::set_error("Invalid FASTA/Q record"); return SKX_EIO; }
-            if (pl.size() < 4 * words) pl.resize(4 * words + 64);
-            line_n = nb;
-            for (int pln = 0; pln < 4; pln++) pl[pln * words + words - 1] = 0;
-            skx::pack_bases_planes(p, nb, &pl[0], &pl[words], &pl[2 * words]);
-            return SKX_OK;
-        }
-        if (nb != line_n) { skx::set_error("Invalid FASTA/Q record"); return SKX_EIO; }
-        skx::pack_qual_plane(p, nb, min_qual, &pl[3 * words]);
-        const uint64_t *lo = &pl[0], *hi = &pl[words], *bd = &pl[2 * words], *qb = &pl[3 * words];
-        for (size_t w = 0; w < words; w++) {
-            const unsigned take = (unsigned)std::min<size_t>(64, nb + 1 - 64 * w), off = (unsigned)(pos & 63);
-            const uint64_t v[5] = {lo[w], hi[w], bd[w], nb / 64 == w ? 1ull << (nb & 63) : 0ull, qb[w]};
-            for (int pln = 0; pln < 5; pln++) cur[pln] |= v[pln] << off;
-            pos += take;
-            if (off + take >= 64) {
-                const int pr = push(cur); if (pr != SKX_OK) return pr;
-                for (int pln = 0; pln < 5; pln++) cur[pln] = off ? v[pln] >> (64 - off) : 0ull;      // (what did not fit; bits beyond `take` are zero)
-            }
-        }
-        return SKX_OK;
-    }
-    int finish() { return (pos & 63) ? push(cur) : SKX_OK; }           // the last, partly filled group
-};
-}  // namespace
-
-// Read sets (every sample plain FASTQ, one or two files), pipelined.  The one-shot form below reads every sample, allocates stream buffers the
-// size of all files together (24 GB for 96 isolates of BASELINE config 5's shape: a 1-3 s allocation when the memory has just been released
-// by another process) and then filters one isolate after the other (11 ms each) on an idle PCIe link.  Here a small pool of stream slots
-// (two device buffers per slot, sized for the largest sample) is filled by the reader threads through the pinned ring, and this thread runs a
-// sample's window / count-filter kernels (reads_sample_words) as soon as its last piece has arrived, then hands the slot back: reading,
-// upload and kernels overlap, and the device holds a few samples' text instead of all of it.  Results are those of the one-shot form
-// (the per-sample kernels do not depend on the order samples arrive in).  SKF_NOT_TAKEN: not this kind of input, or a sample the
-// partition kernels leave to the sort-based form -- the caller takes the one-shot path from the start.
-static int build_reads_pipelined(skx_ctx *ctx, const char *const *file1, const char *const *file2, int n, int k, int rc, const skx_qual *q, int threads,
-                                 skx_dictset **out)
-{
-    if (knob("no_reads_pipeline") || n < 2) return SKF_NOT_TAKEN;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> bound(n, 0), text_bytes(n, 0);
-    struct GzSizes { uint64_t comp[2] = {0, 0}, hint[2] = {0, 0}; int files = 0, gz_files = 0; };
-    std::vector<GzSizes> gzs(n);                                                // (a sample whose files are all gzip may be inflated on the device)
-    uint64_t slot_bytes = 0, raw_cap = 0, comp_cap = 0;
-    bool any_gz = false;
-    constexpr int SKF_OVER_BOUND = PlanePacker::OVER_BOUND;
-    for (int i = 0; i < n; i++) {
-        uint64_t bytes = 0;
-        for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-            if (!f) continue;
-            struct stat sb; unsigned char c0[2] = {0, 0}, tail[4] = {0, 0, 0, 0};
-            const int fd = ::open(f, O_RDONLY);
-            bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && ::read(fd, c0, 2) == 2;
-            uint64_t plain = ok ? (uint64_t)sb.st_size : 0;
-            if (ok && c0[0] == 0x1f && c0[1] == 0x8b) {
-                // gzip: the reader thread inflates as it goes; the stream's size from the trailer (ISIZE, the last member's length mod 2^32).  A
-                // batch in which a file turns out longer than that says is left to the one-shot form (SKF_OVER_BOUND below)
-                ok = sb.st_size > 18 && pread(fd, tail, 4, sb.st_size - 4) == 4;
-                plain = (uint64_t)tail[0] | ((uint64_t)tail[1] << 8) | ((uint64_t)tail[2] << 16) | ((uint64_t)tail[3] << 24);
-                // a trailer that cannot be the whole text (shorter than the file itself): several members -- bgzip's 64 KB blocks, files
-                // joined with cat -- or 4 GB and more.  Six times the file's size then stands for the text's length (reads deflate 3-5 x);
-                // a text that turns out longer sends the batch to the one-shot form like any file longer than its bound
-                if (ok && plain < (uint64_t)sb.st_size) plain = 6 * (uint64_t)sb.st_size;
-                any_gz = true;
-                gzs[i].gz_files++;
-            } else ok = ok && c0[0] == '@';
-            if (fd >= 0) ::close(fd);
-            if (!ok) return SKF_NOT_TAKEN;
-            if (gzs[i].files < 2) { gzs[i].comp[gzs[i].files] = (uint64_t)sb.st_size; gzs[i].hint[gzs[i].files] = plain; }
-            gzs[i].files++;
-            bytes += plain;
-        }
-        if (gzs[i].gz_files == gzs[i].files) comp_cap = std::max<uint64_t>(comp_cap, ((gzs[i].comp[0] + 64 + 255) & ~255ull) + (gzs[i].files > 1 ? ((gzs[i].comp[1] + 64 + 255) & ~255ull) : 0ull));
-        bound[i] = (bytes / 2 + 64 + 255) & ~255ull;                             // plain FASTQ holds at most half its bytes in either stream
-        text_bytes[i] = bytes;
-        slot_bytes = std::max(slot_bytes, bound[i]);
-        raw_cap = std::max(raw_cap, bytes);
-    }
-    SKX_HIP(hipSetDevice(ctx->device));
-    const int nt = std::max(1, std::min({threads, n, 64, cpu_budget()}));      // (parsing + packing: a reader keeps a CPU busy)
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    // a slot per reader thread and a few waiting for their kernels: more only costs allocation time (64 slots = 17 GB took 4.7 s right after
-    // another process had released the memory, 32 slots 0.26 s: profiles/r03zr_reads_pipeline_512.log)
-    // A sample crosses PCIe in one of two forms, chosen by its reader thread when it starts on it (round 6):
-    //   * PACKED -- bit planes, groups of 64 positions, five words each: two code bits, the bases valid_base rejects, the line ends, the quality
-    //     verdicts (fastx.cpp pack_*_planes) -- framed and packed by the reader thread: 5 bits per position instead of two bytes, 157 MB per 50x
-    //     isolate, 0.1-0.3 s of a CPU;
-    //   * RAW -- the file's bytes as read() delivers them (0.55 GB per 50x isolate), the reader thread does nothing else; the device frames the
-    //     records and makes the same planes (skx_fastq.hip).
-    // Raw text alone is bound by the link (~32 GB/s with the readers running = 60 isolates/s), packing alone by the CPUs (16 of them: 40-80
-    // isolates/s); a reader takes RAW while the pinned ring has room -- the link is keeping up -- and PACKED when it is filling up, so
-    // both are busy.  SKX_KNOBS=reads_raw=1: never raw; =2: always.  The window pass and the rebuild of the passing windows' words read the planes
-    // as they are, whoever made them.
-    //   * GZDEV (gzip files) -- the COMPRESSED bytes as read() delivers them, half to a fifth of the text: the reader thread does nothing else, and
-    //     the device inflates (skx_gzdev.hip: block finder, symbolic decode per 64 KB chunk, window maps, text, member lengths and CRCs), frames and
-    //     packs.  A file the device does not vouch for (damaged, unusual header, a stretch that deflates beyond the symbol area) goes through the
-    //     reader threads' inflater on this thread, which accepts it or words the error.  SKX_KNOBS=reads_gz=1: inflate on the reader threads.
-    const long raw_knob = knob("reads_raw");
-    const bool raw_possible = raw_knob != 1 && raw_cap + 2 < 0xFFFFFF00ull;
-    //     Both inflaters work at once: a few reader threads (gz_feed of them) only feed the device -- a 50x isolate is 0.1-0.3 s of read() for them
-    //     and ~50 ms of the device's inflater -- and the others inflate and hand over text or planes as before (~1.1 s of a thread an isolate);
-    //     all take their samples from the same counter, so the split follows the two rates.  reads_gz=2: the device only.
-    const long gz_knob = knob("reads_gz");
-    const bool gz_device = any_gz && raw_possible && comp_cap > 0 && gz_knob != 1;
-    const int gz_tail = (int)(knob("reads_gz_tail") > 0 ? knob("reads_gz_tail") : 20);
-    const int gz_feed = !gz_device ? 0 : gz_knob == 2 ? 1 << 30 : (int)std::max<long>(1, knob("reads_gz_feed") > 0 ? knob("reads_gz_feed") : 3);
-    int n_gz_samples = 0;
-    for (int i = 0; i < n; i++) if (gz_device && gzs[i].gz_files == gzs[i].files) n_gz_samples++;
-    const uint64_t pslot_bytes = ((slot_bytes / 64 + 2) * READ_GROUP_BYTES + 255) & ~255ull;
-    const uint64_t rslot_bytes = raw_possible ? ((raw_cap + 2 + 64 + 255) & ~255ull) : 0;
-    // Two pools of device slots: packed samples (157 MB each at 50x of 5 Mbp; a reader each and a few waiting for their kernels) and raw ones
-    // (0.55 GB each: a few -- the link carries about one at a time -- plus ONE buffer for the planes the device makes of them, since the
-    // kernels take a sample at a time).  Kept small on purpose: a pool of 24 slots that hold either form is 17 GB, and allocating that right
-    // after another process has released its memory took 1.4-1.9 s of a 3 s build (profiles/r06b_reads_modes.log).
-    int P = (int)std::min<uint64_t>((uint64_t)n, std::max<uint64_t>(2, std::min<uint64_t>((uint64_t)nt + 8, (free_b / 8) / (pslot_bytes + 1))));
-    // raw slots: up to one per reader and two waiting for their kernels (a reader holds its slot for as long as it reads -- 0.1 s of a file read
-    // before, 0.25 s of one read for the first time, when sixteen read()s contend for the page cache's LRU lock -- so six slots carried 24 raw
-    // samples a second at most and the link idled at 12 GB/s: profiles/r06d_reads_1000.log).  They are allocated one by one by a helper thread
-    // while the pipeline already runs on the packed pool: 11 GB taken at once right after another process released its memory cost 1.4-1.9 s.
-    const int R = raw_possible ? (int)std::min<uint64_t>((uint64_t)n, std::max<uint64_t>(2, std::min<uint64_t>(raw_knob == 2 || (any_gz && !gz_device) ? (uint64_t)nt + 2 : gz_device ? (uint64_t)std::max(1, (nt - std::min(gz_feed, nt)) / 2) + 2 : (uint64_t)std::max(1, nt / 8) + 3, (free_b / 8) / (rslot_bytes + 1)))) : 0;      // (beside the device's inflater: half the inflating readers send text, the others planes)
-    // slots for compressed samples: one per reader and a few waiting for the inflater (0.27 GB each at 50x of 5 Mbp); the text the device makes of
-    // a sample lives in ONE buffer (the kernels take a sample at a time)
-    const uint64_t gslot_bytes = gz_device ? comp_cap : 0;
-    const int G = gz_device ? (int)std::min<uint64_t>((uint64_t)n_gz_samples, std::max<uint64_t>(2, std::min<uint64_t>((uint64_t)std::min(gz_feed, nt) + 3, (free_b / 8) / (gslot_bytes + 1)))) : 0;
-    if (raw_knob == 2) P = 1;
-    DevBuf<uint8_t> packed_pool, raw_planes, gz_text;
-    std::vector<DevBuf<uint8_t>> raw_slots((size_t)R), gz_slots((size_t)G);
-    SKX_TRY(packed_pool.alloc((uint64_t)P * pslot_bytes));
-    if (R) { SKX_TRY(raw_planes.alloc(pslot_bytes)); SKX_TRY(raw_slots[0].alloc(rslot_bytes)); }
-    if (G) { SKX_TRY(gz_text.alloc(rslot_bytes)); SKX_TRY(gz_slots[0].alloc(gslot_bytes)); }
-    constexpr size_t SLOT = ((8u << 20) / READ_GROUP_BYTES) * READ_GROUP_BYTES;          // whole groups
-    constexpr size_t RAW_CHUNK = (SLOT - 1) / 256 * 256;                                 // raw text leaves in pieces that keep their destinations aligned
-    const int min_qual_host = q ? (int)q->min_qual : 20;
-    const int n_slots = 2 * nt + 8;
-    struct Sample { int slot = -1; int pending = 0; bool read_done = false, queued = false, raw = false, gzdev = false; uint64_t len = 0, junction = 0, coff[2] = {0, 0}; };
-    struct Ring {
-        uint8_t *base = nullptr; std::mutex mu; std::condition_variable cv_free, cv_work, cv_stream, cv_ready;
-        std::vector<int> free_slots, free_stream, free_raw, free_gz; struct Req { int slot; uint8_t *dst; size_t bytes; int sample; }; std::deque<Req> work;
-        std::deque<int> ready; int readers_left = 0, up_pending = 0, raw_active = 0, gz_active = 0; bool failed = false, abort = false, prefer_packed = false;
-        ~Ring() { if (base) (void)hipHostFree(base); }
-    } ring;
-    if (hipHostMalloc((void **)&ring.base, (size_t)n_slots * SLOT, hipHostMallocDefault) != hipSuccess) { ring.base = nullptr; return SKF_NOT_TAKEN; }
-    for (int b = 0; b < n_slots; b++) ring.free_slots.push_back(b);
-    for (int p = 0; p < P; p++) ring.free_stream.push_back(p);
-    if (R) ring.free_raw.push_back(0);
-    if (G) ring.free_gz.push_back(0);
-    ring.readers_left = nt;
-    std::thread raw_alloc([&]() {
-        (void)hipSetDevice(ctx->device);
-        for (int p = 1; p < G; p++) {
-            { std::lock_guard<std::mutex> lk(ring.mu); if (ring.abort || ring.readers_left == 0) break; }
-            if (gz_slots[(size_t)p].alloc(gslot_bytes) != SKX_OK) break;
-            { std::lock_guard<std::mutex> lk(ring.mu); ring.free_gz.push_back(p); }
-            ring.cv_stream.notify_all();
-        }
-        for (int p = 1; p < R; p++) {
-            { std::lock_guard<std::mutex> lk(ring.mu); if (ring.abort || ring.readers_left == 0) break; }
-            if (raw_slots[(size_t)p].alloc(rslot_bytes) != SKX_OK) break;               // (no room: the pipeline goes on with what there is)
-            { std::lock_guard<std::mutex> lk(ring.mu); ring.free_raw.push_back(p); }
-            ring.cv_stream.notify_all();
-        }
-    });
-    struct JoinAlloc { std::thread &t; ~JoinAlloc() { if (t.joinable()) t.join(); } } join_alloc{raw_alloc};
-    phase_add("build.alloc_text_pin_ring", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    std::vector<Sample> smp(n);
-    std::vector<int> rcodes(n, SKX_OK);
-    std::vector<std::string> errs(n);
-    auto mark_ready_locked = [&](int i) { Sample &x = smp[i]; if (x.read_done && x.pending == 0 && !x.queued) { x.queued = true; ring.ready.push_back(i); } };
-    std::vector<std::thread> uploaders;
-    const int n_up = 2;
-    for (int u = 0; u < n_up; u++) uploaders.emplace_back([&]() {
-        (void)hipSetDevice(ctx->device);
-        hipStream_t up = nullptr;
-        if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) up = nullptr;
-        std::vector<Ring::Req> batch;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(ring.mu);
-                ring.cv_work.wait(lk, [&] { return !ring.work.empty() || ring.readers_left == 0; });
-                if (ring.work.empty() && ring.readers_left == 0) break;
-                const size_t take = std::max<size_t>(1, ring.work.size() / 2);
-                batch.assign(ring.work.begin(), ring.work.begin() + (ptrdiff_t)take); ring.work.erase(ring.work.begin(), ring.work.begin() + (ptrdiff_t)take);
-            }
-            bool bad = false;
-            for (auto &r : batch) bad |= hipMemcpyAsync(r.dst, ring.base + (size_t)r.slot * SLOT, r.bytes, hipMemcpyHostToDevice, up) != hipSuccess;
-            bad |= hipStreamSynchronize(up) != hipSuccess;
-            {
-                std::lock_guard<std::mutex> lk(ring.mu);
-                if (bad) { ring.failed = true; ring.abort = true; }
-                for (auto &r : batch) { ring.free_slots.push_back(r.slot); smp[r.sample].pending--; ring.up_pending--; mark_ready_locked(r.sample); }
-            }
-            ring.cv_free.notify_all(); ring.cv_ready.notify_all();
-            if (bad) { ring.cv_stream.notify_all(); }
-        }
-        if (up) (void)hipStreamDestroy(up);
-    });
-    std::atomic<long long> us_wait_stream{0}, us_wait_ring{0}, us_files{0}, n_raw{0}, n_gzdev{0}, bytes_up{0};      // summed over the reader threads
-    auto us_since = [](std::chrono::steady_clock::time_point t) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); };
-    std::vector<std::thread> pool;
-    std::atomic<int> next{0};
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&, t]() {
-            const bool feeder = t < gz_feed;                              // (this thread hands gzip samples to the device's inflater)
-            struct Leave { Ring &r; ~Leave() { { std::lock_guard<std::mutex> lk(r.mu); r.readers_left--; } r.cv_work.notify_all(); r.cv_ready.notify_all(); } } leave{ring};
-            PlanePacker pk;
-            pk.min_qual = min_qual_host; pk.gz = any_gz;
-            for (int i;;) {
-                // the batch's last samples are left to the feeders: a thread that starts inflating one now (~1.1 s) would finish after the device has
-                // been through all of them (~50 ms each)
-                if (!feeder && gz_feed > 0 && n_gz_samples == n && n - next.load() < gz_tail) { std::lock_guard<std::mutex> lk(ring.mu); if (!ring.prefer_packed) break; }
-                if ((i = next.fetch_add(1)) >= n) break;
-                int sslot = -1; bool raw = false, gzdev = false;
-                {
-                    const auto tw = std::chrono::steady_clock::now();
-                    std::unique_lock<std::mutex> lk(ring.mu);
-                    // the link keeps up (few filled pieces of the pinned ring wait for their copy) and a raw slot is to be had: this sample goes as it
-                    // is; otherwise it is packed here.  (reads_raw=2: raw whatever the ring says -- then a raw slot is waited for.)
-                    // Measured (profiles/r06e_reads_modes.log, 16 readers): files read before -- packed 124 isolates/s through the pipeline, raw 91 (the link:
-                    // 46 GB/s), and a reader's time is the read() either way (0.10 s of its 0.11 s per isolate: packing is what fits beside it); files
-                    // read for the first time -- 35 isolates/s in every form (sixteen read()s of fresh tmpfs pages share 26 GB/s).  So raw text is
-                    // what relieves a processor that packs slowly or inflates (gzip: every sample raw), and beside fast packers only a sample or two
-                    // at a time travel raw, on bandwidth the link has left.
-                    const int raw_cap = any_gz ? nt : std::max(1, nt / 8);
-                    auto want_raw = [&] { return R > 0 && !ring.prefer_packed && (raw_knob == 2 || (!ring.free_raw.empty() && ring.raw_active < raw_cap && ring.up_pending * 4 <= n_slots)); };
-                    // a sample of gzip files: its compressed bytes, the device inflates (unless a sample before it turned out irregular: then the
-                    // readers inflate and pack, as they do for plain files)
-                    auto want_gzdev = [&] { return G > 0 && feeder && gzs[i].gz_files == gzs[i].files && !ring.prefer_packed; };
-                    ring.cv_stream.wait(lk, [&] { return ring.abort || (want_gzdev() ? !ring.free_gz.empty() : want_raw() ? !ring.free_raw.empty() : !ring.free_stream.empty()); });
-                    us_wait_stream += us_since(tw);
-                    if (ring.abort) return;
-                    gzdev = want_gzdev();
-                    raw = !gzdev && want_raw();
-                    std::vector<int> &fl = gzdev ? ring.free_gz : raw ? ring.free_raw : ring.free_stream;
-                    sslot = fl.back(); fl.pop_back();
-                    smp[i].slot = sslot; smp[i].raw = raw; smp[i].gzdev = gzdev;
-                    if (raw) ring.raw_active++;
-                    if (gzdev) ring.gz_active++;
-                }
-                const auto t_files = std::chrono::steady_clock::now();
-                struct Out { int slot = -1; size_t used = 0; uint8_t *dst = nullptr; uint64_t off = 0; } x;
-                x.dst = gzdev ? gz_slots[(size_t)sslot].p : raw ? raw_slots[(size_t)sslot].p : packed_pool.p + (uint64_t)sslot * pslot_bytes;
-                auto flush = [&]() {
-                    if (x.slot < 0) return;
-                    { std::lock_guard<std::mutex> lk(ring.mu); ring.work.push_back({x.slot, x.dst + x.off, x.used, i}); smp[i].pending++; ring.up_pending++; }
-                    ring.cv_work.notify_one();
-                    bytes_up += (long long)x.used;
-                    x.off += x.used; x.slot = -1; x.used = 0;
-                };
-                auto give_back = [&]() {
-                    if (x.slot >= 0) { { std::lock_guard<std::mutex> lk(ring.mu); ring.free_slots.push_back(x.slot); } ring.cv_free.notify_one(); x.slot = -1; }
-                };
-                auto take_slot = [&]() -> int {
-                    if (x.slot >= 0) return SKX_OK;
-                    const auto tw = std::chrono::steady_clock::now();
-                    std::unique_lock<std::mutex> lk(ring.mu);
-                    ring.cv_free.wait(lk, [&] { return !ring.free_slots.empty() || ring.abort; });
-                    us_wait_ring += us_since(tw);
-                    if (ring.abort) return SKF_ABORTED;                   // somebody else stopped the pipeline: not this reader's failure
-                    x.slot = ring.free_slots.back(); ring.free_slots.pop_back(); x.used = 0;
-                    return SKX_OK;
-                };
-                int r = SKX_OK;
-                uint64_t sample_len = 0, junction = 0;
-                if (gzdev) {
-                    // the files as they are, each followed by zeros to the next multiple of 256 bytes (at least 64: the inflater's bit reader looks ahead)
-                    n_gzdev++;
-                    uint64_t total = 0;
-                    int fno = 0;
-                    for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-                        if (!f) continue;
-                        const uint64_t want = gzs[i].comp[fno];
-                        smp[i].coff[fno] = total;
-                        const int fd = ::open(f, O_RDONLY);
-                        if (fd < 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                        struct Close { int fd; ~Close() { ::close(fd); } } cl{fd};
-                        (void)posix_fadvise(fd, 0, 0, POSIX_FADV_NOREUSE);
-                        uint64_t got_file = 0;
-                        while (got_file < want) {
-                            if ((r = take_slot()) != SKX_OK) break;
-                            uint8_t *dstp = ring.base + (size_t)x.slot * SLOT + x.used;
-                            const ssize_t rd = ::read(fd, dstp, std::min<uint64_t>(RAW_CHUNK - x.used, want - got_file));
-                            if (rd < 0 && errno == EINTR) continue;
-                            if (rd < 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                            if (rd == 0) { r = SKF_OVER_BOUND; break; }              // (the file shrank since it was measured: the one-shot form takes the batch)
-                            x.used += (size_t)rd; got_file += (uint64_t)rd; total += (uint64_t)rd;
-                            if (x.used >= RAW_CHUNK) flush();
-                        }
-                        if (r != SKX_OK) break;
-                        uint64_t zeros = ((want + 64 + 255) & ~255ull) - want;
-                        while (zeros) {
-                            if ((r = take_slot()) != SKX_OK) break;
-                            const size_t c = (size_t)std::min<uint64_t>(zeros, RAW_CHUNK - x.used);
-                            memset(ring.base + (size_t)x.slot * SLOT + x.used, 0, c);
-                            x.used += c; zeros -= c; total += c;
-                            if (x.used >= RAW_CHUNK) flush();
-                        }
-                        if (r != SKX_OK) break;
-                        fno++;
-                    }
-                    sample_len = total;
-                } else if (raw) {
-                    // the files' bytes into the pinned ring, nothing else: plain files by read() straight into a slot, gzip files inflated by this
-                    // thread's inflater and copied there.  A '\n' is put behind a file that lacks its last one (the device frames lines by their ends)
-                    n_raw++;
-                    uint64_t total = 0; const uint64_t cap = text_bytes[i] + 2;
-                    int fno = 0;
-                    for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-                        if (!f) continue;
-                        if (fno++ == 1) junction = total;
-                        const int fd = ::open(f, O_RDONLY);
-                        if (fd < 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                        struct Close { int fd; ~Close() { ::close(fd); } } cl{fd};
-                        (void)posix_fadvise(fd, 0, 0, POSIX_FADV_NOREUSE);
-                        unsigned char mg[2] = {0, 0};
-                        const bool gz = pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b;
-                        std::unique_ptr<GzReader> zr;
-                        if (gz) { zr.reset(new GzReader); zr->open(fd); }
-                        uint8_t last = '\n'; bool first = true; uint64_t got_file = 0;
-                        for (;;) {
-                            if ((r = take_slot()) != SKX_OK) break;
-                            uint8_t *dstp = ring.base + (size_t)x.slot * SLOT + x.used;
-                            const size_t room = RAW_CHUNK - x.used;               // (> 0: a full piece has left; a byte beyond it stays free for the '\n' a file may lack)
-                            size_t got = 0;
-                            if (zr) {
-                                const uint8_t *np; size_t ng;
-                                // (the inflater hands out what it has, up to its window: copied piecewise into the slot)
-                                if (zr->next(&np, &ng, 0) != 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                                if (ng == 0) break;
-                                size_t done = 0;
-                                while (done < ng && r == SKX_OK) {
-                                    if ((r = take_slot()) != SKX_OK) break;
-                                    dstp = ring.base + (size_t)x.slot * SLOT + x.used;
-                                    const size_t c = std::min(ng - done, RAW_CHUNK - x.used);
-                                    if (total + c > cap) { r = SKF_OVER_BOUND; break; }
-                                    memcpy(dstp, np + done, c);
-                                    if (first) { first = false; if (np[0] != '@') { r = SKF_OVER_BOUND; break; } }      // (a gzip file that is not FASTQ: the one-shot form takes the batch)
-                                    x.used += c; done += c; total += c; got_file += c; last = np[done - 1];
-                                    if (x.used >= RAW_CHUNK) flush();
-                                }
-                                if (r != SKX_OK) break;
-                                continue;
-                            }
-                            const ssize_t rd = ::read(fd, dstp, std::min<uint64_t>(room, cap - total));
-                            if (rd < 0 && errno == EINTR) continue;
-                            if (rd < 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                            got = (size_t)rd;
-                            if (got == 0) {
-                                // (the file grew since it was measured: what the bound was made from no longer holds)
-                                if (total >= cap) { char c1; if (::read(fd, &c1, 1) > 0) { set_error("Invalid FASTA/Q record"); r = SKX_EIO; } }
-                                break;
-                            }
-                            if (first) { first = false; if (dstp[0] != '@') { set_error("Invalid FASTA/Q record"); r = SKX_EIO; break; } }
-                            x.used += got; total += got; got_file += got; last = dstp[got - 1];
-                            if (x.used >= RAW_CHUNK) flush();
-                        }
-                        if (r != SKX_OK) break;
-                        if (got_file == 0) { set_error("Invalid path/file: %s", f); r = SKX_EIO; break; }
-                        if (last != '\n') {
-                            if ((r = take_slot()) != SKX_OK) break;
-                            ring.base[(size_t)x.slot * SLOT + x.used] = '\n'; x.used++; total++;
-                            if (x.used >= RAW_CHUNK) flush();
-                        }
-                    }
-                    sample_len = total;
-                } else {
-                    pk.pos = 0; pk.cap = bound[i] - 32; for (auto &c : pk.cur) c = 0;
-                    pk.push = [&](const uint64_t *grp) -> int {
-                        const int tr = take_slot(); if (tr != SKX_OK) return tr;
-                        memcpy(ring.base + (size_t)x.slot * SLOT + x.used, grp, READ_GROUP_BYTES);
-                        x.used += READ_GROUP_BYTES;
-                        if (x.used == SLOT) flush();
-                        return SKX_OK;
-                    };
-                    const std::function<int(int, const uint8_t *, size_t)> emit = [&](int which, const uint8_t *p, size_t nb) -> int { return pk.emit(which, p, nb); };
-                    for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-                        if (!f) continue;
-                        r = stream_fastq_file(f, emit);
-                        if (r == SKF_NOT_TAKEN && !any_gz) { set_error("Invalid FASTA/Q record"); r = SKX_EIO; }      // (the first byte was '@' a moment ago)
-                        if (r == SKF_NOT_TAKEN) r = SKF_OVER_BOUND;                                      // (a gzip file that is not FASTQ: the one-shot form takes the batch)
-                        if (r != SKX_OK) break;
-                    }
-                    if (r == SKX_OK) r = pk.finish();
-                    sample_len = pk.pos;
-                }
-                if (r == SKX_OK) flush();
-                if (raw) { std::lock_guard<std::mutex> lk(ring.mu); ring.raw_active--; }
-                if (r != SKX_OK) {
-                    give_back();
-                    if (r != SKF_ABORTED) { rcodes[i] = r; errs[i] = skx_last_error(); }      // (only the failure that started it is reported)
-                    { std::lock_guard<std::mutex> lk(ring.mu); ring.abort = true; }
-                    ring.cv_stream.notify_all(); ring.cv_free.notify_all(); ring.cv_ready.notify_all();
-                    return;
-                }
-                us_files += us_since(t_files);
-                { std::lock_guard<std::mutex> lk(ring.mu); smp[i].len = sample_len; smp[i].junction = junction; smp[i].read_done = true; mark_ready_locked(i); }
-                ring.cv_ready.notify_all();
-            }
-        });
-    // this thread: a sample's kernels as soon as its text is on the device
-    std::vector<DevBuf<uint64_t>> wl(n), wh2(n);
-    std::vector<uint64_t> cnt(n, 0);
-    int done = 0, krc = SKX_OK, n_irregular = 0, n_gz_host = 0;
-    double t_kernels = 0.0, t_frame = 0.0, t_inflate = 0.0;
-    FastqScratch fsc;
-    GzDevWork gzw2[1][2];                                               // (a sample's two files)
-    // a gzip sample's two files are decoded on streams of their own, beside each other AND beside the kernels of the samples the reader threads
-    // inflated (this thread goes on with those while a decode is in flight, one at a time: the inflater's buffers are one set)
-    struct Aux {
-        hipStream_t s[2] = {nullptr, nullptr}; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; GzDevFileInfo *fi = nullptr;      // (events, verdicts: [file]; ev[2]: a sample's text is made)
-        ~Aux() { for (auto x : s) if (x) (void)hipStreamDestroy(x); for (auto e : ev) if (e) (void)hipEventDestroy(e); if (fi) (void)hipHostFree(fi); }
-    } aux;
-    if (G) {
-        // (the reader threads are running: a failure here stops the pipeline the way a failed kernel does)
-        const int ar = [&]() -> int {
-            for (int f = 0; f < 2; f++) SKX_HIP(hipStreamCreateWithFlags(&aux.s[f], hipStreamNonBlocking));
-            for (int e = 0; e < 4; e++) SKX_HIP(hipEventCreateWithFlags(&aux.ev[e], hipEventDisableTiming));
-            SKX_HIP(hipHostMalloc((void **)&aux.fi, 4 * sizeof(GzDevFileInfo), hipHostMallocDefault));
-            return SKX_OK;
-        }();
-        if (ar != SKX_OK) { krc = ar; { std::lock_guard<std::mutex> lk(ring.mu); ring.abort = true; } ring.cv_stream.notify_all(); ring.cv_free.notify_all(); }
-    }
-    // the inflater's buffers at the size of the batch's largest file, before the first decode (see gz_device_reserve)
-    if (G && krc == SKX_OK) {
-        for (int i = 0; i < n && krc == SKX_OK; i++)
-            if (gzs[i].gz_files == gzs[i].files)
-                for (int f = 0; f < gzs[i].files && krc == SKX_OK; f++) krc = gz_device_reserve(gzw2[0][f], gzs[i].comp[f], gzs[i].hint[f]);
-        if (krc != SKX_OK) { { std::lock_guard<std::mutex> lk(ring.mu); ring.abort = true; } ring.cv_stream.notify_all(); ring.cv_free.notify_all(); }
-    }
-    int inflight = -1; const int inflight_set = 0, cur_set = 0;
-    auto gz_start = [&](int i, int set) -> int {
-        const uint8_t *comp = gz_slots[(size_t)smp[i].slot].p;
-        for (int f = 0; f < gzs[i].files; f++) {
-            GzDevWork &wk = gzw2[set][f];
-            SKX_TRY(gz_device_decode(ctx, aux.s[f], comp + smp[i].coff[f], gzs[i].comp[f], gzs[i].hint[f], wk));
-            SKX_HIP(hipMemcpyAsync(&aux.fi[set * 2 + f], wk.finfo.p, sizeof(GzDevFileInfo), hipMemcpyDeviceToHost, aux.s[f]));
-            SKX_HIP(hipEventRecord(aux.ev[set * 2 + f], aux.s[f]));
-        }
-        return SKX_OK;
-    };
-    auto gz_decoded = [&](int i, int set) -> bool { for (int f = 0; f < gzs[i].files; f++) if (hipEventQuery(aux.ev[set * 2 + f]) != hipSuccess) return false; return true; };
-    auto stop_pipeline = [&]() { { std::lock_guard<std::mutex> lk(ring.mu); ring.abort = true; } ring.cv_stream.notify_all(); ring.cv_free.notify_all(); };
-    // a sample through the host reader on this thread: what the device's framing calls irregular, and gzip files the device's inflater does not
-    // vouch for -- the reader accepts what is merely unusual and words the error for what is wrong
-    auto host_planes = [&](int i, uint8_t *slot_p, uint64_t &positions) -> int {
-        std::vector<uint64_t> hp;
-        PlanePacker pk; pk.min_qual = min_qual_host; pk.gz = any_gz; pk.cap = bound[i] - 32;
-        pk.push = [&](const uint64_t *grp) -> int { hp.insert(hp.end(), grp, grp + 5); return SKX_OK; };
-        const std::function<int(int, const uint8_t *, size_t)> emit = [&](int which, const uint8_t *p, size_t nb) -> int { return pk.emit(which, p, nb); };
-        int hr = SKX_OK;
-        for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-            if (!f) continue;
-            hr = stream_fastq_file(f, emit);
-            if (hr == SKF_NOT_TAKEN && !any_gz) { set_error("Invalid FASTA/Q record"); hr = SKX_EIO; }
-            if (hr == SKF_NOT_TAKEN || hr == SKF_OVER_BOUND) hr = SKF_NOT_TAKEN;          // (the one-shot form takes the batch)
-            if (hr != SKX_OK) break;
-        }
-        if (hr == SKX_OK) hr = pk.finish();
-        if (hr == SKX_OK && !hp.empty() && hipMemcpyAsync(slot_p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) hr = SKX_ENODEV;
-        if (hr == SKX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) hr = SKX_ENODEV;      // (hp goes)
-        positions = pk.pos;
-        return hr;
-    };
-    while (done < n) {
-        int i = -1; bool finish = false;
-        {
-            std::unique_lock<std::mutex> lk(ring.mu);
-            ring.cv_ready.wait(lk, [&] { return !ring.ready.empty() || ring.abort || inflight >= 0; });      // (every sample is queued by whoever sees its last piece arrive)
-            if (ring.abort) break;
-            // the sample in the inflater is taken up again when its decode has ended, when nothing else waits, or when the next one needs the inflater
-            if (inflight >= 0 && (ring.ready.empty() || smp[ring.ready.front()].gzdev || gz_decoded(inflight, inflight_set))) finish = true;
-            else { i = ring.ready.front(); ring.ready.pop_front(); }
-        }
-        if (finish) { i = inflight; inflight = -1; }
-        else if (smp[i].gzdev) {
-            krc = gz_start(i, 0);
-            if (krc != SKX_OK) { stop_pipeline(); break; }
-            inflight = i;
-            continue;
-        }
-        // the next gzip sample's decode starts as soon as this one's text is made (the inflater's buffers are free then: the streams wait for that
-        // on the device), beside this one's framing and window kernels
-        auto start_next_gz = [&](bool after_text) -> int {
-            int j = -1;
-            { std::lock_guard<std::mutex> lk(ring.mu); if (!ring.ready.empty() && smp[ring.ready.front()].gzdev) { j = ring.ready.front(); ring.ready.pop_front(); } }
-            if (j < 0) return SKX_OK;
-            if (after_text) {
-                SKX_HIP(hipEventRecord(aux.ev[2], ctx->stream));
-                for (int f = 0; f < 2; f++) SKX_HIP(hipStreamWaitEvent(aux.s[f], aux.ev[2], 0));
-            }
-            SKX_TRY(gz_start(j, 0));
-            inflight = j;
-            return SKX_OK;
-        };
-        const auto tk = std::chrono::steady_clock::now();
-        skx_qual qs = q ? *q : skx_qual{5, 20, SKX_QUAL_STRICT};
-        uint8_t *slot_p = smp[i].raw || smp[i].gzdev ? raw_planes.p : packed_pool.p + (uint64_t)smp[i].slot * pslot_bytes;      // where the sample's planes are
-        uint64_t positions = smp[i].len;
-        if (smp[i].gzdev) {
-            // compressed bytes: both files decoded to symbols side by side, the verdicts and lengths read back, then the text of one behind the
-            // other's (a '\n' behind a file that lacks its last one, as the raw form's readers put it), member CRCs checked, and the device's framing
-            const int nf = gzs[i].files;
-            GzDevFileInfo fi[2] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-            bool vouched = true;
-            GzDevWork *gzw = gzw2[cur_set];
-            for (int f = 0; f < nf && krc == SKX_OK; f++) {
-                if (hipEventSynchronize(aux.ev[cur_set * 2 + f]) != hipSuccess) krc = SKX_ENODEV;
-                fi[f] = aux.fi[cur_set * 2 + f];
-            }
-            uint64_t junction = 0, len = 0;
-            if (krc == SKX_OK) {
-                for (int f = 0; f < nf; f++) vouched = vouched && fi[f].status == 0 && fi[f].total > 0;
-                if (vouched) {
-                    junction = nf > 1 ? fi[0].total + (fi[0].last != '\n') : 0;
-                    len = (nf > 1 ? junction + fi[1].total + (fi[1].last != '\n') : fi[0].total + (fi[0].last != '\n'));
-                    if (len > text_bytes[i] + 2 || len + 64 > gz_text.n || fi[0].first != '@' || (nf > 1 && fi[1].first != '@')) vouched = false;      // (the host reader decides what it is)
-                }
-            }
-            if (krc == SKX_OK && vouched) {
-                hipStream_t st = ctx->stream;
-                uint64_t at = 0;
-                for (int f = 0; f < nf && krc == SKX_OK; f++) {
-                    krc = gz_device_text(ctx, st, gzw[f], gz_text.p + at, fi[f].total, fi[f].n_members);
-                    at += fi[f].total;
-                    if (krc == SKX_OK && fi[f].last != '\n') { if (hipMemsetAsync(gz_text.p + at, '\n', 1, st) != hipSuccess) krc = SKX_ENODEV; at++; }
-                }
-                for (int f = 0; f < nf && krc == SKX_OK; f++)
-                    if (hipMemcpyAsync(&fi[f], gzw[f].finfo.p, sizeof(GzDevFileInfo), hipMemcpyDeviceToHost, st) != hipSuccess) krc = SKX_ENODEV;
-                if (krc == SKX_OK) krc = start_next_gz(true);
-                t_inflate += std::chrono::duration<double>(std::chrono::steady_clock::now() - tk).count();
-                int irregular = 0;
-                if (krc == SKX_OK) krc = fastq_frame_planes(ctx, gz_text.p, len, junction, min_qual_host, (uint64_t *)slot_p, fsc, &positions, &irregular);      // (returns with the stream idle)
-                for (int f = 0; f < nf; f++) vouched = vouched && fi[f].status == 0;                                                                       // (the members' CRCs)
-                if (krc == SKX_OK && vouched && irregular) {
-                    n_irregular++;
-                    { std::lock_guard<std::mutex> lk(ring.mu); ring.prefer_packed = true; }
-                    krc = host_planes(i, slot_p, positions);
-                }
-            }
-            if (krc == SKX_OK && !vouched) {
-                if (inflight < 0) krc = start_next_gz(false);
-                if (knob("gz_debug"))
-                    fprintf(stderr, "gz on device: sample %d (%s) not vouched for: status %u / %u, text %llu / %llu bytes, first bytes %u / %u\n", i, file1[i], fi[0].status, fi[1].status,
-                            (unsigned long long)fi[0].total, (unsigned long long)fi[1].total, fi[0].first, fi[1].first);
-                n_gz_host++; krc = host_planes(i, slot_p, positions);
-            }
-            t_frame += std::chrono::duration<double>(std::chrono::steady_clock::now() - tk).count();
-        } else if (smp[i].raw) {
-            // the device frames the records and makes the planes; a text it calls irregular goes through the host reader here and now (which
-            // accepts what is merely unusual -- blank lines between records -- and words the error for what is wrong), and the readers pack the
-            // samples that follow: files of one run tend to share their quirks
-            int irregular = 0;
-            krc = fastq_frame_planes(ctx, raw_slots[(size_t)smp[i].slot].p, smp[i].len, smp[i].junction, min_qual_host, (uint64_t *)slot_p, fsc, &positions, &irregular);
-            if (krc == SKX_OK && irregular) {
-                n_irregular++;
-                { std::lock_guard<std::mutex> lk(ring.mu); ring.prefer_packed = true; }
-                krc = host_planes(i, slot_p, positions);
-            }
-            t_frame += std::chrono::duration<double>(std::chrono::steady_clock::now() - tk).count();
-        }
-        // (the kernels read the packed planes themselves: the two record streams never exist in memory)
-        if (krc == SKX_OK) krc = reads_sample_words(ctx, nullptr, nullptr, positions, k, rc, qs, wl[i], wh2[i], &cnt[i], (const uint64_t *)slot_p);      // (returns with the stream idle: the slot is free)
-        t_kernels += std::chrono::duration<double>(std::chrono::steady_clock::now() - tk).count();
-        { std::lock_guard<std::mutex> lk(ring.mu); (smp[i].gzdev ? ring.free_gz : smp[i].raw ? ring.free_raw : ring.free_stream).push_back(smp[i].slot); if (smp[i].gzdev) ring.gz_active--; if (krc != SKX_OK) ring.abort = true; }
-        ring.cv_stream.notify_all();
-        if (krc != SKX_OK) { ring.cv_free.notify_all(); break; }
-        done++;
-    }
-    { std::lock_guard<std::mutex> lk(ring.mu); if (done < n) ring.abort = true; }
-    ring.cv_stream.notify_all(); ring.cv_free.notify_all();
-    for (auto &th : pool) th.join();
-    for (auto &u : uploaders) u.join();
-    phase_add("build.read_upload", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    phase_add("build.reads_kernels_overlapped", t_kernels);
-    phase_add("build.reads_device_framing_overlapped", t_frame);
-    phase_add("build.readers_files_thread_s", us_files.load() * 1e-6);               // parse + pack, waits for pinned slots included
-    phase_add("build.readers_wait_pinned_thread_s", us_wait_ring.load() * 1e-6);
-    phase_add("build.readers_wait_device_slot_thread_s", us_wait_stream.load() * 1e-6);
-    phase_add("build.reads_samples_sent_raw", (double)n_raw.load());
-    phase_add("build.reads_samples_sent_compressed", (double)n_gzdev.load());
-    phase_add("build.reads_samples_inflated_on_host_after_all", (double)n_gz_host);
-    phase_add("build.reads_device_inflate_overlapped", t_inflate);
-    phase_add("build.reads_samples_irregular", (double)n_irregular);
-    phase_add("build.reads_uploaded_GB", (double)bytes_up.load() * 1e-9);
-    if (ring.failed) { set_error("upload of the sequence files failed"); return SKX_ENODEV; }
-    // the kernels' verdict first (SKF_NOT_TAKEN included: the one-shot form takes the batch -- the readers it interrupted recorded nothing),
-    // then the reader whose own failure stopped the pipeline
-    if (krc != SKX_OK) return krc;
-    for (int i = 0; i < n; i++) if (rcodes[i] == SKF_OVER_BOUND) return SKF_NOT_TAKEN;
-    for (int i = 0; i < n; i++) if (rcodes[i] != SKX_OK) { set_error("%s", errs[i].c_str()); return rcodes[i]; }
-    if (done < n) { set_error("internal: read-set pipeline stopped early"); return SKX_EUNSUP; }
-    raw_alloc.join();
-    packed_pool.release(); raw_planes.release(); raw_slots.clear(); gz_slots.clear(); gz_text.release();
-    for (auto &st2 : gzw2) for (auto &g : st2) g = GzDevWork();
-    const auto t1 = std::chrono::steady_clock::now();
-    skx_dictset *d = nullptr;
-    int r = reads_words_to_dictset(ctx, wl, wh2, cnt, k, rc, &d);
-    if (r == SKF_NOT_TAKEN) return r;                                           // (regions beyond the LDS sort: the sort-based form, from the files)
-    if (r != SKX_OK) return r;
-    phase_add("build.dictionaries", std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
-    for (int sidx2 = 0; sidx2 < n; sidx2++)
-        if ((d->sorted ? d->sample_size[sidx2] : d->raw_total[sidx2]) == 0) { set_error("%s has no valid sequence", file1[sidx2]); delete d; return SKX_EEMPTY; }
-    *out = d;
-    return SKX_OK;
-}
-
 // Test hook (not part of the drop-in boundary): FASTQ text through the device framing (skx_fastq.hip), the planes expanded to the two record
 // streams the read-set kernels would see -- sequence A C T G N '\n', quality ' ' (passes) / '!' (fails) / '\n'.  seq / qual: room for len / 2 + 64.
 extern "C" int skx_debug_fastq_frame(skx_ctx *ctx, const uint8_t *text, uint64_t len, uint64_t junction, int min_qual, uint8_t *seq, uint8_t *qual,
@@ -1380,361 +769,6 @@ extern "C" int skx_debug_gz_inflate(skx_ctx *ctx, const uint8_t *gz, uint64_t le
     }
     if (ms) { ms[0] = m0; ms[1] = m1; }
     SKX_HIP(hipGetLastError());
-    return SKX_OK;
-    });
-}
-
-extern "C" int skx_dictset_build_files(skx_ctx *ctx, const char *const *file1, const char *const *file2, int n, int k, int rc,
-                                       const skx_qual *q, int threads, double proportion_reads, skx_dictset **out)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !file1 || n <= 0 || !out) { set_error("bad arguments"); return SKX_EINVAL; }
-    SKX_TRY(check_k(k));
-    if (!(proportion_reads > 0.0) && !knob("host_parse") && !knob("reads_sort")) {
-        const int pr = build_reads_pipelined(ctx, file1, file2, n, k, rc, q, threads, out);
-        if (pr != SKF_NOT_TAKEN) return pr;
-    }
-    // Reader threads.  A plain (uncompressed, single-file) FASTA sample is not parsed on the host at all: its bytes are read
-    // into pinned memory and uploaded as they are, and the device strips headers and line breaks (skx_parse.hip) -- the host
-    // side of an assembly is one read() and one asynchronous copy.  FASTQ, .gz and two-file samples are parsed by the host
-    // reader (fastx.cpp) and uploaded as record streams.  Either way the uploads of some samples run beside the reading of
-    // others, each thread on its own stream.
-    std::vector<int> rcodes(n, SKX_OK);
-    std::vector<std::string> errs(n);
-    std::vector<DevBuf<uint8_t>> d_seq(n), d_qual(n);
-    std::vector<uint64_t> raw_len(n, 0), slot_off(n, 0), slot_len(n, 0);
-    std::vector<char> is_raw(n, 0);
-    std::vector<skx_stream> ss(n);
-    size_t step = 1;
-    if (proportion_reads > 0.0) { step = (size_t)std::llround(1.0 / proportion_reads); if (step == 0) step = 1; }
-    const bool device_parse = step == 1 && !knob("host_parse");
-    const auto t_read0 = std::chrono::steady_clock::now();
-    bool any_pair = false;
-    for (int i = 0; file2 && i < n; i++) any_pair |= file2[i] != nullptr;
-    const int nt = std::max(1, std::min({threads, n, any_pair ? 64 : 32, std::max(8, 2 * cpu_budget())}));      // (paired read sets are parsed on the host: CPU work, more threads pay)      // 5 GB of FASTA text: 0.43 / 0.24 / 0.24 / 0.32 s with 8 / 16 / 32 / 64 readers (tools/read_knobs.py)
-    // Raw path plumbing: reader threads make no HIP calls at all (creating a stream or a pinned buffer per thread serialises in
-    // the runtime: 64 threads spent 0.28 s each waiting for theirs).  They read() file pieces into the slots of ONE pinned ring;
-    // a single uploader issues the copies on one stream and recycles the slots.  The ring is pinned by a helper thread while
-    // this one sizes and allocates the device buffers.
-    // The regions' word buffer -- the largest allocation of a build, ~10 bytes per base -- is asked for now, on a thread of its own, and put back
-    // into the allocator's cache, where dictset_build_device finds it: as a box's first GPU process the allocation waits ~1 s for memory the
-    // driver hands out for the first time (build.dictionaries 0.98 s of a 2.46 s `ska build`, profiles/r06f_bench_full.json), and that second
-    // can pass beside the reading of the files.  The size is the one dictset_build_device will compute if the longest sample is as long as
-    // the largest plain file says (headers and line ends make it ~2 % more: the cache hands out a block up to a quarter larger than asked).
-    std::thread warm_thread;
-    struct JoinWarm { std::thread &t; ~JoinWarm() { if (t.joinable()) t.join(); } } join_warm{warm_thread};
-    if (device_parse && !any_pair && n >= 8 && !knob("no_prewarm")) {
-        uint64_t maxlen = 0; bool plain = true;
-        for (int i = 0; i < n && plain; i++) { struct stat sb; if (stat(file1[i], &sb) != 0 || !S_ISREG(sb.st_mode)) plain = false; else maxlen = std::max<uint64_t>(maxlen, (uint64_t)sb.st_size); }
-        for (int i = 0; i < n && plain; i++) { const size_t L = strlen(file1[i]); if (L > 3 && (!strcmp(file1[i] + L - 3, ".gz") || !strcmp(file1[i] + L - 3, ".xz") || !strcmp(file1[i] + L - 4, ".bz2") || !strcmp(file1[i] + L - 4, ".zst"))) plain = false; }
-        if (plain && maxlen > (1u << 20)) {
-            const bool wide_w = k > 31;
-            const uint64_t per_region = wide_w ? 3200 : 4900;
-            const int need = std::max(0, ilog2_ceil((maxlen + per_region - 1) / per_region)), base_logB = wide_w ? 11 : 10;
-            const int logB_w = std::min({need > base_logB ? std::max(base_logB, need - 5) : need, 2 * (k - 1), MAX_LOGB});
-            const uint64_t mean = (maxlen >> logB_w) + 1, cap_w = ((mean + mean / 5 + 256) + 63) / 64 * 64;
-            const uint64_t bytes = (((uint64_t)n << logB_w) * cap_w * (wide_w ? 2 : 1) + 2048) * 8;
-            size_t free_b = 0, total_b = 0;
-            (void)hipSetDevice(ctx->device);
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes < free_b / 2) {
-                const int dev = ctx->device;
-                warm_thread = std::thread([bytes, dev]() { (void)hipSetDevice(dev); hipError_t e = hipSuccess; if (void *p = dev_alloc(bytes, &e)) dev_free(p); });
-            }
-        }
-    }
-    constexpr size_t SLOT = 8u << 20;
-    // (a thread streaming a FASTQ sample fills a sequence and a quality slot at a time: two per thread and a few in flight)
-    const int n_slots = any_pair ? 2 * nt + 8 : std::max(4, std::min(2 * nt, 32));
-    struct Ring {
-        uint8_t *base = nullptr; std::mutex mu; std::condition_variable cv_free, cv_work;
-        std::vector<int> free_slots; struct Req { int slot; uint8_t *dst; size_t bytes; }; std::deque<Req> work; int readers_left = 0; bool failed = false;
-        ~Ring() { if (base) (void)hipHostFree(base); }
-    } ring;
-    std::thread pin_thread;
-    std::atomic<int> pin_rc{-1};
-    if (device_parse) pin_thread = std::thread([&]() {
-        (void)hipSetDevice(ctx->device);
-        pin_rc = hipHostMalloc((void **)&ring.base, (size_t)n_slots * SLOT, hipHostMallocDefault) == hipSuccess ? 0 : 1;
-    });
-    struct JoinPin { std::thread &t; ~JoinPin() { if (t.joinable()) t.join(); } } join_pin{pin_thread};
-    // one device buffer for all raw texts and one for all record streams (a slot per single-file sample, sized from stat):
-    // two allocations whatever the number of samples
-    DevBuf<uint8_t> raw_all, out_all, hs_seq_all, hs_qual_all;
-    std::vector<uint64_t> hs_off(n, 0), hs_len(n, 0);
-    std::vector<uint8_t> hs_fq(n, 0);
-    if (device_parse) {
-        uint64_t tot = 0;
-        for (int i = 0; i < n; i++) {
-            struct stat sb; unsigned char c0 = 0;
-            if (file2 && file2[i]) continue;
-            // only plain FASTA text is parsed on the device: a FASTQ or gzip sample reserves nothing here (raw_upload would refuse it and
-            // its two slots would stay allocated, uncounted by the batch planner)
-            const int fd = ::open(file1[i], O_RDONLY);
-            const bool fasta = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 1 && ::read(fd, &c0, 1) == 1 && c0 == '>';
-            if (fd >= 0) ::close(fd);
-            if (!fasta) continue;
-            slot_off[i] = tot; slot_len[i] = ((uint64_t)sb.st_size + 64 + 255) & ~255ull;
-            tot += slot_len[i];
-        }
-        if (tot) { SKX_HIP(hipSetDevice(ctx->device)); SKX_TRY(raw_all.alloc(tot)); SKX_TRY(out_all.alloc(tot)); }
-        // the samples the host reader will parse (two files, FASTQ): one buffer for all their record streams and one for the quality
-        // streams, a slot each bounded from the file sizes -- plain FASTQ holds at most half its bytes in either stream, plain FASTA
-        // all of them; gzip (size unknown) keeps an allocation of its own.  No device allocation per sample from the reader threads
-        // (64 of them for 32 isolates queued behind one another: most of 5 s).
-        uint64_t htot = 0; bool any_q = false;
-        for (int i = 0; i < n; i++) {
-            if (slot_len[i]) continue;
-            uint64_t bytes = 0; bool fq = false, ok = true;
-            for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-                if (!f) continue;
-                struct stat sb; unsigned char c0 = 0;
-                const int fd = ::open(f, O_RDONLY);
-                if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || ::read(fd, &c0, 1) != 1 || (c0 != '@' && c0 != '>')) ok = false;
-                else { bytes += (uint64_t)sb.st_size; fq |= c0 == '@'; }
-                if (fd >= 0) ::close(fd);
-            }
-            if (!ok || !bytes) continue;
-            hs_off[i] = htot; hs_len[i] = ((fq ? bytes / 2 : bytes) + 64 + 255) & ~255ull; hs_fq[i] = fq ? 1 : 0;
-            htot += hs_len[i]; any_q |= fq;
-        }
-        if (htot) { SKX_HIP(hipSetDevice(ctx->device)); SKX_TRY(hs_seq_all.alloc(htot)); if (any_q) SKX_TRY(hs_qual_all.alloc(htot)); }
-        pin_thread.join();
-        phase_add("build.alloc_text_pin_ring", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_read0).count());
-        if (pin_rc != 0) { ring.base = nullptr; }                                 // no pinned memory: every sample takes the host reader
-        else for (int b = 0; b < n_slots; b++) ring.free_slots.push_back(b);
-    }
-    const bool ring_ok = device_parse && ring.base;                            // the pinned ring + uploader threads carry raw files and host-parsed streams alike
-    const bool raw_ok = ring_ok && raw_all.p;
-    ring.readers_left = nt;
-    // uploader: copies queued pieces on one stream, a batch at a time, and returns their slots
-    std::vector<std::thread> uploaders;
-    const int n_up = 2;                                                         // two streams keep both copy engines busy
-    if (ring_ok) for (int u = 0; u < n_up; u++) uploaders.emplace_back([&]() {
-        (void)hipSetDevice(ctx->device);
-        hipStream_t up = nullptr;
-        if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) up = nullptr;
-        std::vector<Ring::Req> batch;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(ring.mu);
-                ring.cv_work.wait(lk, [&] { return !ring.work.empty() || ring.readers_left == 0; });
-                if (ring.work.empty() && ring.readers_left == 0) break;
-                const size_t take = std::max<size_t>(1, ring.work.size() / 2);          // leave work for the other uploader
-                batch.assign(ring.work.begin(), ring.work.begin() + (ptrdiff_t)take); ring.work.erase(ring.work.begin(), ring.work.begin() + (ptrdiff_t)take);
-            }
-            bool bad = false;
-            for (auto &r : batch) bad |= hipMemcpyAsync(r.dst, ring.base + (size_t)r.slot * SLOT, r.bytes, hipMemcpyHostToDevice, up) != hipSuccess;
-            bad |= hipStreamSynchronize(up) != hipSuccess;
-            {
-                std::lock_guard<std::mutex> lk(ring.mu);
-                if (bad) ring.failed = true;
-                for (auto &r : batch) ring.free_slots.push_back(r.slot);
-            }
-            ring.cv_free.notify_all();
-        }
-        if (up) (void)hipStreamDestroy(up);
-    });
-    std::vector<std::thread> pool;
-    std::atomic<int> next{0};
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&]() {
-            struct Leave { Ring &r; ~Leave() { { std::lock_guard<std::mutex> lk(r.mu); r.readers_left--; } r.cv_work.notify_all(); } } leave{ring};
-            hipStream_t up_st = nullptr;                                             // host-reader path only, created on first use
-            struct Drop { hipStream_t &s; ~Drop() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } drop{up_st};
-            // raw upload of a plain FASTA file: SKX_OK (taken), SKF_NOT_TAKEN (use the host reader), or an error
-            auto raw_upload = [&](int i) -> int {
-                if (!slot_len[i]) return SKF_NOT_TAKEN;
-                const int fd = ::open(file1[i], O_RDONLY);
-                if (fd < 0) return SKF_NOT_TAKEN;                                    // the host reader reports it
-                struct Close { int fd; ~Close() { ::close(fd); } } cl{fd};
-                // the pages are read once: without this hint every first access promotes its page on the kernel's LRU lists, under one lock
-                // for all reader threads (1 000 fresh 5 MB files on tmpfs: 0.47 s instead of 0.23 s for the same read() calls)
-                (void)posix_fadvise(fd, 0, 0, POSIX_FADV_NOREUSE);
-                const uint64_t cap = slot_len[i] - 64;                               // the size stat reported
-                uint8_t *dst = raw_all.p + slot_off[i];
-                uint64_t off = 0;
-                while (off < cap) {
-                    int slot;
-                    {
-                        std::unique_lock<std::mutex> lk(ring.mu);
-                        ring.cv_free.wait(lk, [&] { return !ring.free_slots.empty() || ring.failed; });
-                        if (ring.failed) { set_error("upload of the sequence files failed"); return SKX_ENODEV; }
-                        slot = ring.free_slots.back(); ring.free_slots.pop_back();
-                    }
-                    uint8_t *buf = ring.base + (size_t)slot * SLOT;
-                    const size_t want = (size_t)std::min<uint64_t>(SLOT, cap - off);
-                    size_t got = 0;
-                    while (got < want) { const ssize_t r = read(fd, buf + got, want - got); if (r < 0 && errno == EINTR) continue; if (r <= 0) break; got += (size_t)r; }
-                    const bool not_fasta = off == 0 && got && buf[0] != '>';         // FASTQ ('@'), gzip (1f 8b), anything else: the host reader's
-                    if (got == 0 || not_fasta) {
-                        { std::lock_guard<std::mutex> lk(ring.mu); ring.free_slots.push_back(slot); }
-                        ring.cv_free.notify_one();
-                        if (not_fasta) return SKF_NOT_TAKEN;
-                        break;                                                         // the file shrank under us: what was read is the file
-                    }
-                    { std::lock_guard<std::mutex> lk(ring.mu); ring.work.push_back({slot, dst + off, got}); }
-                    ring.cv_work.notify_one();
-                    off += got;
-                }
-                if (off == 0) return SKF_NOT_TAKEN;
-                raw_len[i] = off; is_raw[i] = 1;
-                return SKX_OK;
-            };
-            // a plain FASTQ sample: its files' lines go straight from a small read buffer into pinned slots -- one filling with sequence
-            // lines, one with quality lines -- which the uploaders copy to the sample's places in the two stream buffers
-            auto stream_fastq = [&](int i) -> int {
-                struct Out { int slot = -1; size_t used = 0; uint8_t *dst = nullptr; uint64_t off = 0; } o[2];
-                o[0].dst = hs_seq_all.p + hs_off[i]; o[1].dst = hs_qual_all.p + hs_off[i];
-                const uint64_t cap = hs_len[i] - 32;
-                auto flush = [&](Out &x) {
-                    if (x.slot < 0) return;
-                    { std::lock_guard<std::mutex> lk(ring.mu); ring.work.push_back({x.slot, x.dst + x.off, x.used}); }
-                    ring.cv_work.notify_one();
-                    x.off += x.used; x.slot = -1; x.used = 0;
-                };
-                auto give_back = [&]() {
-                    for (auto &x : o) if (x.slot >= 0) { { std::lock_guard<std::mutex> lk(ring.mu); ring.free_slots.push_back(x.slot); } ring.cv_free.notify_one(); x.slot = -1; }
-                };
-                const std::function<int(int, const uint8_t *, size_t)> emit = [&](int which, const uint8_t *p, size_t nb) -> int {
-                    Out &x = o[which];
-                    if (x.off + x.used + nb + 1 > cap) { set_error("Invalid FASTA/Q record"); return SKX_EIO; }      // (more sequence than half the file: not FASTQ)
-                    if (x.slot >= 0 && x.used + nb + 1 <= SLOT) {                       // the common case: the line and its terminator fit the slot being filled
-                        uint8_t *d = ring.base + (size_t)x.slot * SLOT + x.used;
-                        memcpy(d, p, nb); d[nb] = '\n';
-                        x.used += nb + 1;
-                        if (x.used == SLOT) flush(x);
-                        return SKX_OK;
-                    }
-                    bool term = false;                                                  // the line, then its '\n', across slot ends
-                    static const uint8_t nl = '\n';
-                    for (;;) {
-                        if (nb == 0) { if (term) break; term = true; p = &nl; nb = 1; }
-                        if (x.slot < 0) {
-                            std::unique_lock<std::mutex> lk(ring.mu);
-                            ring.cv_free.wait(lk, [&] { return !ring.free_slots.empty() || ring.failed; });
-                            if (ring.failed) { set_error("upload of the sequence files failed"); return SKX_ENODEV; }
-                            x.slot = ring.free_slots.back(); ring.free_slots.pop_back(); x.used = 0;
-                        }
-                        const size_t take = std::min(nb, SLOT - x.used);
-                        memcpy(ring.base + (size_t)x.slot * SLOT + x.used, p, take);
-                        x.used += take; p += take; nb -= take;
-                        if (x.used == SLOT) flush(x);
-                    }
-                    return SKX_OK;
-                };
-                for (const char *f : {file1[i], file2 ? file2[i] : nullptr}) {
-                    if (!f) continue;
-                    int r = stream_fastq_file(f, emit);
-                    if (r == SKF_NOT_TAKEN && f != file1[i]) { set_error("Invalid FASTA/Q record"); r = SKX_EIO; }      // file 2 is parsed in file 1's mode (ska_dict.rs:356-366)
-                    if (r != SKX_OK) { give_back(); return r; }              // (SKF_NOT_TAKEN: the first file, before anything was emitted)
-                }
-                flush(o[0]); flush(o[1]);
-                if (o[0].off != o[1].off) { set_error("Invalid FASTA/Q record"); return SKX_EIO; }
-                ss[i].seq = o[0].dst; ss[i].qual = o[1].dst; ss[i].len = o[0].off;
-                return SKX_OK;
-            };
-            HostStream h;                                                            // (its buffers live across this thread's samples: no fresh pages per sample)
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                if (raw_ok) {
-                    const int r = raw_upload(i);
-                    if (r == SKX_OK) continue;
-                    if (r != SKF_NOT_TAKEN) { rcodes[i] = r; errs[i] = skx_last_error(); continue; }
-                }
-                if (ring_ok && hs_len[i] && hs_fq[i] && hs_qual_all.p) {
-                    const int r = stream_fastq(i);
-                    if (r == SKX_OK) continue;
-                    if (r != SKF_NOT_TAKEN) { rcodes[i] = r; errs[i] = skx_last_error(); continue; }
-                }
-                rcodes[i] = read_sample_stream(file1[i], file2 ? file2[i] : nullptr, proportion_reads, h);
-                if (rcodes[i] != SKX_OK) { errs[i] = skx_last_error(); continue; }
-                const size_t len = h.seq.size();
-                // the parsed streams travel through the pinned ring like the raw files (a copy from pageable memory goes through the
-                // runtime's one staging path: 32 reader threads shared ~3 GB/s, 5.6 s for 32 isolates); the uploads are complete when the
-                // uploader threads have been joined, which is before anything reads them
-                auto up = [&](DevBuf<uint8_t> &own, uint8_t *slot_ptr, const std::vector<uint8_t> &src, uint8_t **where) -> int {
-                    struct { uint8_t *p; } dst{slot_ptr};
-                    if (!dst.p) { (void)hipSetDevice(ctx->device); SKX_TRY(own.alloc(len + 16)); dst.p = own.p; }      // no slot (gzip, a stream longer than its bound)
-                    *where = dst.p;
-                    if (!ring_ok) {
-                        (void)hipSetDevice(ctx->device);
-                        if (!up_st && hipStreamCreateWithFlags(&up_st, hipStreamNonBlocking) != hipSuccess) up_st = nullptr;
-                        if (len) { SKX_HIP(hipMemcpyAsync(dst.p, src.data(), len, hipMemcpyHostToDevice, up_st)); SKX_HIP(hipStreamSynchronize(up_st)); }
-                        return SKX_OK;
-                    }
-                    for (size_t off = 0; off < len; off += SLOT) {
-                        int slot;
-                        {
-                            std::unique_lock<std::mutex> lk(ring.mu);
-                            ring.cv_free.wait(lk, [&] { return !ring.free_slots.empty() || ring.failed; });
-                            if (ring.failed) { set_error("upload of the sequence files failed"); return SKX_ENODEV; }
-                            slot = ring.free_slots.back(); ring.free_slots.pop_back();
-                        }
-                        const size_t nb = std::min<size_t>(SLOT, len - off);
-                        memcpy(ring.base + (size_t)slot * SLOT, src.data() + off, nb);
-                        { std::lock_guard<std::mutex> lk(ring.mu); ring.work.push_back({slot, dst.p + off, nb}); }
-                        ring.cv_work.notify_one();
-                    }
-                    return SKX_OK;
-                };
-                const bool fits = hs_len[i] && len + 16 <= hs_len[i] && (!h.is_fastq || hs_qual_all.p);
-                uint8_t *at_seq = nullptr, *at_qual = nullptr;
-                rcodes[i] = up(d_seq[i], fits ? hs_seq_all.p + hs_off[i] : nullptr, h.seq, &at_seq);
-                if (rcodes[i] == SKX_OK && h.is_fastq) rcodes[i] = up(d_qual[i], fits ? hs_qual_all.p + hs_off[i] : nullptr, h.qual, &at_qual);
-                if (rcodes[i] != SKX_OK) { errs[i] = skx_last_error(); continue; }
-                ss[i].seq = at_seq; ss[i].qual = h.is_fastq ? at_qual : nullptr; ss[i].len = len;
-            }
-        });
-    for (auto &th : pool) th.join();
-    for (auto &u : uploaders) u.join();
-    phase_add("build.read_upload", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_read0).count());
-    if (ring.failed) { set_error("upload of the sequence files failed"); return SKX_ENODEV; }
-    for (int i = 0; i < n; i++) if (rcodes[i] != SKX_OK) { set_error("%s", errs[i].c_str()); return rcodes[i]; }
-    // the raw FASTA texts -> record streams, all files in one set of launches
-    {
-        PhaseTimer t_parse("build.device_fasta_parse");
-        SKX_HIP(hipSetDevice(ctx->device));
-        hipStream_t st = ctx->stream;
-        std::vector<int> idx;
-        for (int i = 0; i < n; i++) if (is_raw[i]) idx.push_back(i);
-        const int m = (int)idx.size();
-        if (m) {
-            std::vector<const uint8_t *> h_raw(m); std::vector<uint8_t *> h_out(m); std::vector<uint64_t> h_len(m), h_base(m + 1, 0);
-            for (int j = 0; j < m; j++) {
-                const int i = idx[j];
-                h_raw[j] = raw_all.p + slot_off[i]; h_out[j] = out_all.p + slot_off[i]; h_len[j] = raw_len[i];
-                h_base[j + 1] = h_base[j] + fasta_parse_tiles(raw_len[i]);
-            }
-            const uint64_t tiles = h_base[m];
-            std::vector<uint32_t> h_tf(tiles);
-            for (int j = 0; j < m; j++) std::fill(h_tf.begin() + (ptrdiff_t)h_base[j], h_tf.begin() + (ptrdiff_t)h_base[j + 1], (uint32_t)j);
-            DevBuf<const uint8_t *> g_raw; DevBuf<uint8_t *> g_out; DevBuf<uint64_t> g_len, g_outlen, g_base, g_off, g_sum; DevBuf<uint32_t> g_tf; DevBuf<uint8_t> g_kind;
-            SKX_TRY(g_raw.alloc(m)); SKX_TRY(g_out.alloc(m)); SKX_TRY(g_len.alloc(m)); SKX_TRY(g_outlen.alloc(m)); SKX_TRY(g_base.alloc(m + 1));
-            SKX_TRY(g_off.alloc(tiles)); SKX_TRY(g_sum.alloc(tiles)); SKX_TRY(g_tf.alloc(tiles)); SKX_TRY(g_kind.alloc(tiles));
-            SKX_HIP(hipMemcpyAsync(g_raw.p, h_raw.data(), m * sizeof(void *), hipMemcpyHostToDevice, st));
-            SKX_HIP(hipMemcpyAsync(g_out.p, h_out.data(), m * sizeof(void *), hipMemcpyHostToDevice, st));
-            SKX_HIP(hipMemcpyAsync(g_len.p, h_len.data(), m * 8, hipMemcpyHostToDevice, st));
-            SKX_HIP(hipMemcpyAsync(g_base.p, h_base.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-            if (tiles) SKX_HIP(hipMemcpyAsync(g_tf.p, h_tf.data(), tiles * 4, hipMemcpyHostToDevice, st));
-            launch_fasta_parse(g_raw.p, g_len.p, g_out.p, g_outlen.p, g_tf.p, g_base.p, tiles, g_sum.p, g_off.p, g_kind.p, m, st);
-            std::vector<uint64_t> h_outlen(m);
-            SKX_HIP(hipMemcpyAsync(h_outlen.data(), g_outlen.p, m * 8, hipMemcpyDeviceToHost, st));
-            SKX_HIP(hipStreamSynchronize(st));
-            SKX_HIP(hipGetLastError());
-            for (int j = 0; j < m; j++) { const int i = idx[j]; ss[i].seq = out_all.p + slot_off[i]; ss[i].qual = nullptr; ss[i].len = h_outlen[j]; }
-        }
-        raw_all.release();
-    }
-    skx_dictset *d = nullptr;
-    if (warm_thread.joinable()) { PhaseTimer t_w("build.wait_for_word_buffer"); warm_thread.join(); }
-    const auto t_dev0 = std::chrono::steady_clock::now();
-    int r = skx_dictset_build(ctx, ss.data(), n, 1, k, rc, q, &d);
-    phase_add("build.dictionaries", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_dev0).count());
-    if (r == SKX_EEMPTY) {      // "{file} has no valid sequence" (ska_dict.rs:374-376)
-        int bad = 0; sscanf(skx_last_error(), "sample %d", &bad);
-        set_error("%s has no valid sequence", file1[bad]);
-    }
-    if (r != SKX_OK) return r;
-    *out = d;
     return SKX_OK;
     });
 }
@@ -2484,16 +1518,12 @@ struct SampleNeed { uint64_t resident = 0, transient = 0; };
 static SampleNeed sample_device_bytes(const char *f1, const char *f2, bool wide, unsigned min_count)
 {
     uint64_t bytes = 0; bool reads = false;
-    for (const char *f : {f1, f2}) {
-        if (!f) continue;
-        struct stat sb;
-        if (stat(f, &sb) != 0) continue;                       // the reader reports a missing file
-        unsigned char c0 = 0;
-        const int fd = ::open(f, O_RDONLY);
-        if (fd >= 0) { if (::read(fd, &c0, 1) != 1) c0 = 0; ::close(fd); }
-        const bool gz = c0 == 0x1f;
-        reads |= gz || c0 == '@';
-        bytes += (uint64_t)sb.st_size * (gz ? 5u : 1u);        // upper estimate of the text
+    for (const char *f : sample_files(f1, f2)) {
+        const FileProbe p = probe_file(f);
+        if (!p.found) continue;                                // the reader reports a missing file
+        const bool gz = p.n_head >= 1 && p.head[0] == 0x1f;
+        reads |= gz || (p.n_head >= 1 && p.head[0] == '@');
+        bytes += p.size * (gz ? 5u : 1u);                      // upper estimate of the text
     }
     SampleNeed n;
     if (reads) {

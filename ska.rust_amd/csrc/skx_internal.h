@@ -314,8 +314,24 @@ int skf_read_stream(const char *path, SkfMeta &m, std::vector<skx_key> &keys, st
                     const DevDecode *dev = nullptr);
 }  // namespace skx
 
-// helpers shared by the ABI translation units (skx_api.cpp, skx_api_io.cpp)
+// helpers shared by the ABI translation units (skx_api.cpp, skx_build_files.cpp, skx_api_io.cpp)
 namespace skx {
+// the one or two paths of a sample, and what a look at a file tells (skx_build_files.cpp): each caller decides for itself what it makes of it
+struct SampleFiles { const char *f[2]; int n; const char *const *begin() const { return f; } const char *const *end() const { return f + n; } };
+inline SampleFiles sample_files(const char *f1, const char *f2) { SampleFiles s{{nullptr, nullptr}, 0}; for (const char *f : {f1, f2}) if (f) s.f[s.n++] = f; return s; }
+inline SampleFiles sample_files(const char *const *file1, const char *const *file2, int i) { return sample_files(file1[i], file2 ? file2[i] : nullptr); }
+struct FileProbe {
+    bool opened = false, found = false, regular = false, has_tail = false;      // found: stat answered (a file that cannot be opened may still be found)
+    uint64_t size = 0; int n_head = 0; unsigned char head[2] = {0, 0}, tail[4] = {0, 0, 0, 0};      // the first bytes of a regular file; a gzip file's last four (ISIZE)
+    bool gzip() const { return n_head == 2 && head[0] == 0x1f && head[1] == 0x8b; }
+};
+FileProbe probe_file(const char *path, bool gz_trailer = false);
+// how an assembly batch's (sample, bucket) regions are laid out (skx_api.cpp): 2^logB regions a sample (-1: not bucketed, the sort-based form takes
+// the batch) of `cap` words each
+struct RegionLayout { int logB; uint32_t cap; };
+uint32_t region_capacity(uint64_t longest_sample, int logB);
+RegionLayout region_layout(uint64_t longest_sample, int k);
+int reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std::vector<DevBuf<uint64_t>> &wh2, const std::vector<uint64_t> &cnt, int k, int rc, skx_dictset **out);
 // pieces of the single-GPU path the collective layer (skx_comm.hip) composes
 int dictset_sort(skx_dictset *d);                                    // raw regions -> sorted, folded regions + sub-index (no-op when they are)
 int keyset_flatten(skx_keyset *ks);                                  // ks->flat = the rows as one compact list of packed words (engine order)

@@ -315,7 +315,7 @@ def test_builds_are_deterministic(tmp_path, monkeypatch):
 
 def test_read_set_pipeline_equals_one_shot(tmp_path):
     """`ska build` on read sets runs reader threads, uploads and the per-isolate kernels as a pipeline over a small pool of device slots
-    (skx_api.cpp build_reads_pipelined); SKX_KNOBS=no_reads_pipeline is the one-shot form it replaced.  Same .skf bytes either way and with a
+    (skx_build_files.cpp ReadsPipeline); SKX_KNOBS=no_reads_pipeline is the one-shot form it replaced.  Same .skf bytes either way and with a
     pool of ONE slot (every sample reuses it), for paired and single-file samples, k = 31 and 41; a broken record fails both forms with the
     reference's message (ska_dict.rs:131-153 via needletail)."""
     import synth
