@@ -196,6 +196,16 @@ int  skx_array_distance(skx_array *a, double constant, int filt_ambig, skx_dist 
  * NoConst stage removes, added to every pair's matches), instead of being filtered out of the matrix first.  Same numbers as
  * skx_array_filter x 2 + skx_array_distance. */
 int  skx_array_distance_filtered(skx_array *a, double min_freq, int filt_ambig, skx_dist *out, int64_t *constant, uint64_t *rows_used);
+/* The rows of that table that hold a query sample (`ska distance --query`): query = n_query distinct sample indices in any order,
+ * out = n_query x n_samples row-major, out[q * n_samples + j] = the pair (query[q], j) with the numbers skx_array_distance /
+ * skx_array_distance_filtered give it (same planes, same counts, same arithmetic); the entry j == query[q] is zeroed.  The filters stay
+ * those of the whole array: thresholds, *constant and the kept rows are the full table's.  The bit planes are built with the queries in
+ * front and the pair sweep runs over the band of the queries, so the count buffers are n_query x n_samples pairs, not n_samples^2.
+ * SKX_EINVAL with a message for an index out of range, a repeated index or n_query < 1.  The array is left as it is; both key widths
+ * and arrays held as pieces are taken. */
+int  skx_array_distance_query(skx_array *a, double constant, int filt_ambig, const int *query, int n_query, skx_dist *out);
+int  skx_array_distance_query_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query,
+                                       skx_dist *out, int64_t *constant, uint64_t *rows_used);
 /* The two halves of skx_array_distance, so that a multi-GPU host can exchange the bit planes between them (SURVEY.md 8e:
  * "tile the pair matrix over ranks"): every rank builds the planes of its own samples over the (globally filtered) rows, the
  * planes are all-gathered (plane-major: planes[p][sample][word], 4 planes with filt_ambig, 8 without), and each rank

@@ -31,6 +31,14 @@ int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, in
 typedef struct { const char *tree, *clusters; double cluster_snps, cluster_mismatches; } skh_dist_extras;
 /* skh_distance_skf_tsv, and the extras from the same table */
 int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *extras, char **buf, uint64_t *len);
+/* `ska distance <skf> --query / --query-file / --query-skf`: the header and exactly those lines of skh_distance_skf_tsv's table in which Sample1
+ * or Sample2 is a query sample, in the table's order and text.  names[n_names]: query samples by name (repeats collapse; one that is not in
+ * the array: SKX_EINVAL "Could not find sample(s): {..}").  query_skf (NULL: none): a second file merged into the first in memory exactly as
+ * skh_merge would (its refusals and messages), every sample of it a query; the table is then the merged array's.  The filters stay those of
+ * the whole array.  One file: the one-pass filtered load, then skx_array_distance_query; two: skx_array_merge, then
+ * skx_array_distance_query_filtered.  An empty query set is SKX_EINVAL. */
+int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const char *query_skf, const char *const *names, int n_names, double min_freq,
+                           int filt_ambig, char **buf, uint64_t *len);
 /* the joins of skx_dist_nj / skx_matrix_nj over n leaves as one line of Newick (host only).  A negative raw length is written as 0 and the
  * difference moved to the sibling branch of the same join, so the distance between the two joined nodes is kept (Kuhner-Felsenstein).
  * Midpoint root: the two leaves with the largest path distance in the corrected tree (ties to the lowest (id, id)), the root half way

@@ -2238,27 +2238,67 @@ extern "C" int skx_array_write_fasta(skx_array *a, int fd)
 static const int PAIR_CLASS_NUM[10] = {36, 18, 12, 9, 18, 6, 12, 4, 8, 12};
 
 // pair-class counts -> VariantDist (merge_ska_array.rs:596-631), pairs (i in [i_lo, i_hi), j > i) row-major; h rows are relative to i_lo
+static void finish_pair(const unsigned long long *c, double constant, int filt_ambig, skx_dist &o)
+{
+    double mismatches = (double)c[0], matches = constant, distance;
+    if (filt_ambig) { matches += (double)c[2]; distance = (double)(c[2] - c[3]); }
+    else {
+        unsigned long long m = 0, num = 0;
+        for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)PAIR_CLASS_NUM[q]; }
+        matches += (double)m;
+        distance = (double)(36ull * c[1] - num) / 36.0;
+    }
+    o.distance = distance;
+    o.mismatch_prop = (matches + mismatches) == 0.0 ? 0.0 : mismatches / (matches + mismatches);
+    o.match_count = (uint64_t)matches; o.mismatch_count = (uint64_t)mismatches;
+}
 static void finish_pairs(const unsigned long long *h, int S, int i_lo, int i_hi, double constant, int filt_ambig, skx_dist *out)
 {
     uint64_t n = 0;
     for (int i = i_lo; i < i_hi; i++)
-        for (int j = i + 1; j < S; j++, n++) {
-            const unsigned long long *c = &h[((uint64_t)(i - i_lo) * S + j) * DIST_NCOUNT];
-            double mismatches = (double)c[0], matches = constant, distance;
-            if (filt_ambig) { matches += (double)c[2]; distance = (double)(c[2] - c[3]); }
-            else {
-                unsigned long long m = 0, num = 0;
-                for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)PAIR_CLASS_NUM[q]; }
-                matches += (double)m;
-                distance = (double)(36ull * c[1] - num) / 36.0;
-            }
-            out[n].distance = distance;
-            out[n].mismatch_prop = (matches + mismatches) == 0.0 ? 0.0 : mismatches / (matches + mismatches);
-            out[n].match_count = (uint64_t)matches; out[n].mismatch_count = (uint64_t)mismatches;
+        for (int j = i + 1; j < S; j++, n++) finish_pair(&h[((uint64_t)(i - i_lo) * S + j) * DIST_NCOUNT], constant, filt_ambig, out[n]);
+}
+// ---- the query form (skx_array_distance_query*): the planes are built in query-first order -- slot s holds sample order[s], the queries
+// ascending in slots [0, Q), every other sample ascending behind them -- and the band [0, Q) of the pair sweep then holds every pair with a
+// query in it exactly once, in a count buffer of Q x S pairs.  The counts of a pair do not depend on which of the two comes first.
+struct skx::QueryPlan {
+    std::vector<int> query, slot;         // query[q] = sample of the caller's q-th row; slot[sample] = where the planes hold it
+    DevBuf<int> order;                    // [S] on the device
+    int Q() const { return (int)query.size(); }
+};
+static int query_plan(skx_array *a, const int *query, int n_query, QueryPlan &qp)
+{
+    const int S = (int)a->names.size();
+    if (!query || n_query < 1) { set_error("distance query: at least one query sample is needed"); return SKX_EINVAL; }
+    std::vector<char> is_q((size_t)S, 0);
+    for (int q = 0; q < n_query; q++) {
+        if (query[q] < 0 || query[q] >= S) { set_error("distance query: sample index %d is outside the array's %d samples", query[q], S); return SKX_EINVAL; }
+        if (is_q[query[q]]) { set_error("distance query: sample index %d is given twice", query[q]); return SKX_EINVAL; }
+        is_q[query[q]] = 1;
+    }
+    qp.query.assign(query, query + n_query);
+    std::vector<int> order; order.reserve((size_t)S);
+    for (int pass = 1; pass >= 0; pass--) for (int s = 0; s < S; s++) if (is_q[s] == pass) order.push_back(s);
+    qp.slot.resize((size_t)S);
+    for (int s = 0; s < S; s++) qp.slot[order[s]] = s;
+    SKX_TRY(qp.order.alloc((uint64_t)S));
+    SKX_HIP(hipMemcpyAsync(qp.order.p, order.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, a->ctx->stream));
+    SKX_HIP(hipStreamSynchronize(a->ctx->stream));            // (order is a local)
+    return SKX_OK;
+}
+// h = the counts of the band [0, Q) over slots; out[q * S + j] = the pair (query[q], j), zeroed where j is the query itself
+static void finish_query(const unsigned long long *h, int S, const QueryPlan &qp, double constant, int filt_ambig, skx_dist *out)
+{
+    for (int q = 0; q < qp.Q(); q++)
+        for (int j = 0; j < S; j++) {
+            skx_dist &o = out[(uint64_t)q * S + j];
+            const int x = qp.slot[qp.query[q]], y = qp.slot[j];
+            if (x == y) { o = skx_dist{}; continue; }
+            finish_pair(&h[((uint64_t)std::min(x, y) * S + std::max(x, y)) * DIST_NCOUNT], constant, filt_ambig, o);      // (min < Q: x is a query's slot)
         }
 }
 // bit planes of the rows flagged 1 in keep: scan, keep words, planes (every word written).  rows = how many
-int skx::planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows)
+int skx::planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows, const int *order)
 {
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
@@ -2273,14 +2313,15 @@ int skx::planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf
     if (!rows) { SKX_TRY(planes.zero(st)); return SKX_OK; }
     launch_keep_bits(keep, pos.p, U, kb.p, gp.p, st);
     SKX_TRY(fg.alloc(rows / 4096 + 2));
-    launch_build_planes_keep(a->matrix.p, a->pitch, S, U, kb.p, gp.p, planes.p, wpr, filt, st, fg.p, rows);
+    launch_build_planes_keep(a->matrix.p, a->pitch, S, U, kb.p, gp.p, planes.p, wpr, filt, st, fg.p, rows, order);
     SKX_HIP(hipStreamSynchronize(st));            // pos / kb / gp / fg go out of scope
     return SKX_OK;
 }
 // --allow-ambiguous over the rows flagged in keep (nullptr: all): the twelve pair classes differ from the three of the default sweep only on rows
 // that hold an ambiguous cell (the row statistics say which), so the rows without one go through the 4-plane sweep, their counts filed as classes
 // 0-2, and only the others through the 8-plane, twelve-class one (merge_ska_array.rs:587-632 sums per row: any split of the rows gives the sums)
-static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double constant, skx_dist *out)
+// qp: the query form -- planes in query-first order, the band of the queries, out as skx_array_distance_query lays it out
+static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double constant, skx_dist *out, const QueryPlan *qp = nullptr)
 {
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
@@ -2288,7 +2329,8 @@ static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double co
     SKX_TRY(clean.alloc(U)); SKX_TRY(dirty.alloc(U));
     launch_split_keep(keep, a->mask.p, U, clean.p, dirty.p, st, knob("stale_row_mask") ? 2 : 0);
     DevBuf<uint64_t> pc, pd; uint64_t wc = 1, wd = 1, nc = 0, nd = 0;
-    SKX_TRY(planes_of_kept_rows(a, clean.p, 1, pc, wc, nc));
+    const int *order = qp ? qp->order.p : nullptr;
+    SKX_TRY(planes_of_kept_rows(a, clean.p, 1, pc, wc, nc, order));
     if (nc) {
         // the split rests on the row statistics: on a clean row every present cell is one base, i.e. plane 0 (present) == plane 1 (unambiguous).
         // Statistics that missed a code (none of the engine's operations leaves such, but the array is the caller's) show up here: all rows
@@ -2300,11 +2342,11 @@ static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double co
         SKX_HIP(hipStreamSynchronize(st));
         if (differ) { launch_split_keep(keep, a->mask.p, U, clean.p, dirty.p, st, 1); nc = 0; pc.release(); }
     }
-    SKX_TRY(planes_of_kept_rows(a, dirty.p, 0, pd, wd, nd));
-    return planes_distance_split(ctx, pc.p, wc, nc, pd.p, wd, nd, S, constant, 0, S, out);
+    SKX_TRY(planes_of_kept_rows(a, dirty.p, 0, pd, wd, nd, order));
+    return planes_distance_split(ctx, pc.p, wc, nc, pd.p, wd, nd, S, constant, 0, qp ? qp->Q() : S, out, qp);
 }
 int skx::planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint64_t wpr_clean, uint64_t rows_clean, const uint64_t *planes_dirty, uint64_t wpr_dirty,
-                               uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out)
+                               uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp)
 {
     hipStream_t st = ctx->stream;
     if (S < 2 || i_lo >= i_hi) return SKX_OK;
@@ -2317,10 +2359,12 @@ int skx::planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint6
     SKX_HIP(hipMemcpyAsync(h.data(), cnt.p, h.size() * 8, hipMemcpyDeviceToHost, st));
     SKX_HIP(hipStreamSynchronize(st));
     SKX_HIP(hipGetLastError());
-    finish_pairs(h.data(), S, i_lo, i_hi, constant, 0, out);
+    if (qp) finish_query(h.data(), S, *qp, constant, 0, out);
+    else finish_pairs(h.data(), S, i_lo, i_hi, constant, 0, out);
     return SKX_OK;
 }
-int skx::planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out)
+int skx::planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out,
+                         const QueryPlan *qp)
 {
     hipStream_t st = ctx->stream;
     if (S < 2 || i_lo >= i_hi) return SKX_OK;
@@ -2332,25 +2376,30 @@ int skx::planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t w
     SKX_HIP(hipMemcpyAsync(h.data(), cnt.p, h.size() * 8, hipMemcpyDeviceToHost, st));
     SKX_HIP(hipStreamSynchronize(st));
     SKX_HIP(hipGetLastError());
-    finish_pairs(h.data(), S, i_lo, i_hi, constant, filt_ambig, out);
+    if (qp) finish_query(h.data(), S, *qp, constant, filt_ambig, out);
+    else finish_pairs(h.data(), S, i_lo, i_hi, constant, filt_ambig, out);
     return SKX_OK;
 }
 
 // generic_modes::distance (generic_modes.rs:136-189) on an array in memory without touching it: the two filters decide per row, the
 // bit planes are built over the rows that stay, the pair sweep runs on those -- no compaction of the rows x samples matrix.
-extern "C" int skx_array_distance_filtered(skx_array *a, double min_freq, int filt_ambig, skx_dist *out, int64_t *constant, uint64_t *rows_used)
+// query / n_query: nullptr / 0 = the whole table (skx_array_distance_filtered), else the rows of skx_array_distance_query_filtered
+static int distance_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query, bool is_query, skx_dist *out, int64_t *constant,
+                             uint64_t *rows_used)
 {
-    return skx_guarded([&]() -> int {
     if (!a || !out) { set_error("bad arguments"); return SKX_EINVAL; }
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     SKX_HIP(hipSetDevice(ctx->device));
     SKX_TRY(array_materialize(a));
     const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
+    QueryPlan plan; const QueryPlan *qp = nullptr;
+    if (is_query) { SKX_TRY(query_plan(a, query, n_query, plan)); qp = &plan; }
+    const int *order = qp ? qp->order.p : nullptr;
     const uint64_t S_total = a->total_samples ? a->total_samples : (uint64_t)S;
     const uint64_t thr = min_freq * (double)S_total >= 1.0 ? (uint64_t)std::ceil((double)S_total * min_freq) : 0;       // generic_modes.rs:149-159
     if (constant) *constant = 0;
     if (rows_used) *rows_used = 0;
-    if (S < 2) return SKX_OK;
+    if (S < 2) { if (qp) out[0] = skx_dist{}; return SKX_OK; }
     StageTimer t(ctx, &ctx->tm.distance);
     uint64_t kept = 0; unsigned long long n_const = 0;
     DevBuf<uint64_t> planes; uint64_t wpr = 1;
@@ -2368,20 +2417,28 @@ extern "C" int skx_array_distance_filtered(skx_array *a, double min_freq, int fi
         if (!filt_ambig && kept) {
             if (constant) *constant = (int64_t)n_const;
             if (rows_used) *rows_used = kept;
-            return distance_ambiguous_split(a, keep.p, (double)n_const, out);
+            return distance_ambiguous_split(a, keep.p, (double)n_const, out, qp);
         }
         wpr = std::max<uint64_t>((kept + 63) / 64, 1);
         SKX_TRY(planes.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * wpr));
         if (!kept) SKX_TRY(planes.zero(st));                                 // (otherwise every word is written by the plane kernel)
         launch_keep_bits(keep.p, pos.p, U, kb.p, gp.p, st);
         DevBuf<uint32_t> fg; SKX_TRY(fg.alloc(kept / 4096 + 2));
-        if (kept) launch_build_planes_keep(a->matrix.p, a->pitch, S, U, kb.p, gp.p, planes.p, wpr, filt_ambig, st, fg.p, kept);
+        if (kept) launch_build_planes_keep(a->matrix.p, a->pitch, S, U, kb.p, gp.p, planes.p, wpr, filt_ambig, st, fg.p, kept, order);
         SKX_HIP(hipStreamSynchronize(st));            // keep / pos / kb / gp go out of scope
     } else { SKX_TRY(planes.alloc((filt_ambig ? 4 : 8) * (uint64_t)S)); SKX_TRY(planes.zero(st)); }
     if (constant) *constant = (int64_t)n_const;
     if (rows_used) *rows_used = kept;
-    return planes_distance(ctx, planes.p, S, wpr, filt_ambig, (double)n_const, 0, S, out);
-    });
+    return planes_distance(ctx, planes.p, S, wpr, filt_ambig, (double)n_const, 0, qp ? qp->Q() : S, out, qp);
+}
+extern "C" int skx_array_distance_filtered(skx_array *a, double min_freq, int filt_ambig, skx_dist *out, int64_t *constant, uint64_t *rows_used)
+{
+    return skx_guarded([&]() -> int { return distance_filtered(a, min_freq, filt_ambig, nullptr, 0, false, out, constant, rows_used); });
+}
+extern "C" int skx_array_distance_query_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query, skx_dist *out, int64_t *constant,
+                                                 uint64_t *rows_used)
+{
+    return skx_guarded([&]() -> int { return distance_filtered(a, min_freq, filt_ambig, query, n_query, true, out, constant, rows_used); });
 }
 
 extern "C" int skx_array_distance_planes(skx_array *a, int filt_ambig, const void **planes, uint64_t *words_per_row, int *n_planes)
@@ -2430,6 +2487,27 @@ extern "C" int skx_array_distance(skx_array *a, double constant, int filt_ambig,
     launch_build_planes(a->matrix.p, a->pitch, S, U, planes.p, wpr, filt_ambig, st);
     SKX_TRY(planes_distance(ctx, planes.p, S, wpr, filt_ambig, constant, 0, S, out));
     return SKX_OK;
+    });
+}
+// skx_array_distance for the pairs that hold a query: the same planes in query-first order, the band of the queries
+extern "C" int skx_array_distance_query(skx_array *a, double constant, int filt_ambig, const int *query, int n_query, skx_dist *out)
+{
+    return skx_guarded([&]() -> int {
+    if (!a || !out) { set_error("bad arguments"); return SKX_EINVAL; }
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
+    QueryPlan qp;
+    SKX_TRY(query_plan(a, query, n_query, qp));
+    if (S < 2) { out[0] = skx_dist{}; return SKX_OK; }
+    StageTimer t(ctx, &ctx->tm.distance);
+    if (!filt_ambig && U) return distance_ambiguous_split(a, nullptr, constant, out, &qp);
+    const uint64_t wpr = (U + 63) / 64;
+    DevBuf<uint64_t> planes;
+    SKX_TRY(planes.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * std::max<uint64_t>(wpr, 1)));
+    launch_build_planes(a->matrix.p, a->pitch, S, U, planes.p, wpr, filt_ambig, st, qp.order.p);
+    return planes_distance(ctx, planes.p, S, wpr, filt_ambig, constant, 0, qp.Q(), out, &qp);
     });
 }
 

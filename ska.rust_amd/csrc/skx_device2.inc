@@ -343,10 +343,12 @@ void launch_differ_u32(const uint32_t *a, const uint32_t *b, uint64_t n, int *fl
 // accumulator is the lane's byte of plane p; two accumulators give the 16 bits it stores per plane -- the lanes' pieces are adjacent,
 // a wave writes 128 contiguous bytes per plane.  No LDS traffic but the table, no ballots (a ballot per plane and 64 rows per wave
 // instruction cost ~10 x the instructions: build_planes_out_kernel below has the numbers).  A workgroup serves PLS samples.
+// ORD (the query sweep): slot s of the planes holds sample order[s] -- the queries in front, so that the band form of the pair sweep covers them.
+// The identity instantiations are the code every other caller launches: `order` is not read there.
 constexpr int PLS = 8;
-template <bool FILT>
+template <bool FILT, bool ORD = false>
 __global__ __launch_bounds__(256) void build_planes_kernel(const uint8_t *matrix, uint64_t pitch, int n_samples, uint64_t n_cols, uint64_t *planes,
-                                                           uint64_t wpr, uint64_t plane_stride)
+                                                           uint64_t wpr, uint64_t plane_stride, const int *order)
 {
     constexpr int NP = FILT ? 4 : 8, NA = NP / 4;
     __shared__ uint32_t s_lut[NA][256];
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(256) void build_planes_kernel(const uint8_t *matrix
     const int s_lo = (int)blockIdx.y * PLS, s_hi = s_lo + PLS < n_samples ? s_lo + PLS : n_samples;
     auto fetch = [&](int s) {                                          // rows are padded to the pitch (>= 256 bytes past n_cols): the load stays inside the row's allocation
         u32x4 v = {0x2D2D2D2Du, 0x2D2D2D2Du, 0x2D2D2D2Du, 0x2D2D2D2Du};
-        if (c < n_cols) v = *reinterpret_cast<const u32x4 *>(matrix + (uint64_t)s * pitch + c);
+        if (c < n_cols) v = *reinterpret_cast<const u32x4 *>(matrix + (uint64_t)(ORD ? order[s] : s) * pitch + c);
         return v;
     };
     u32x4 nx = fetch(s_lo);
@@ -396,12 +398,17 @@ __global__ __launch_bounds__(256) void build_planes_kernel(const uint8_t *matrix
     }
 }
 void launch_build_planes(const uint8_t *matrix, uint64_t pitch, int n_samples, uint64_t n_cols, uint64_t *planes, uint64_t wpr, int filt,
-                         hipStream_t st)
+                         hipStream_t st, const int *order)
 {
     if (!wpr || !n_samples) return;
     const dim3 grid((unsigned)((wpr + 63) / 64), (unsigned)((n_samples + PLS - 1) / PLS));
-    if (filt) hipLaunchKernelGGL(build_planes_kernel<true>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, (uint64_t)n_samples * wpr);
-    else hipLaunchKernelGGL(build_planes_kernel<false>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, (uint64_t)n_samples * wpr);
+    const uint64_t stride = (uint64_t)n_samples * wpr;
+    if (order) {
+        if (filt) hipLaunchKernelGGL((build_planes_kernel<true, true>), grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, stride, order);
+        else hipLaunchKernelGGL((build_planes_kernel<false, true>), grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, stride, order);
+    }
+    else if (filt) hipLaunchKernelGGL(build_planes_kernel<true>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, stride, order);
+    else hipLaunchKernelGGL(build_planes_kernel<false>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, planes, wpr, stride, order);
 }
 
 // ---- planes of the kept rows only (`ska distance` on an array in memory: the filters of generic_modes::distance decide per row,
@@ -434,10 +441,11 @@ __global__ __launch_bounds__(256) void first_groups_kernel(const uint64_t *keep_
 // 1 000 samples x 22.6 M rows, 22.54 M kept (the 72 339 constant rows go; 11.3 GB of planes): 35 ms (one row per lane, a ballot per plane, one sample per workgroup: ~640 wave instructions
 // per 512 cells) -> 22 ms (this form cut by input rows, first / last word of a workgroup OR-ed into the planes atomically: 44 M global
 // atomics) -> 9.3 ms (profiles/r03zzm_build_planes.log).
-template <bool FILT>
+// ORD: as in build_planes_kernel -- slot s_lo + s holds sample order[s_lo + s]; the identity instantiations do not read `order`.
+template <bool FILT, bool ORD = false>
 __global__ __launch_bounds__(256) void build_planes_out_kernel(const uint8_t *matrix, uint64_t pitch, int n_samples, uint64_t n_cols, const uint64_t *keep_bits,
                                                                const uint64_t *gpos, const uint32_t *first_group, uint64_t kept,
-                                                               uint64_t *planes, uint64_t wpr, uint64_t plane_stride)
+                                                               uint64_t *planes, uint64_t wpr, uint64_t plane_stride, const int *order)
 {
     constexpr int NP = FILT ? 4 : 8, NA = NP / 4;
     __shared__ uint32_t s_lut[NA][256];
@@ -490,7 +498,7 @@ __global__ __launch_bounds__(256) void build_planes_out_kernel(const uint8_t *ma
         u32x2 nx[2];
         auto fetch = [&](int s) {
 #pragma unroll
-            for (int h = 0; h < 2; h++) { nx[h] = u32x2{0x2D2D2D2Du, 0x2D2D2D2Du}; if (live[h]) nx[h] = *reinterpret_cast<const u32x2 *>(matrix + (uint64_t)(s_lo + s) * pitch + c0 + 8ull * (threadIdx.x + 256u * h)); }
+            for (int h = 0; h < 2; h++) { nx[h] = u32x2{0x2D2D2D2Du, 0x2D2D2D2Du}; if (live[h]) nx[h] = *reinterpret_cast<const u32x2 *>(matrix + (uint64_t)(ORD ? order[s_lo + s] : s_lo + s) * pitch + c0 + 8ull * (threadIdx.x + 256u * h)); }
         };
         fetch(0);
         for (int s = 0; s < ns; s++) {
@@ -565,14 +573,19 @@ void launch_keep_bits(const uint8_t *keep, const uint64_t *pos, uint64_t n, uint
 }
 // planes must be zeroed; wpr = words per sample of the KEPT rows
 void launch_build_planes_keep(const uint8_t *matrix, uint64_t pitch, int n_samples, uint64_t n_cols, const uint64_t *keep_bits, const uint64_t *gpos,
-                              uint64_t *planes, uint64_t wpr, int filt, hipStream_t st, uint32_t *first_group, uint64_t kept)
+                              uint64_t *planes, uint64_t wpr, int filt, hipStream_t st, uint32_t *first_group, uint64_t kept, const int *order)
 {
     if (!n_cols || !n_samples || !wpr || !kept) return;
     const uint64_t n_groups = (n_cols + 63) / 64;
     hipLaunchKernelGGL(first_groups_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, st, keep_bits, gpos, n_groups, first_group);
     const dim3 grid((unsigned)((kept + 4095) / 4096), (unsigned)((n_samples + PS - 1) / PS));
-    if (filt) hipLaunchKernelGGL(build_planes_out_kernel<true>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, (uint64_t)n_samples * wpr);
-    else hipLaunchKernelGGL(build_planes_out_kernel<false>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, (uint64_t)n_samples * wpr);
+    const uint64_t stride = (uint64_t)n_samples * wpr;
+    if (order) {
+        if (filt) hipLaunchKernelGGL((build_planes_out_kernel<true, true>), grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, stride, order);
+        else hipLaunchKernelGGL((build_planes_out_kernel<false, true>), grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, stride, order);
+    }
+    else if (filt) hipLaunchKernelGGL(build_planes_out_kernel<true>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, stride, order);
+    else hipLaunchKernelGGL(build_planes_out_kernel<false>, grid, dim3(256), 0, st, matrix, pitch, n_samples, n_cols, keep_bits, gpos, first_group, kept, planes, wpr, stride, order);
 }
 
 // filter-ambiguous pair counts from the 4-plane layout: a 64 x 64 tile of sample pairs per workgroup, 4 x 2 pairs per thread

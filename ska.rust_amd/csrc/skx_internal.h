@@ -336,13 +336,16 @@ int reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std:
 int dictset_sort(skx_dictset *d);                                    // raw regions -> sorted, folded regions + sub-index (no-op when they are)
 int keyset_flatten(skx_keyset *ks);                                  // ks->flat = the rows as one compact list of packed words (engine order)
 int keyset_union_tables(skx_ctx *ctx, const uint64_t *words, const std::vector<uint64_t> &h_off, const std::vector<uint32_t> &h_cnt, int k, int rc, skx_keyset **out);
-int planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out);
+struct QueryPlan;                                                    // skx_api.cpp: the query-first order of skx_array_distance_query (nullptr: the table's pairs)
+int planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out,
+                    const QueryPlan *qp = nullptr);
 // --allow-ambiguous with the rows split by whether one of their cells is ambiguous: planes_clean = 4 planes (FILT) of the rows without such a cell
 // (counts filed as classes 0-2), planes_dirty = 8 planes of the others; either may be absent (nullptr / 0 rows)
 int planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint64_t wpr_clean, uint64_t rows_clean, const uint64_t *planes_dirty, uint64_t wpr_dirty,
-                          uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out);
+                          uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp = nullptr);
 // bit planes of the rows flagged 1 in keep (4 planes with filt, else 8): every word written; rows = how many
-int planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows);
+// (order: launch_build_planes_keep's, device memory or nullptr)
+int planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows, const int *order = nullptr);
 int cpu_budget();                                                    // CPUs the process may keep busy (hardware threads, or the control group's quota)
 int check_k(int k);                                                  // "Invalid k-mer length" (ska_dict.rs:342-344)
 bool mappable_output_fd(int fd, off_t *pos);                         // regular file, read-write, not O_APPEND: can be written through a mapping

@@ -65,7 +65,10 @@ const std::vector<Cmd> &commands()
           {"--tree", "<FILE>", "(MI355X engine) Write the midpoint-rooted neighbour-joining tree of the distances (Newick) to this file"},
           {"--clusters", "<PREFIX>", "(MI355X engine) Write single-linkage clusters to <PREFIX>.clusters.csv and their graph to <PREFIX>.graph.dot"},
           {"--cluster-snps", "<N>", "(MI355X engine) Largest SNP distance that links two samples (with --clusters) [default: 10]"},
-          {"--cluster-mismatches", "<P>", "(MI355X engine) Largest mismatch proportion that links two samples (with --clusters) [default: 1.0]"}}},
+          {"--cluster-mismatches", "<P>", "(MI355X engine) Largest mismatch proportion that links two samples (with --clusters) [default: 1.0]"},
+          {"--query", "<NAMES>", "(MI355X engine) Print only the table's lines that name one of these samples (comma separated)"},
+          {"--query-file", "<FILE>", "(MI355X engine) The same, sample names from a file (one per line)"},
+          {"--query-skf", "<FILE>", "(MI355X engine) Merge this .skf into <SKF_FILE> in memory and print the lines that name one of its samples"}}},
         {"merge", "Combine multiple split k-mer files", "ska merge -o <OUTPUT> [SKF_FILES]...",
          {{"[SKF_FILES]...", "", "List of input split-kmer (.skf) files"}},
          {{"-o", "<OUTPUT>", "Output prefix"}}},

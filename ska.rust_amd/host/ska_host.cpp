@@ -3,6 +3,7 @@
 // get_input_list / load_array / set_ostream; cli.rs + lib.rs:557-727,808-827 for build | align | distance | nk).
 // Written in C++ because the image has no Rust toolchain; it only talks to the engine through include/skx.h.
 #include "../../include/skx_host.h"
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -138,6 +139,7 @@ extern "C" int skh_align_fd(skx_array *a, int filter_type, int mask_ambig, int i
 
 static int distance_text(skx_array *a, const std::vector<skx_dist> &d, char **buf, uint64_t *len);
 static int distance_text_names(const std::vector<const char *> &names, const skx_dist *d, char **buf, uint64_t *len);
+static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, skx_array **merged, std::vector<uint64_t> *n_each = nullptr);
 extern "C" int skh_distance_tsv(skx_array *a, double min_freq, int filt_ambig, char **buf, uint64_t *len)
 {
     return skx_guarded([&]() -> int {
@@ -158,6 +160,11 @@ static int distance_text(skx_array *a, const std::vector<skx_dist> &d, char **bu
     for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
     return distance_text_names(names, d.data(), buf, len);
 }
+static const char DIST_HEADER[] = "Sample1\tSample2\tDistance\tMismatches (proportion)\tMatch count\tMismatch count\n";
+static void put_dist_line(std::string &o, const char *n1, const char *n2, const skx_dist &d)
+{
+    put(o, "%s\t%s\t%.2f\t%.5f\t%llu\t%llu\n", n1, n2, d.distance, d.mismatch_prop, (unsigned long long)d.match_count, (unsigned long long)d.mismatch_count);
+}
 static int distance_text_names(const std::vector<const char *> &names, const skx_dist *d, char **buf, uint64_t *len)
 {
     const uint64_t S = names.size();
@@ -170,16 +177,14 @@ static int distance_text_names(const std::vector<const char *> &names, const skx
         for (uint64_t i; (i = next.fetch_add(1)) < S;) {
             size_t n = (size_t)(i * (2 * S - i - 1) / 2);               // pairs before row i
             std::string &o = part[i];
-            for (uint64_t j = i + 1; j < S; j++, n++)
-                put(o, "%s\t%s\t%.2f\t%.5f\t%llu\t%llu\n", names[i], names[j], d[n].distance, d[n].mismatch_prop,
-                    (unsigned long long)d[n].match_count, (unsigned long long)d[n].mismatch_count);
+            for (uint64_t j = i + 1; j < S; j++, n++) put_dist_line(o, names[i], names[j], d[n]);
         }
     };
     std::vector<std::thread> th;
     for (int t = 1; t < T; t++) th.emplace_back(work);
     work();
     for (auto &t : th) t.join();
-    std::string out = "Sample1\tSample2\tDistance\tMismatches (proportion)\tMatch count\tMismatch count\n";
+    std::string out = DIST_HEADER;
     size_t total = out.size();
     for (auto &x : part) total += x.size();
     out.reserve(total);
@@ -251,6 +256,80 @@ extern "C" int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, d
     r = distance_table(a, (double)constant, filt_ambig, extras, buf, len);
     skx_array_free(a);
     return r;
+    });
+}
+
+// the lines of distance_text_names' table that name a query, in its order (ascending first sample, then ascending second); d as
+// skx_array_distance_query lays it out: d[q * S + j] = the pair (query[q], j)
+static int distance_query_text(const std::vector<const char *> &names, const std::vector<int> &query, const skx_dist *d, char **buf, uint64_t *len)
+{
+    const uint64_t S = names.size();
+    Phase pt("distance.table_text");
+    std::vector<int> row_of(S, -1), sorted(query);
+    for (size_t q = 0; q < query.size(); q++) row_of[query[q]] = (int)q;
+    std::sort(sorted.begin(), sorted.end());
+    const int T = (int)std::min<uint64_t>(std::max<uint64_t>(1, S / 16), std::min(32u, std::max(1u, std::thread::hardware_concurrency())));
+    std::vector<std::string> part(S);
+    std::atomic<uint64_t> next{0};
+    auto work = [&]() {
+        for (uint64_t i; (i = next.fetch_add(1)) < S;) {
+            std::string &o = part[i];
+            if (row_of[i] >= 0) for (uint64_t j = i + 1; j < S; j++) put_dist_line(o, names[i], names[j], d[(uint64_t)row_of[i] * S + j]);
+            else for (auto it = std::upper_bound(sorted.begin(), sorted.end(), (int)i); it != sorted.end(); ++it)
+                put_dist_line(o, names[i], names[*it], d[(uint64_t)row_of[*it] * S + i]);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    std::string out = DIST_HEADER;
+    size_t total = out.size();
+    for (auto &x : part) total += x.size();
+    out.reserve(total);
+    for (auto &x : part) out += x;
+    return to_buf(out, buf, len);
+}
+extern "C" int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const char *query_skf, const char *const *names, int n_names, double min_freq,
+                                      int filt_ambig, char **buf, uint64_t *len)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !skf_file || !buf || !len || n_names < 0 || (n_names && !names)) { skx_set_error("skh_distance_query_tsv: bad arguments"); return SKX_EINVAL; }
+    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
+    skx_array *a = nullptr; int64_t removed = 0, constant = 0; int r;
+    std::vector<uint64_t> n_each;
+    if (query_skf) {                                                                   // `ska merge skf_file query_skf`, kept in memory
+        const char *files[2] = {skf_file, query_skf};
+        if ((r = merge_files(ctx, files, 2, &a, &n_each)) != SKX_OK) return r;
+    } else {
+        skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
+        if ((r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant)) != SKX_OK) return r;
+    }
+    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
+    skx_array_info_t info; skx_array_info(a, &info);
+    const uint64_t S = info.n_samples;
+    std::vector<const char *> all(S);
+    for (uint64_t i = 0; i < S; i++) all[i] = skx_array_name(a, i);
+    // the query set: the names (each its first match, as skx_array_delete_samples looks them up) and every sample the second file brought
+    std::vector<char> is_q(S, 0);
+    for (int n = 0; n < n_names; n++) {
+        uint64_t i = 0;
+        while (i < S && strcmp(all[i], names[n]) != 0) i++;
+        if (i == S) { skx_set_error("Could not find sample(s): {\"%s\"}", names[n]); return SKX_EINVAL; }                     // merge_ska_array.rs:252-254
+        is_q[i] = 1;
+    }
+    if (query_skf) for (uint64_t i = std::min<uint64_t>(n_each[0], S); i < S; i++) is_q[i] = 1;               // (the first file's samples come first)
+    std::vector<int> query;
+    for (uint64_t i = 0; i < S; i++) if (is_q[i]) query.push_back((int)i);
+    if (query.empty()) { skx_set_error("No query samples given"); return SKX_EINVAL; }
+    std::vector<skx_dist> d(query.size() * S);
+    {
+        Phase pd("distance.pair_sweep");
+        if (query_skf) { uint64_t rows = 0; r = skx_array_distance_query_filtered(a, min_freq, filt_ambig, query.data(), (int)query.size(), d.data(), &constant, &rows); }
+        else r = skx_array_distance_query(a, (double)constant, filt_ambig, query.data(), (int)query.size(), d.data());
+        if (r != SKX_OK) return r;
+    }
+    return distance_query_text(all, query, d.data(), buf, len);
     });
 }
 
@@ -353,9 +432,10 @@ extern "C" int skh_load_array(skx_ctx *ctx, const char *const *inputs, int n_inp
     });
 }
 
-extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files, const char *out_prefix)
+// the files of `ska merge` loaded and merged in memory (skh_merge saves the result, `ska distance --query-skf` sweeps it)
+// n_each (optional): the samples each file brought, in file order -- the merged array holds them in that order
+static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, skx_array **merged, std::vector<uint64_t> *n_each)
 {
-    return skx_guarded([&]() -> int {
     if (n_files < 2) { skx_set_error("Need at least two files to merge"); return SKX_EINVAL; }                    // lib.rs:729-731
     std::vector<skx_array *> arrs(n_files, nullptr);
     auto cleanup = [&]() { for (auto p : arrs) if (p) skx_array_free(p); };
@@ -402,6 +482,7 @@ extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files
             cleanup(); skx_set_error("Failed to load input file (inconsistent k-mer lengths?): %s", skf_files[i]); return SKX_EINVAL;
         }
     skx_phase_add("merge.other_files_wall", since(t_m1));
+    if (n_each) for (auto p : arrs) { skx_array_info_t info; skx_array_info(p, &info); n_each->push_back(info.n_samples); }
     const auto t_m2 = std::chrono::steady_clock::now();
     skx_array *m = nullptr;
     int r = skx_array_merge(ctx, arrs.data(), n_files, &m);
@@ -409,6 +490,15 @@ extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files
     const auto t_m3 = std::chrono::steady_clock::now();
     cleanup();
     skx_phase_add("merge.release_inputs_wall", since(t_m3));
+    if (r != SKX_OK) return r;
+    *merged = m;
+    return SKX_OK;
+}
+extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files, const char *out_prefix)
+{
+    return skx_guarded([&]() -> int {
+    skx_array *m = nullptr;
+    int r = merge_files(ctx, skf_files, n_files, &m);
     if (r != SKX_OK) return r;
     r = skh_save_skf(m, out_prefix);
     skx_array_free(m);
@@ -709,7 +799,7 @@ struct Args {
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
-                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", nullptr};
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -822,6 +912,23 @@ struct DistExtras {
     }
     const skh_dist_extras *get() const { return x.tree || x.clusters ? &x : nullptr; }
 };
+// --query / --query-file of `ska distance`: the names of both, repeats collapsed.  0, or the exit code after the refusal was printed
+const struct { const char *flag, *arg; } QUERY_OPTS[] = {{"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
+bool has_query(const Args &a) { for (auto &q : QUERY_OPTS) if (a.has(q.flag)) return true; return false; }
+int read_query_names(const Args &a, std::vector<std::string> &names)
+{
+    auto add = [&](const std::string &n) { if (!n.empty() && std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n); };
+    for (auto &o : a.opt) {
+        if (o.first == "--query") { std::istringstream ls(o.second); std::string t; while (std::getline(ls, t, ',')) add(t); }
+        else if (o.first == "--query-file") {                                          // io_utils::get_input_list as `ska delete -f` reads it: first column
+            std::ifstream in(o.second);
+            if (!in) return fail("Unable to open file_list");
+            std::string line;
+            while (std::getline(in, line)) { std::istringstream ls(line); std::string t; if (ls >> t) add(t); }
+        }
+    }
+    return 0;
+}
 struct BuildOpts { int k = 31; skx_qual q{5, 20, SKX_QUAL_STRICT}; bool auto_count = false; double prop = 0.0; };
 int parse_build_opts(const Args &a, BuildOpts &o)                                      // cli.rs:27-108 (Build)
 {
@@ -1095,6 +1202,21 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (v.find_first_not_of("0123456789") != std::string::npos || v.empty()) return clap_invalid(v, "--threads <THREADS>", ("`" + v + "` isn't a valid number of cores").c_str());
         if (atoi(v.c_str()) < 1) return clap_invalid(v, "--threads <THREADS>", "Threads must be one or higher");
     }
+    if (cmd == "distance" && has_query(a)) {
+        // the query is cut from one device's table, and the tree and the clusters need all of it: refused as clap refuses arguments that conflict
+        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"},
+                                                                {"--cluster-mismatches", "--cluster-mismatches <P>"}, {"--gpus", "--gpus <GPUS>"}};
+        for (auto &q : QUERY_OPTS)
+            for (auto &o : others)
+                if (a.has(q.flag) && (a.has(o.first) || (multi && !strcmp(o.first, "--gpus")))) {
+                    fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", q.arg, o.second, skh_usage_line("distance"));
+                    return 2;
+                }
+        for (auto &q : QUERY_OPTS) if (a.has(q.flag) && a.get(q.flag).empty()) return clap_invalid("", q.arg, "a value is required");
+        std::vector<std::string> names;
+        if (int e = read_query_names(a, names)) return e;
+        if (names.empty() && !a.has("--query-skf")) return clap_invalid(a.get("--query", a.get("--query-file")), a.has("--query") ? "--query <NAMES>" : "--query-file <FILE>", "no sample names given");
+    }
     const bool files_from_build = multi && (cmd == "align" || cmd == "distance");        // (--gpus N: sequence files or -f, and the build options)
     if (cmd == "build" || files_from_build) {
         if (cmd == "build" && !a.has("-o")) return clap_missing("build", "-o <OUTPUT>");
@@ -1187,7 +1309,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1277,7 +1399,16 @@ extern "C" int skh_main(int argc, char **argv)
         char *buf = nullptr; uint64_t len = 0;
         (void)in;
         const DistExtras dx(a);
-        if (skh_distance_skf_tsv_extras(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get(), &buf, &len) != SKX_OK)
+        if (has_query(a)) {
+            std::vector<std::string> names; std::vector<const char *> cn;
+            if (int e = read_query_names(a, names)) return e;
+            for (auto &n : names) cn.push_back(n.c_str());
+            const std::string qskf = a.get("--query-skf");
+            if (skh_distance_query_tsv(ctx, a.pos[0].c_str(), a.has("--query-skf") ? qskf.c_str() : nullptr, cn.data(), (int)cn.size(), mf, !a.has("--allow-ambiguous"), &buf, &len) != SKX_OK)
+                rcode = engine_fail();
+            else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
+        }
+        else if (skh_distance_skf_tsv_extras(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get(), &buf, &len) != SKX_OK)
             rcode = engine_fail();
         else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
     } else if (cmd == "nk") {

@@ -79,7 +79,8 @@ skx_comm_allgather skx_comm_allreduce_u32 skx_comm_gather_root skx_shard_range s
 skh_build_sharded skh_align_sharded skh_distance_sharded
 skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf skh_load_array skh_sample_name skh_main skh_merge skh_delete skh_weed skh_cov skh_cov_fit skh_align_inputs_fd skh_distance_skf_tsv skh_help skh_log
 skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo
-skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras""".split()
+skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras
+skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv""".split()
 
 _lib = None
 
@@ -109,6 +110,9 @@ def load_library():
     lib.skh_nj_newick.argtypes = [C.POINTER(cp), vp, i, pp, C.POINTER(u64)]
     lib.skh_distance_clusters.argtypes = [C.POINTER(cp), vp, i, d, d, pp, C.POINTER(u64), pp, C.POINTER(u64)]
     lib.skh_distance_skf_tsv_extras.argtypes = [vp, cp, d, i, C.POINTER(DistExtras), pp, C.POINTER(u64)]
+    lib.skx_array_distance_query.argtypes = [vp, d, i, vp, i, vp]
+    lib.skx_array_distance_query_filtered.argtypes = [vp, d, i, vp, i, vp, C.POINTER(C.c_int64), C.POINTER(u64)]
+    lib.skh_distance_query_tsv.argtypes = [vp, cp, cp, C.POINTER(cp), i, d, i, pp, C.POINTER(u64)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -409,6 +413,15 @@ class Context:
         p, n = C.c_void_p(), C.c_uint64()
         _check(_lib.skh_distance_skf_tsv_extras(self.h, skf_file.encode(), min_freq, int(filt_ambig), C.byref(x) if tree or clusters else None,
                                                 C.byref(p), C.byref(n)))
+        return _take(p, n)
+
+    def distance_query_tsv(self, skf_file, names=(), query_skf=None, min_freq=0.0, filt_ambig=True):
+        """`ska distance <skf> --query NAMES [--query-skf FILE]` (skh_distance_query_tsv) -> the header and the table's lines that name a query"""
+        names = list(names)
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.skh_distance_query_tsv(self.h, skf_file.encode(), query_skf.encode() if query_skf else None, arr, len(names), float(min_freq),
+                                           int(filt_ambig), C.byref(p), C.byref(n)))
         return _take(p, n)
 
     def close(self):
@@ -944,6 +957,21 @@ class Array:
         cst, rows = C.c_int64(), C.c_uint64()
         _check(_lib.skx_array_distance_filtered(self.h, float(min_freq), int(filt_ambig), _np_ptr(out), C.byref(cst), C.byref(rows)))
         return out[: s * (s - 1) // 2], cst.value, rows.value
+
+    def distance_query(self, query, constant=0.0, filt_ambig=True):
+        """skx_array_distance_query: out[q][j] = the pair (query[q], j) as `distance` gives it, the entry j == query[q] zeroed"""
+        q = np.ascontiguousarray(query, np.int32)
+        out = np.zeros((max(len(q), 1), self.nsamples), DIST_DT)
+        _check(_lib.skx_array_distance_query(self.h, float(constant), int(filt_ambig), _np_ptr(q), len(q), _np_ptr(out)))
+        return out[: len(q)]
+
+    def distance_query_filtered(self, query, min_freq=0.0, filt_ambig=True):
+        """skx_array_distance_query_filtered -> (out[q][j] as `distance_filtered` gives the pair, constant sites, rows used)"""
+        q = np.ascontiguousarray(query, np.int32)
+        out = np.zeros((max(len(q), 1), self.nsamples), DIST_DT)
+        cst, rows = C.c_int64(), C.c_uint64()
+        _check(_lib.skx_array_distance_query_filtered(self.h, float(min_freq), int(filt_ambig), _np_ptr(q), len(q), _np_ptr(out), C.byref(cst), C.byref(rows)))
+        return out[: len(q)], cst.value, rows.value
 
     def distance_planes(self, filt_ambig=True):
         """device pointer to this array's bit planes [n_planes][n_samples][words_per_row] -> (ptr, words_per_row, n_planes)"""
