@@ -206,6 +206,32 @@ int  skx_array_distance_filtered(skx_array *a, double min_freq, int filt_ambig, 
 int  skx_array_distance_query(skx_array *a, double constant, int filt_ambig, const int *query, int n_query, skx_dist *out);
 int  skx_array_distance_query_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query,
                                        skx_dist *out, int64_t *constant, uint64_t *rows_used);
+/* The lines of that table a user of a large collection asks for (`ska distance --max-snps / --max-mismatches / --closest`; the reference leaves
+ * the selection to scripts/cluster_dists.py), picked on the device band by band over the pair matrix, so that device and host memory are
+ * O(band x n_samples + selected pairs) instead of O(n_samples^2).  A pair's values are the skx_dist skx_array_distance_filtered gives it, compared
+ * as those doubles: max_snps keeps distance <= max_snps, max_mismatches keeps mismatch_prop <= max_mismatches; a pair that passes every threshold
+ * given is a candidate.  closest = K: for every sample its candidate partners ordered by (distance, partner index), the first min(K, how many)
+ * of them its nearest; a pair is kept when either of its samples has the other among its nearest.  K >= n_samples - 1 is no constraint.
+ * band_rows: first samples of the pair matrix swept at a time (any positive value is taken as given). */
+typedef struct {
+    double  max_snps;        /* < 0: none */
+    double  max_mismatches;  /* < 0: none; at most 1 */
+    int32_t closest;         /* 0: none; at most 1 024 unless >= n_samples - 1 */
+    int32_t band_rows;       /* 0: the engine's choice -- the largest multiple of 64 whose count buffer stays within 1 GiB, at least 64 */
+} skx_select_spec;
+typedef struct { uint32_t i, j; skx_dist d; } skx_dist_pair;               /* i < j: sample indices; d: bit for bit the full table's entry */
+/* what a call did: bands swept, first samples per band, bytes of the device count buffer, pairs that passed the thresholds */
+typedef struct { uint64_t bands, band_rows, count_buffer_bytes, candidates; } skx_select_info;
+/* pairs: malloc'd (skx_free), n_pairs of them ascending by (i, j), i.e. in the table's order; constant / rows_used as skx_array_distance_filtered
+ * reports them; info may be NULL.  SKX_EINVAL with a message that begins "distance select:" for a NaN, max_mismatches > 1, closest < 0,
+ * 1 024 < closest < n_samples - 1, band_rows < 0 or none of the three criteria given.  Fewer than two samples: zero pairs.  The array is left as
+ * it is; both key widths and arrays held as pieces are taken. */
+int  skx_array_distance_select(skx_array *a, double min_freq, int filt_ambig, const skx_select_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                               int64_t *constant, uint64_t *rows_used, skx_select_info *info);
+/* The same selection on an array the two filters have been applied to already (skx_array_load_filtered), as skx_array_distance_query is to
+ * skx_array_distance_query_filtered: every row is swept and `constant` (>= 0, else SKX_EINVAL) is added to every pair's matches. */
+int  skx_array_distance_select_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_select_spec *spec, skx_dist_pair **pairs,
+                                           uint64_t *n_pairs, skx_select_info *info);
 /* The two halves of skx_array_distance, so that a multi-GPU host can exchange the bit planes between them (SURVEY.md 8e:
  * "tile the pair matrix over ranks"): every rank builds the planes of its own samples over the (globally filtered) rows, the
  * planes are all-gathered (plane-major: planes[p][sample][word], 4 planes with filt_ambig, 8 without), and each rank

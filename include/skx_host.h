@@ -39,6 +39,9 @@ int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, double min_f
  * skx_array_distance_query_filtered.  An empty query set is SKX_EINVAL. */
 int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const char *query_skf, const char *const *names, int n_names, double min_freq,
                            int filt_ambig, char **buf, uint64_t *len);
+/* `ska distance <skf> --max-snps / --max-mismatches / --closest`: the header and exactly those lines of skh_distance_skf_tsv's table that
+ * skx_array_distance_select keeps under `spec`, in the table's order and text.  The same one-pass filtered load; the full table is never formed. */
+int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_select_spec *spec, char **buf, uint64_t *len);
 /* the joins of skx_dist_nj / skx_matrix_nj over n leaves as one line of Newick (host only).  A negative raw length is written as 0 and the
  * difference moved to the sibling branch of the same join, so the distance between the two joined nodes is kept (Kuhner-Felsenstein).
  * Midpoint root: the two leaves with the largest path distance in the corrected tree (ties to the lowest (id, id)), the root half way

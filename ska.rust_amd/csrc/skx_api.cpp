@@ -2234,23 +2234,35 @@ extern "C" int skx_array_write_fasta(skx_array *a, int fd)
     });
 }
 
-// numerators over 36 of |S1 n S2| / (|S1||S2|) per pair class [2..11] of pair_counts_kernel<false>
-static const int PAIR_CLASS_NUM[10] = {36, 18, 12, 9, 18, 6, 12, 4, 8, 12};
-
-// pair-class counts -> VariantDist (merge_ska_array.rs:596-631), pairs (i in [i_lo, i_hi), j > i) row-major; h rows are relative to i_lo
-static void finish_pair(const unsigned long long *c, double constant, int filt_ambig, skx_dist &o)
+// pair-class counts -> VariantDist (merge_ska_array.rs:596-631), pairs (i in [i_lo, i_hi), j > i) row-major; h rows are relative to i_lo.
+// In two steps, because the line selection (skx_select.hip) does the first on the device and hands the integers over: the counts -> mismatches,
+// m (what joins the constant in the matches) and key (the exact numerator of the distance: over 1 with filt_ambig, over 36 without;
+// pair_class_num in skx_internal.h); the integers -> the table's doubles
+static void pair_integers(const unsigned long long *c, int filt_ambig, unsigned long long &mism, unsigned long long &m, unsigned long long &key)
 {
-    double mismatches = (double)c[0], matches = constant, distance;
-    if (filt_ambig) { matches += (double)c[2]; distance = (double)(c[2] - c[3]); }
+    mism = c[0];
+    if (filt_ambig) { m = c[2]; key = c[2] - c[3]; }
     else {
-        unsigned long long m = 0, num = 0;
-        for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)PAIR_CLASS_NUM[q]; }
-        matches += (double)m;
-        distance = (double)(36ull * c[1] - num) / 36.0;
+        unsigned long long num = 0;
+        m = 0;
+        for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)pair_class_num(q); }
+        key = 36ull * c[1] - num;
     }
-    o.distance = distance;
+}
+static inline double key_distance(unsigned long long key, int filt_ambig) { return filt_ambig ? (double)key : (double)key / 36.0; }
+static void finish_counts(unsigned long long mism, unsigned long long m, unsigned long long key, double constant, int filt_ambig, skx_dist &o)
+{
+    double mismatches = (double)mism, matches = constant;
+    matches += (double)m;
+    o.distance = key_distance(key, filt_ambig);
     o.mismatch_prop = (matches + mismatches) == 0.0 ? 0.0 : mismatches / (matches + mismatches);
     o.match_count = (uint64_t)matches; o.mismatch_count = (uint64_t)mismatches;
+}
+static void finish_pair(const unsigned long long *c, double constant, int filt_ambig, skx_dist &o)
+{
+    unsigned long long mism, m, key;
+    pair_integers(c, filt_ambig, mism, m, key);
+    finish_counts(mism, m, key, constant, filt_ambig, o);
 }
 static void finish_pairs(const unsigned long long *h, int S, int i_lo, int i_hi, double constant, int filt_ambig, skx_dist *out)
 {
@@ -2317,19 +2329,17 @@ int skx::planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf
     SKX_HIP(hipStreamSynchronize(st));            // pos / kb / gp / fg go out of scope
     return SKX_OK;
 }
-// --allow-ambiguous over the rows flagged in keep (nullptr: all): the twelve pair classes differ from the three of the default sweep only on rows
-// that hold an ambiguous cell (the row statistics say which), so the rows without one go through the 4-plane sweep, their counts filed as classes
-// 0-2, and only the others through the 8-plane, twelve-class one (merge_ska_array.rs:587-632 sums per row: any split of the rows gives the sums)
-// qp: the query form -- planes in query-first order, the band of the queries, out as skx_array_distance_query lays it out
-static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double constant, skx_dist *out, const QueryPlan *qp = nullptr)
+// the planes a sweep runs on: one set (p: 4 planes with filt_ambig, 8 without), or the clean / dirty split of --allow-ambiguous
+struct SweepPlanes { DevBuf<uint64_t> p, pc, pd; uint64_t wpr = 1, wc = 1, wd = 1, nc = 0, nd = 0; bool split = false; };
+static int ambiguous_split_planes(skx_array *a, const uint8_t *keep, const int *order, SweepPlanes &sp)
 {
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
     DevBuf<uint8_t> clean, dirty;
     SKX_TRY(clean.alloc(U)); SKX_TRY(dirty.alloc(U));
     launch_split_keep(keep, a->mask.p, U, clean.p, dirty.p, st, knob("stale_row_mask") ? 2 : 0);
-    DevBuf<uint64_t> pc, pd; uint64_t wc = 1, wd = 1, nc = 0, nd = 0;
-    const int *order = qp ? qp->order.p : nullptr;
+    DevBuf<uint64_t> &pc = sp.pc, &pd = sp.pd; uint64_t &wc = sp.wc, &wd = sp.wd, &nc = sp.nc, &nd = sp.nd;
+    sp.split = true;
     SKX_TRY(planes_of_kept_rows(a, clean.p, 1, pc, wc, nc, order));
     if (nc) {
         // the split rests on the row statistics: on a clean row every present cell is one base, i.e. plane 0 (present) == plane 1 (unambiguous).
@@ -2342,8 +2352,17 @@ static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double co
         SKX_HIP(hipStreamSynchronize(st));
         if (differ) { launch_split_keep(keep, a->mask.p, U, clean.p, dirty.p, st, 1); nc = 0; pc.release(); }
     }
-    SKX_TRY(planes_of_kept_rows(a, dirty.p, 0, pd, wd, nd, order));
-    return planes_distance_split(ctx, pc.p, wc, nc, pd.p, wd, nd, S, constant, 0, qp ? qp->Q() : S, out, qp);
+    return planes_of_kept_rows(a, dirty.p, 0, pd, wd, nd, order);
+}
+// --allow-ambiguous over the rows flagged in keep (nullptr: all): the twelve pair classes differ from the three of the default sweep only on rows
+// that hold an ambiguous cell (the row statistics say which), so the rows without one go through the 4-plane sweep, their counts filed as classes
+// 0-2, and only the others through the 8-plane, twelve-class one (merge_ska_array.rs:587-632 sums per row: any split of the rows gives the sums)
+// qp: the query form -- planes in query-first order, the band of the queries, out as skx_array_distance_query lays it out
+static int distance_ambiguous_split(skx_array *a, const uint8_t *keep, double constant, skx_dist *out, const QueryPlan *qp = nullptr)
+{
+    SweepPlanes sp;
+    SKX_TRY(ambiguous_split_planes(a, keep, qp ? qp->order.p : nullptr, sp));
+    return planes_distance_split(a->ctx, sp.pc.p, sp.wc, sp.nc, sp.pd.p, sp.wd, sp.nd, (int)a->names.size(), constant, 0, qp ? qp->Q() : (int)a->names.size(), out, qp);
 }
 int skx::planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint64_t wpr_clean, uint64_t rows_clean, const uint64_t *planes_dirty, uint64_t wpr_dirty,
                                uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp)
@@ -2381,28 +2400,15 @@ int skx::planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t w
     return SKX_OK;
 }
 
-// generic_modes::distance (generic_modes.rs:136-189) on an array in memory without touching it: the two filters decide per row, the
-// bit planes are built over the rows that stay, the pair sweep runs on those -- no compaction of the rows x samples matrix.
-// query / n_query: nullptr / 0 = the whole table (skx_array_distance_filtered), else the rows of skx_array_distance_query_filtered
-static int distance_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query, bool is_query, skx_dist *out, int64_t *constant,
-                             uint64_t *rows_used)
+// the planes of the rows the two filters keep (sp: one set, or the split when --allow-ambiguous has rows to sweep); n_const = rows the NoConst stage removes
+static int filtered_planes(skx_array *a, double min_freq, int filt_ambig, const int *order, SweepPlanes &sp, unsigned long long &n_const, uint64_t &kept)
 {
-    if (!a || !out) { set_error("bad arguments"); return SKX_EINVAL; }
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
-    SKX_HIP(hipSetDevice(ctx->device));
-    SKX_TRY(array_materialize(a));
     const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
-    QueryPlan plan; const QueryPlan *qp = nullptr;
-    if (is_query) { SKX_TRY(query_plan(a, query, n_query, plan)); qp = &plan; }
-    const int *order = qp ? qp->order.p : nullptr;
     const uint64_t S_total = a->total_samples ? a->total_samples : (uint64_t)S;
     const uint64_t thr = min_freq * (double)S_total >= 1.0 ? (uint64_t)std::ceil((double)S_total * min_freq) : 0;       // generic_modes.rs:149-159
-    if (constant) *constant = 0;
-    if (rows_used) *rows_used = 0;
-    if (S < 2) { if (qp) out[0] = skx_dist{}; return SKX_OK; }
-    StageTimer t(ctx, &ctx->tm.distance);
-    uint64_t kept = 0; unsigned long long n_const = 0;
-    DevBuf<uint64_t> planes; uint64_t wpr = 1;
+    kept = 0; n_const = 0;
+    DevBuf<uint64_t> &planes = sp.p; uint64_t &wpr = sp.wpr;
     if (U) {
         DevBuf<uint8_t> keep; DevBuf<uint64_t> pos, sc_offs, kb, gp; DevBuf<uint32_t> sc_sums; DevBuf<unsigned long long> d_c;
         SKX_TRY(keep.alloc(U)); SKX_TRY(pos.alloc(U + 1)); SKX_TRY(sc_sums.alloc(scan_u8_blocks(U))); SKX_TRY(sc_offs.alloc(scan_u8_blocks(U) + 1));
@@ -2414,11 +2420,7 @@ static int distance_filtered(skx_array *a, double min_freq, int filt_ambig, cons
         SKX_HIP(hipMemcpyAsync(&kept, pos.p + U, 8, hipMemcpyDeviceToHost, st));
         SKX_HIP(hipMemcpyAsync(&n_const, d_c.p, 8, hipMemcpyDeviceToHost, st));
         SKX_HIP(hipStreamSynchronize(st));
-        if (!filt_ambig && kept) {
-            if (constant) *constant = (int64_t)n_const;
-            if (rows_used) *rows_used = kept;
-            return distance_ambiguous_split(a, keep.p, (double)n_const, out, qp);
-        }
+        if (!filt_ambig && kept) return ambiguous_split_planes(a, keep.p, order, sp);
         wpr = std::max<uint64_t>((kept + 63) / 64, 1);
         SKX_TRY(planes.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * wpr));
         if (!kept) SKX_TRY(planes.zero(st));                                 // (otherwise every word is written by the plane kernel)
@@ -2427,9 +2429,33 @@ static int distance_filtered(skx_array *a, double min_freq, int filt_ambig, cons
         if (kept) launch_build_planes_keep(a->matrix.p, a->pitch, S, U, kb.p, gp.p, planes.p, wpr, filt_ambig, st, fg.p, kept, order);
         SKX_HIP(hipStreamSynchronize(st));            // keep / pos / kb / gp go out of scope
     } else { SKX_TRY(planes.alloc((filt_ambig ? 4 : 8) * (uint64_t)S)); SKX_TRY(planes.zero(st)); }
+    return SKX_OK;
+}
+// generic_modes::distance (generic_modes.rs:136-189) on an array in memory without touching it: the two filters decide per row, the
+// bit planes are built over the rows that stay, the pair sweep runs on those -- no compaction of the rows x samples matrix.
+// query / n_query: nullptr / 0 = the whole table (skx_array_distance_filtered), else the rows of skx_array_distance_query_filtered
+static int distance_filtered(skx_array *a, double min_freq, int filt_ambig, const int *query, int n_query, bool is_query, skx_dist *out, int64_t *constant,
+                             uint64_t *rows_used)
+{
+    if (!a || !out) { set_error("bad arguments"); return SKX_EINVAL; }
+    skx_ctx *ctx = a->ctx;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    const int S = (int)a->names.size();
+    QueryPlan plan; const QueryPlan *qp = nullptr;
+    if (is_query) { SKX_TRY(query_plan(a, query, n_query, plan)); qp = &plan; }
+    if (constant) *constant = 0;
+    if (rows_used) *rows_used = 0;
+    if (S < 2) { if (qp) out[0] = skx_dist{}; return SKX_OK; }
+    StageTimer t(ctx, &ctx->tm.distance);
+    uint64_t kept = 0; unsigned long long n_const = 0;
+    SweepPlanes sp;
+    SKX_TRY(filtered_planes(a, min_freq, filt_ambig, qp ? qp->order.p : nullptr, sp, n_const, kept));
     if (constant) *constant = (int64_t)n_const;
     if (rows_used) *rows_used = kept;
-    return planes_distance(ctx, planes.p, S, wpr, filt_ambig, (double)n_const, 0, qp ? qp->Q() : S, out, qp);
+    const int i_hi = qp ? qp->Q() : S;
+    if (sp.split) return planes_distance_split(ctx, sp.pc.p, sp.wc, sp.nc, sp.pd.p, sp.wd, sp.nd, S, (double)n_const, 0, i_hi, out, qp);
+    return planes_distance(ctx, sp.p.p, S, sp.wpr, filt_ambig, (double)n_const, 0, i_hi, out, qp);
 }
 extern "C" int skx_array_distance_filtered(skx_array *a, double min_freq, int filt_ambig, skx_dist *out, int64_t *constant, uint64_t *rows_used)
 {
@@ -2439,6 +2465,159 @@ extern "C" int skx_array_distance_query_filtered(skx_array *a, double min_freq, 
                                                  uint64_t *rows_used)
 {
     return skx_guarded([&]() -> int { return distance_filtered(a, min_freq, filt_ambig, query, n_query, true, out, constant, rows_used); });
+}
+
+// ---- the line selection (skx_array_distance_select): the same planes as the table's, the pair sweep band by band over the pair matrix, and
+// after every band the selection kernels of skx_select.hip on its count buffer -- only the candidates' integers come back to the host, which
+// finishes them with finish_counts, i.e. with the table's own arithmetic.
+// one band's counts, launched as planes_distance / planes_distance_split launch them (cnt zeroed by the caller: one filtered launch per zeroed buffer)
+static int sweep_band(skx_ctx *ctx, const SweepPlanes &sp, int S, int filt_ambig, unsigned long long *cnt, int i_lo, int i_hi)
+{
+    hipStream_t st = ctx->stream;
+    if (!sp.split) { SKX_HIP((hipError_t)launch_pair_counts(sp.p.p, S, sp.wpr, filt_ambig, cnt, st, i_lo, i_hi)); return SKX_OK; }
+    if (sp.nc && sp.pc.p) SKX_HIP((hipError_t)launch_pair_counts(sp.pc.p, S, sp.wc, 2, cnt, st, i_lo, i_hi));
+    if (sp.nd && sp.pd.p) SKX_HIP((hipError_t)launch_pair_counts(sp.pd.p, S, sp.wd, 0, cnt, st, i_lo, i_hi));
+    return SKX_OK;
+}
+// the largest key whose distance, by finish_counts' own expression, is <= max_snps (>= 0): a floor, then a step either way against that expression
+static unsigned long long select_kmax(double max_snps, int filt_ambig)
+{
+    const double scaled = max_snps * (filt_ambig ? 1.0 : 36.0);
+    if (!(scaled < 4e18)) return 1ull << 62;                               // (no key reaches it; also +inf)
+    unsigned long long k = (unsigned long long)std::floor(scaled);
+    while (key_distance(k + 1, filt_ambig) <= max_snps) k++;
+    while (k > 0 && key_distance(k, filt_ambig) > max_snps) k--;
+    return k;
+}
+// prefiltered_constant >= 0: the array has been filtered already (skx_array_distance_select_prefiltered) -- every row is swept and this is the constant;
+// < 0: the two filters are applied here (skx_array_distance_select)
+static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, const skx_select_spec *spec, int64_t prefiltered_constant, skx_dist_pair **pairs,
+                                 uint64_t *n_pairs, int64_t *constant, uint64_t *rows_used, skx_select_info *info)
+{
+    if (!a || !spec || !pairs || !n_pairs) { set_error("distance select: bad arguments"); return SKX_EINVAL; }
+    *pairs = nullptr; *n_pairs = 0;
+    if (constant) *constant = 0;
+    if (rows_used) *rows_used = 0;
+    if (info) *info = skx_select_info{0, 0, 0, 0};
+    const int S = (int)a->names.size();
+    if (std::isnan(spec->max_snps) || std::isnan(spec->max_mismatches)) { set_error("distance select: a threshold is not a number"); return SKX_EINVAL; }
+    if (spec->max_mismatches > 1.0) { set_error("distance select: max_mismatches is a proportion, at most 1"); return SKX_EINVAL; }
+    if (spec->closest < 0) { set_error("distance select: closest must be zero (none) or more"); return SKX_EINVAL; }
+    if (spec->band_rows < 0) { set_error("distance select: band_rows must be zero (the engine's choice) or more"); return SKX_EINVAL; }
+    if (spec->max_snps < 0.0 && spec->max_mismatches < 0.0 && spec->closest == 0) {
+        set_error("distance select: none of max_snps, max_mismatches and closest is given"); return SKX_EINVAL;
+    }
+    const bool nearest = spec->closest > 0 && (int64_t)spec->closest < (int64_t)S - 1;        // K >= S - 1: every candidate is among the nearest
+    if (nearest && (uint32_t)spec->closest > SEL_MAX_K) {
+        set_error("distance select: closest %d is above the %u a sample's list holds (and below the %d that would keep every pair)", spec->closest, SEL_MAX_K, S - 1);
+        return SKX_EINVAL;
+    }
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    if (S < 2) return SKX_OK;
+    const uint64_t U = a->n_rows;
+    StageTimer t(ctx, &ctx->tm.distance);
+    // the planes: the table's (distance_filtered), or those of skx_array_distance for an array that is filtered already
+    SweepPlanes sp; uint64_t kept = 0; unsigned long long n_const = 0;
+    if (prefiltered_constant < 0) SKX_TRY(filtered_planes(a, min_freq, filt_ambig, nullptr, sp, n_const, kept));
+    else {
+        n_const = (unsigned long long)prefiltered_constant; kept = U;
+        if (!filt_ambig && U) SKX_TRY(ambiguous_split_planes(a, nullptr, nullptr, sp));
+        else {
+            sp.wpr = (U + 63) / 64;
+            SKX_TRY(sp.p.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * std::max<uint64_t>(sp.wpr, 1)));
+            if (!U) SKX_TRY(sp.p.zero(st));                                     // (otherwise every word is written by the plane kernel)
+            launch_build_planes(a->matrix.p, a->pitch, S, U, sp.p.p, sp.wpr, filt_ambig, st);
+        }
+    }
+    if (constant) *constant = (int64_t)n_const;
+    if (rows_used) *rows_used = kept;
+    // a --closest list orders by (key, partner) in one 64-bit word: the key, at most 36 per swept row, must stay below 2^32
+    if (nearest && kept >= (1ull << 32) / 36) { set_error("distance select: closest is not available above %llu rows", (1ull << 32) / 36); return SKX_EUNSUP; }
+    const SelCriteria crit{filt_ambig, (double)n_const, spec->max_snps < 0.0 ? ~0ull : select_kmax(spec->max_snps, filt_ambig), spec->max_mismatches < 0.0 ? -1.0 : spec->max_mismatches};
+    uint64_t band = (uint64_t)spec->band_rows;
+    if (!band) band = std::max<uint64_t>(64, ((1ull << 30) / ((uint64_t)S * DIST_NCOUNT * 8)) / 64 * 64);
+    band = std::min<uint64_t>(band, (uint64_t)S);
+    const uint64_t bands = ((uint64_t)S + band - 1) / band;
+    DevBuf<unsigned long long> cnt;
+    SKX_TRY(cnt.alloc(band * S * DIST_NCOUNT));
+    std::vector<SelRecord> rec;
+    unsigned long long candidates = 0;
+    if (!nearest) {
+        DevBuf<uint32_t> d_n; DevBuf<uint64_t> d_off; DevBuf<SelRecord> d_rec;
+        SKX_TRY(d_n.alloc(band)); SKX_TRY(d_off.alloc(band + 1));
+        std::vector<uint32_t> h_n(band); std::vector<uint64_t> h_off(band + 1);
+        for (uint64_t b = 0; b < bands; b++) {
+            const int lo = (int)(b * band), hi = (int)std::min<uint64_t>((uint64_t)S, (b + 1) * band), rows = hi - lo;
+            SKX_TRY(cnt.zero(st));
+            SKX_TRY(sweep_band(ctx, sp, S, filt_ambig, cnt.p, lo, hi));
+            launch_select_count(cnt.p, S, lo, hi, crit, d_n.p, st);
+            SKX_HIP(hipMemcpyAsync(h_n.data(), d_n.p, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+            SKX_HIP(hipStreamSynchronize(st));
+            h_off[0] = 0;
+            for (int r = 0; r < rows; r++) h_off[r + 1] = h_off[r] + h_n[r];
+            const uint64_t n = h_off[rows];
+            if (!n) continue;
+            if (d_rec.n < n) SKX_TRY(d_rec.alloc(n));
+            SKX_HIP(hipMemcpyAsync(d_off.p, h_off.data(), (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, st));
+            launch_select_write(cnt.p, S, lo, hi, crit, d_off.p, d_rec.p, st);
+            const size_t at = rec.size();
+            rec.resize(at + n);
+            SKX_HIP(hipMemcpyAsync(rec.data() + at, d_rec.p, n * sizeof(SelRecord), hipMemcpyDeviceToHost, st));
+            SKX_HIP(hipStreamSynchronize(st));                                  // (h_off is reused by the next band)
+        }
+        SKX_HIP(hipGetLastError());
+        candidates = rec.size();
+    } else {
+        const uint32_t K = (uint32_t)spec->closest;
+        DevBuf<SelNear> lists; DevBuf<unsigned long long> d_cand;
+        SKX_TRY(lists.alloc((uint64_t)S * K)); SKX_TRY(d_cand.alloc(1)); SKX_TRY(d_cand.zero(st));
+        SKX_HIP(hipMemsetAsync(lists.p, 0xFF, (uint64_t)S * K * sizeof(SelNear), st));          // every place unused
+        for (uint64_t b = 0; b < bands; b++) {
+            const int lo = (int)(b * band), hi = (int)std::min<uint64_t>((uint64_t)S, (b + 1) * band);
+            SKX_TRY(cnt.zero(st));
+            SKX_TRY(sweep_band(ctx, sp, S, filt_ambig, cnt.p, lo, hi));
+            launch_select_nearest(cnt.p, S, lo, hi, crit, K, lists.p, d_cand.p, st);
+        }
+        std::vector<SelNear> h_lists((uint64_t)S * K);
+        SKX_HIP(hipMemcpyAsync(h_lists.data(), lists.p, h_lists.size() * sizeof(SelNear), hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipMemcpyAsync(&candidates, d_cand.p, 8, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipStreamSynchronize(st));
+        SKX_HIP(hipGetLastError());
+        // the union of the lists as (min, max) pairs, each once, in the table's order
+        for (int s = 0; s < S; s++)
+            for (uint32_t e = 0; e < K; e++) {
+                const SelNear &x = h_lists[(uint64_t)s * K + e];
+                if (x.sort_key == ~0ull) break;                                   // (the used places come first)
+                const uint32_t partner = (uint32_t)x.sort_key;
+                rec.push_back(SelRecord{std::min((uint32_t)s, partner), std::max((uint32_t)s, partner), x.mism, x.m, x.key});
+            }
+        std::sort(rec.begin(), rec.end(), [](const SelRecord &x, const SelRecord &y) { return x.i != y.i ? x.i < y.i : x.j < y.j; });
+        rec.erase(std::unique(rec.begin(), rec.end(), [](const SelRecord &x, const SelRecord &y) { return x.i == y.i && x.j == y.j; }), rec.end());
+    }
+    skx_dist_pair *out = (skx_dist_pair *)malloc(std::max<size_t>(rec.size(), 1) * sizeof(skx_dist_pair));
+    if (!out) { set_error("out of host memory"); return SKX_ENOMEM; }
+    for (size_t n = 0; n < rec.size(); n++) {
+        out[n].i = rec[n].i; out[n].j = rec[n].j;
+        finish_counts(rec[n].mism, rec[n].m, rec[n].key, (double)n_const, filt_ambig, out[n].d);
+    }
+    *pairs = out; *n_pairs = rec.size();
+    if (info) *info = skx_select_info{bands, band, band * (uint64_t)S * DIST_NCOUNT * 8, candidates};
+    return SKX_OK;
+}
+extern "C" int skx_array_distance_select(skx_array *a, double min_freq, int filt_ambig, const skx_select_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                                         int64_t *constant, uint64_t *rows_used, skx_select_info *info)
+{
+    return skx_guarded([&]() -> int { return array_distance_select(a, min_freq, filt_ambig, spec, -1, pairs, n_pairs, constant, rows_used, info); });
+}
+extern "C" int skx_array_distance_select_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_select_spec *spec, skx_dist_pair **pairs,
+                                                     uint64_t *n_pairs, skx_select_info *info)
+{
+    return skx_guarded([&]() -> int {
+    if (constant < 0) { set_error("distance select: constant must be zero or more"); return SKX_EINVAL; }
+    return array_distance_select(a, 0.0, filt_ambig, spec, constant, pairs, n_pairs, nullptr, nullptr, info);
+    });
 }
 
 extern "C" int skx_array_distance_planes(skx_array *a, int filt_ambig, const void **planes, uint64_t *words_per_row, int *n_planes)

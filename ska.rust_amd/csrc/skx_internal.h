@@ -343,6 +343,23 @@ int planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, i
 // (counts filed as classes 0-2), planes_dirty = 8 planes of the others; either may be absent (nullptr / 0 rows)
 int planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint64_t wpr_clean, uint64_t rows_clean, const uint64_t *planes_dirty, uint64_t wpr_dirty,
                           uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp = nullptr);
+// numerators over 36 of |S1 n S2| / (|S1||S2|) per pair class [2..11] of pair_counts_kernel<false> (constexpr: host and device code read the same table)
+constexpr int pair_class_num(int q) { constexpr int t[10] = {36, 18, 12, 9, 18, 6, 12, 4, 8, 12}; return t[q]; }
+// ---- line selection (skx_select.hip; driver: distance_select in skx_api.cpp) over a band's count buffer [i_hi - i_lo][S][DIST_NCOUNT]
+// a candidate pair as the device hands it over: the integers finish_counts turns into the table's skx_dist
+struct SelRecord { uint32_t i, j; unsigned long long mism, m, key; };
+// one place of a sample's --closest list: sort_key = key << 32 | partner (all ones: unused), ascending = (distance, partner index) ascending
+struct SelNear { unsigned long long sort_key, mism, m, key; };
+// kmax: the largest key whose distance passes --max-snps (~0: no threshold); pmax: --max-mismatches (< 0: none)
+struct SelCriteria { int filt_ambig; double constant; unsigned long long kmax; double pmax; };
+constexpr uint32_t SEL_MAX_K = 1024;                                 // places of a --closest list the kernels' LDS is sized for
+// n_row[r] = candidates (j > i) of row i_lo + r; then the records at row_off[r] .. row_off[r + 1], ascending j (out holds row_off[i_hi - i_lo] of them)
+void launch_select_count(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t *n_row, hipStream_t st);
+void launch_select_write(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, const uint64_t *row_off, SelRecord *out, hipStream_t st);
+// merges the band's candidates into lists[S][K] (initialised to all ones by the caller): the rows of the band first, then the columns;
+// *n_candidates += the band's candidate pairs
+void launch_select_nearest(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t K, SelNear *lists, unsigned long long *n_candidates,
+                           hipStream_t st);
 // bit planes of the rows flagged 1 in keep (4 planes with filt, else 8): every word written; rows = how many
 // (order: launch_build_planes_keep's, device memory or nullptr)
 int planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows, const int *order = nullptr);

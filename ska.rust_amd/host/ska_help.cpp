@@ -68,7 +68,10 @@ const std::vector<Cmd> &commands()
           {"--cluster-mismatches", "<P>", "(MI355X engine) Largest mismatch proportion that links two samples (with --clusters) [default: 1.0]"},
           {"--query", "<NAMES>", "(MI355X engine) Print only the table's lines that name one of these samples (comma separated)"},
           {"--query-file", "<FILE>", "(MI355X engine) The same, sample names from a file (one per line)"},
-          {"--query-skf", "<FILE>", "(MI355X engine) Merge this .skf into <SKF_FILE> in memory and print the lines that name one of its samples"}}},
+          {"--query-skf", "<FILE>", "(MI355X engine) Merge this .skf into <SKF_FILE> in memory and print the lines that name one of its samples"},
+          {"--max-snps", "<N>", "(MI355X engine) Print only the lines whose SNP distance is at most N"},
+          {"--max-mismatches", "<P>", "(MI355X engine) Print only the lines whose mismatch proportion is at most P"},
+          {"--closest", "<K>", "(MI355X engine) Print only the lines that join a sample to one of its K closest (among the lines the two thresholds keep)"}}},
         {"merge", "Combine multiple split k-mer files", "ska merge -o <OUTPUT> [SKF_FILES]...",
          {{"[SKF_FILES]...", "", "List of input split-kmer (.skf) files"}},
          {{"-o", "<OUTPUT>", "Output prefix"}}},

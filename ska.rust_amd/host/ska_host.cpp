@@ -333,6 +333,50 @@ extern "C" int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const 
     });
 }
 
+// the header and one line per selected pair (ascending (i, j): the table's order), formatted in slices by a few threads
+static int distance_select_text(const std::vector<const char *> &names, const skx_dist_pair *p, uint64_t n, char **buf, uint64_t *len)
+{
+    Phase pt("distance.table_text");
+    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n / 4096, std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+    std::vector<std::string> part(T);
+    auto work = [&](uint64_t t) { for (uint64_t x = n * t / T; x < n * (t + 1) / T; x++) put_dist_line(part[t], names[p[x].i], names[p[x].j], p[x].d); };
+    std::vector<std::thread> th;
+    for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    std::string out = DIST_HEADER;
+    size_t total = out.size();
+    for (auto &x : part) total += x.size();
+    out.reserve(total);
+    for (auto &x : part) out += x;
+    return to_buf(out, buf, len);
+}
+extern "C" int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_select_spec *spec, char **buf, uint64_t *len)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !skf_file || !spec || !buf || !len) { skx_set_error("skh_distance_select_tsv: bad arguments"); return SKX_EINVAL; }
+    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
+    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
+    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
+    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
+    if (r != SKX_OK) return r;
+    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
+    skx_array_info_t info; skx_array_info(a, &info);
+    std::vector<const char *> names(info.n_samples);
+    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
+    skx_dist_pair *pairs = nullptr; uint64_t n = 0;
+    skx_select_info si{0, 0, 0, 0};
+    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance_select_prefiltered(a, constant, filt_ambig, spec, &pairs, &n, &si)) != SKX_OK) return r; }
+    char msg[200];
+    snprintf(msg, sizeof msg, "Selected %llu lines of %llu candidate pairs: %llu bands of %llu samples, count buffer of %llu bytes", (unsigned long long)n,
+             (unsigned long long)si.candidates, (unsigned long long)si.bands, (unsigned long long)si.band_rows, (unsigned long long)si.count_buffer_bytes);
+    skh_log(2, "ska::generic_modes", msg);
+    r = distance_select_text(names, pairs, n, buf, len);
+    skx_free(pairs);
+    return r;
+    });
+}
+
 extern "C" int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
                                    double min_freq, int filter_ambig_as_missing, int fd)
 {
@@ -799,7 +843,7 @@ struct Args {
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
-                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", nullptr};
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -915,6 +959,17 @@ struct DistExtras {
 // --query / --query-file of `ska distance`: the names of both, repeats collapsed.  0, or the exit code after the refusal was printed
 const struct { const char *flag, *arg; } QUERY_OPTS[] = {{"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
 bool has_query(const Args &a) { for (auto &q : QUERY_OPTS) if (a.has(q.flag)) return true; return false; }
+// --max-snps / --max-mismatches / --closest of `ska distance`: the lines of the table picked on the device (skh_distance_select_tsv)
+const struct { const char *flag, *arg; } SELECT_OPTS[] = {{"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"}, {"--closest", "--closest <K>"}};
+bool has_select(const Args &a) { for (auto &q : SELECT_OPTS) if (a.has(q.flag)) return true; return false; }
+skx_select_spec select_spec(const Args &a)
+{
+    skx_select_spec sp{-1.0, -1.0, 0, 0};
+    if (a.has("--max-snps")) sp.max_snps = strtod(a.get("--max-snps").c_str(), nullptr);
+    if (a.has("--max-mismatches")) sp.max_mismatches = strtod(a.get("--max-mismatches").c_str(), nullptr);
+    if (a.has("--closest")) sp.closest = (int32_t)std::min<unsigned long long>(strtoull(a.get("--closest").c_str(), nullptr, 10), INT32_MAX);
+    return sp;
+}
 int read_query_names(const Args &a, std::vector<std::string> &names)
 {
     auto add = [&](const std::string &n) { if (!n.empty() && std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n); };
@@ -1202,6 +1257,32 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (v.find_first_not_of("0123456789") != std::string::npos || v.empty()) return clap_invalid(v, "--threads <THREADS>", ("`" + v + "` isn't a valid number of cores").c_str());
         if (atoi(v.c_str()) < 1) return clap_invalid(v, "--threads <THREADS>", "Threads must be one or higher");
     }
+    if (cmd == "distance" && has_select(a)) {
+        // the selection runs on one device and never forms the table the tree, the clusters and the query cut are taken from: refused as clap
+        // refuses arguments that conflict, the earliest selection option named first
+        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--gpus", "--gpus <GPUS>"},
+                                                                {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
+        for (auto &q : SELECT_OPTS)
+            for (auto &o : others)
+                if (a.has(q.flag) && (a.has(o.first) || (multi && !strcmp(o.first, "--gpus")))) {
+                    fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", q.arg, o.second, skh_usage_line("distance"));
+                    return 2;
+                }
+        for (auto &q : SELECT_OPTS) {
+            if (!a.has(q.flag)) continue;
+            const std::string v = a.get(q.flag);
+            if (!strcmp(q.flag, "--closest")) {                                                  // usize::from_str, then the range
+                if (v.empty()) return clap_invalid(v, q.arg, "cannot parse integer from empty string");
+                if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, q.arg, "invalid digit found in string");
+                if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, q.arg, "must be one or higher");
+                continue;
+            }
+            if (!lo_float(v)) return clap_invalid(v, q.arg, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
+            const double t = strtod(v.c_str(), nullptr);
+            if (!strcmp(q.flag, "--max-snps")) { if (!(t >= 0.0)) return clap_invalid(v, q.arg, "must be zero or more"); }
+            else if (!(t >= 0.0 && t <= 1.0)) return clap_invalid(v, q.arg, "Proportion must be between 0 and 1 (inclusive)");
+        }
+    }
     if (cmd == "distance" && has_query(a)) {
         // the query is cut from one device's table, and the tree and the clusters need all of it: refused as clap refuses arguments that conflict
         const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"},
@@ -1309,7 +1390,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1406,6 +1487,11 @@ extern "C" int skh_main(int argc, char **argv)
             const std::string qskf = a.get("--query-skf");
             if (skh_distance_query_tsv(ctx, a.pos[0].c_str(), a.has("--query-skf") ? qskf.c_str() : nullptr, cn.data(), (int)cn.size(), mf, !a.has("--allow-ambiguous"), &buf, &len) != SKX_OK)
                 rcode = engine_fail();
+            else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
+        }
+        else if (has_select(a)) {
+            const skx_select_spec sp = select_spec(a);
+            if (skh_distance_select_tsv(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), &sp, &buf, &len) != SKX_OK) rcode = engine_fail();
             else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
         }
         else if (skh_distance_skf_tsv_extras(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get(), &buf, &len) != SKX_OK)

@@ -20,6 +20,7 @@ OK, EINVAL, EIO, ENODEV, ENOMEM, EEMPTY, EUNSUP, EFORMAT = range(8)
 
 KEY_DT = np.dtype([("lo", "<u8"), ("hi", "<u8")])
 DIST_DT = np.dtype([("distance", "<f8"), ("mismatch_prop", "<f8"), ("match_count", "<u8"), ("mismatch_count", "<u8")])
+PAIR_DT = np.dtype([("i", "<u4"), ("j", "<u4"), ("d", DIST_DT)])      # skx_dist_pair
 NJ_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("len_a", "<f8"), ("len_b", "<f8")])      # skx_nj_join
 
 
@@ -60,6 +61,20 @@ class DistExtras(C.Structure):
     _fields_ = [("tree", C.c_char_p), ("clusters", C.c_char_p), ("cluster_snps", C.c_double), ("cluster_mismatches", C.c_double)]
 
 
+class SelectSpec(C.Structure):
+    """skx_select_spec (include/skx.h): the criteria of `ska distance --max-snps / --max-mismatches / --closest`; a negative threshold / 0 = not given"""
+    _fields_ = [("max_snps", C.c_double), ("max_mismatches", C.c_double), ("closest", C.c_int32), ("band_rows", C.c_int32)]
+
+    @classmethod
+    def of(cls, max_snps=None, max_mismatches=None, closest=0, band_rows=0):
+        return cls(-1.0 if max_snps is None else float(max_snps), -1.0 if max_mismatches is None else float(max_mismatches), int(closest), int(band_rows))
+
+
+class SelectInfo(C.Structure):
+    """skx_select_info (include/skx.h)"""
+    _fields_ = [("bands", C.c_uint64), ("band_rows", C.c_uint64), ("count_buffer_bytes", C.c_uint64), ("candidates", C.c_uint64)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[skx {code}] {msg}")
@@ -80,7 +95,8 @@ skh_build_sharded skh_align_sharded skh_distance_sharded
 skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf skh_load_array skh_sample_name skh_main skh_merge skh_delete skh_weed skh_cov skh_cov_fit skh_align_inputs_fd skh_distance_skf_tsv skh_help skh_log
 skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo
 skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras
-skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv""".split()
+skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv
+skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv""".split()
 
 _lib = None
 
@@ -113,6 +129,9 @@ def load_library():
     lib.skx_array_distance_query.argtypes = [vp, d, i, vp, i, vp]
     lib.skx_array_distance_query_filtered.argtypes = [vp, d, i, vp, i, vp, C.POINTER(C.c_int64), C.POINTER(u64)]
     lib.skh_distance_query_tsv.argtypes = [vp, cp, cp, C.POINTER(cp), i, d, i, pp, C.POINTER(u64)]
+    lib.skx_array_distance_select.argtypes = [vp, d, i, C.POINTER(SelectSpec), pp, C.POINTER(u64), C.POINTER(C.c_int64), C.POINTER(u64), C.POINTER(SelectInfo)]
+    lib.skx_array_distance_select_prefiltered.argtypes = [vp, C.c_int64, i, C.POINTER(SelectSpec), pp, C.POINTER(u64), C.POINTER(SelectInfo)]
+    lib.skh_distance_select_tsv.argtypes = [vp, cp, d, i, C.POINTER(SelectSpec), pp, C.POINTER(u64)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -422,6 +441,13 @@ class Context:
         p, n = C.c_void_p(), C.c_uint64()
         _check(_lib.skh_distance_query_tsv(self.h, skf_file.encode(), query_skf.encode() if query_skf else None, arr, len(names), float(min_freq),
                                            int(filt_ambig), C.byref(p), C.byref(n)))
+        return _take(p, n)
+
+    def distance_select_tsv(self, skf_file, min_freq=0.0, filt_ambig=True, max_snps=None, max_mismatches=None, closest=0, band_rows=0):
+        """`ska distance <skf> --max-snps N --max-mismatches P --closest K` (skh_distance_select_tsv) -> the header and the table's lines the criteria keep"""
+        spec = SelectSpec.of(max_snps, max_mismatches, closest, band_rows)
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.skh_distance_select_tsv(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n)))
         return _take(p, n)
 
     def close(self):
@@ -972,6 +998,27 @@ class Array:
         cst, rows = C.c_int64(), C.c_uint64()
         _check(_lib.skx_array_distance_query_filtered(self.h, float(min_freq), int(filt_ambig), _np_ptr(q), len(q), _np_ptr(out), C.byref(cst), C.byref(rows)))
         return out[: len(q)], cst.value, rows.value
+
+    def distance_select(self, min_freq=0.0, filt_ambig=True, max_snps=None, max_mismatches=None, closest=0, band_rows=0):
+        """skx_array_distance_select: the pairs of `distance_filtered`'s table the criteria keep, picked on the device band by band ->
+        (pairs (PAIR_DT, ascending (i, j)), constant sites, rows used, info dict)"""
+        spec = SelectSpec.of(max_snps, max_mismatches, closest, band_rows)
+        p, n, cst, rows, info = C.c_void_p(), C.c_uint64(), C.c_int64(), C.c_uint64(), SelectInfo()
+        _check(_lib.skx_array_distance_select(self.h, float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n), C.byref(cst), C.byref(rows), C.byref(info)))
+        pairs = np.frombuffer(C.string_at(p, n.value * PAIR_DT.itemsize), PAIR_DT).copy() if n.value else np.zeros(0, PAIR_DT)
+        if p:
+            _lib.skx_free(p)
+        return pairs, cst.value, rows.value, {f: getattr(info, f) for f, _ in SelectInfo._fields_}
+
+    def distance_select_prefiltered(self, constant=0, filt_ambig=True, max_snps=None, max_mismatches=None, closest=0, band_rows=0):
+        """skx_array_distance_select_prefiltered: the pairs of `distance`'s table (every row, `constant` added) the criteria keep -> (pairs, info dict)"""
+        spec = SelectSpec.of(max_snps, max_mismatches, closest, band_rows)
+        p, n, info = C.c_void_p(), C.c_uint64(), SelectInfo()
+        _check(_lib.skx_array_distance_select_prefiltered(self.h, int(constant), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n), C.byref(info)))
+        pairs = np.frombuffer(C.string_at(p, n.value * PAIR_DT.itemsize), PAIR_DT).copy() if n.value else np.zeros(0, PAIR_DT)
+        if p:
+            _lib.skx_free(p)
+        return pairs, {f: getattr(info, f) for f, _ in SelectInfo._fields_}
 
     def distance_planes(self, filt_ambig=True):
         """device pointer to this array's bit planes [n_planes][n_samples][words_per_row] -> (ptr, words_per_row, n_planes)"""
