@@ -367,6 +367,29 @@ int  skx_dist_nj(skx_ctx *ctx, const skx_dist *d, int n_samples, skx_nj_join *jo
 /* the same on a full row-major n x n host matrix of doubles (symmetric, zero diagonal, finite; refused otherwise) */
 int  skx_matrix_nj(skx_ctx *ctx, const double *m, int n, skx_nj_join *joins);
 
+/* ---- `ska distance --no-table`: the tree and the clusters without the table.  The pair matrix is swept band by band as for
+ * skx_array_distance_select, and two consumers keep their result on the device: a union-find over the pairs that pass the cluster thresholds
+ * (a link points the higher root at the lower, so a cluster's root is its lowest sample whatever the order of the bands), and the float64
+ * matrix of the distances, which neighbour joining then runs on as it runs for skx_dist_nj.  Device memory: the band's count buffer, 8 n^2
+ * bytes for the joins, O(n) besides; host memory O(n).  The thresholds are those of skh_distance_clusters, i.e. on the values as the table
+ * prints them (skh_cluster_cutoffs). */
+typedef struct {
+    double  cluster_snps, cluster_mismatches;   /* as skh_distance_clusters takes them; used when labels != NULL */
+    int32_t band_rows;                          /* 0: the engine's choice, as skx_select_spec.band_rows */
+} skx_banded_spec;
+/* what a call did: bands swept, first samples per band, bytes of the device count buffer, pairs within the thresholds, clusters */
+typedef struct { uint64_t bands, band_rows, count_buffer_bytes, edges, clusters; } skx_banded_info;
+/* labels (n_samples, or NULL): labels[i] = the lowest sample of i's cluster, the partition skh_distance_clusters makes of the full table.
+ * joins (n_samples - 1, or NULL): the records skx_dist_nj gives on the full table's distances, bit for bit; n_samples as skx_dist_nj takes it
+ * (2 .. 65 535).  constant / rows_used as skx_array_distance_filtered reports them; info may be NULL.  SKX_EINVAL with a message that begins
+ * "distance banded:" when both outputs are NULL, a threshold is NaN or negative (with labels) or band_rows < 0.  Fewer than two samples and
+ * labels only: every sample its own cluster.  The array is left as it is; both key widths and arrays held as pieces are taken. */
+int  skx_array_distance_banded(skx_array *a, double min_freq, int filt_ambig, const skx_banded_spec *spec,
+                               uint32_t *labels, skx_nj_join *joins, int64_t *constant, uint64_t *rows_used, skx_banded_info *info);
+/* The same on an array the two filters have been applied to already, as skx_array_distance_select_prefiltered is to skx_array_distance_select */
+int  skx_array_distance_banded_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_banded_spec *spec,
+                                           uint32_t *labels, skx_nj_join *joins, skx_banded_info *info);
+
 /* wall-clock phases of the host-side path (file reading + upload, .skf codec, FASTA writer ...), accumulated per name since the
  * last reset: a JSON object {"phase": seconds, ...} in first-use order (malloc'd, skx_free).  The reference has no counterpart;
  * bench.py's end_to_end leg and SKX_DEBUG read them.  skx_phase_add lets host glue above the ABI record its own phases. */

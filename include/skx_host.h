@@ -55,6 +55,18 @@ int skh_nj_newick(const char *const *names, const skx_nj_join *joins, int n, cha
  * line per edge in table order, "}"; " and \ in a name escaped with \.  Either output pointer pair may be NULL. */
 int skh_distance_clusters(const char *const *names, const skx_dist *d, int n, double max_snps, double max_mismatches,
                           char **csv, uint64_t *csv_len, char **dot, uint64_t *dot_len);
+/* the CSV half of skh_distance_clusters from the clusters themselves: labels[i] = the lowest sample of i's cluster (labels[labels[i]] ==
+ * labels[i] <= i, refused otherwise), as skx_array_distance_banded returns them */
+int skh_clusters_csv(const char *const *names, const uint32_t *labels, int n, char **csv, uint64_t *csv_len);
+/* skh_distance_clusters' two rules as what a device compares (host only): a pair is an edge exactly when its key (the numerator of its distance:
+ * over 1 with filt_ambig, over 36 without) is <= *kmax and its mismatch proportion, as a double, is <= *pmax.  Rounding to a fixed number of
+ * decimals is monotone, so both exist; they are found by bisection against snprintf / strtod.  A max_snps no key exceeds gives *kmax = 2^62.
+ * SKX_EINVAL for a NaN or a negative threshold. */
+int skh_cluster_cutoffs(double max_snps, double max_mismatches, int filt_ambig, uint64_t *kmax, double *pmax);
+/* `ska distance <skf> --no-table --tree / --clusters`: the files of skh_distance_skf_tsv_extras' extras, byte for byte, without the table and
+ * without <prefix>.graph.dot (its edge list is the O(pairs) object this form avoids).  The same one-pass filtered load, then
+ * skx_array_distance_banded_prefiltered: host memory is O(samples).  extras must name at least one of the two. */
+int skh_distance_banded_files(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *extras);
 /* generic_modes::distance (generic_modes.rs:136-189): two-stage filter, then the long-form TSV with the
  * VariantDist Display format "{:.2}\t{:.5}\t{}\t{}" (merge_ska_array.rs:57-65) */
 int skh_distance_tsv(skx_array *a, double min_freq, int filt_ambig, char **buf, uint64_t *len);

@@ -2,6 +2,7 @@
 // .skf life-cycle operations (cov / map / .skf files: skx_api_io.cpp; sequence files onto the device: skx_build_files.cpp).
 // No CPU fallback exists: without a usable HIP device every compute entry point fails with SKX_ENODEV.
 #include "skx_internal.h"
+#include "../../include/skx_host.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -14,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <unordered_map>
 #include <thread>
 #include <cerrno>
@@ -2249,7 +2251,6 @@ static void pair_integers(const unsigned long long *c, int filt_ambig, unsigned 
         key = 36ull * c[1] - num;
     }
 }
-static inline double key_distance(unsigned long long key, int filt_ambig) { return filt_ambig ? (double)key : (double)key / 36.0; }
 static void finish_counts(unsigned long long mism, unsigned long long m, unsigned long long key, double constant, int filt_ambig, skx_dist &o)
 {
     double mismatches = (double)mism, matches = constant;
@@ -2489,8 +2490,41 @@ static unsigned long long select_kmax(double max_snps, int filt_ambig)
     while (k > 0 && key_distance(k, filt_ambig) > max_snps) k--;
     return k;
 }
-// prefiltered_constant >= 0: the array has been filtered already (skx_array_distance_select_prefiltered) -- every row is swept and this is the constant;
-// < 0: the two filters are applied here (skx_array_distance_select)
+// the planes a banded sweep runs on.  prefiltered_constant >= 0: the array has been filtered already (the *_prefiltered entry points) -- every row is
+// swept and this is the constant; < 0: the two filters are applied here.  The table's planes (distance_filtered), or those of skx_array_distance
+static int banded_planes(skx_array *a, double min_freq, int filt_ambig, int64_t prefiltered_constant, SweepPlanes &sp, unsigned long long &n_const, uint64_t &kept)
+{
+    hipStream_t st = a->ctx->stream;
+    const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
+    if (prefiltered_constant < 0) return filtered_planes(a, min_freq, filt_ambig, nullptr, sp, n_const, kept);
+    n_const = (unsigned long long)prefiltered_constant; kept = U;
+    if (!filt_ambig && U) return ambiguous_split_planes(a, nullptr, nullptr, sp);
+    sp.wpr = (U + 63) / 64;
+    SKX_TRY(sp.p.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * std::max<uint64_t>(sp.wpr, 1)));
+    if (!U) SKX_TRY(sp.p.zero(st));                                         // (otherwise every word is written by the plane kernel)
+    launch_build_planes(a->matrix.p, a->pitch, S, U, sp.p.p, sp.wpr, filt_ambig, st);
+    return SKX_OK;
+}
+// first samples of the pair matrix swept at a time: as asked, or the largest multiple of 64 whose count buffer stays within 1 GiB, at least 64
+static uint64_t banded_rows(int32_t asked, int S)
+{
+    uint64_t band = (uint64_t)asked;
+    if (!band) band = std::max<uint64_t>(64, ((1ull << 30) / ((uint64_t)S * DIST_NCOUNT * 8)) / 64 * 64);
+    return std::min<uint64_t>(band, (uint64_t)S);
+}
+// the band loop: cnt (band x S pairs) zeroed and swept for every band [lo, hi) in turn, then handed to consume(lo, hi) on the context's stream
+template <typename F>
+static int for_each_band(skx_ctx *ctx, const SweepPlanes &sp, int S, int filt_ambig, DevBuf<unsigned long long> &cnt, uint64_t band, F &&consume)
+{
+    for (uint64_t lo = 0; lo < (uint64_t)S; lo += band) {
+        const int hi = (int)std::min<uint64_t>((uint64_t)S, lo + band);
+        SKX_TRY(cnt.zero(ctx->stream));
+        SKX_TRY(sweep_band(ctx, sp, S, filt_ambig, cnt.p, (int)lo, hi));
+        SKX_TRY(consume((int)lo, hi));
+    }
+    return SKX_OK;
+}
+// prefiltered_constant: see banded_planes
 static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, const skx_select_spec *spec, int64_t prefiltered_constant, skx_dist_pair **pairs,
                                  uint64_t *n_pairs, int64_t *constant, uint64_t *rows_used, skx_select_info *info)
 {
@@ -2516,29 +2550,15 @@ static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, 
     SKX_HIP(hipSetDevice(ctx->device));
     SKX_TRY(array_materialize(a));
     if (S < 2) return SKX_OK;
-    const uint64_t U = a->n_rows;
     StageTimer t(ctx, &ctx->tm.distance);
-    // the planes: the table's (distance_filtered), or those of skx_array_distance for an array that is filtered already
     SweepPlanes sp; uint64_t kept = 0; unsigned long long n_const = 0;
-    if (prefiltered_constant < 0) SKX_TRY(filtered_planes(a, min_freq, filt_ambig, nullptr, sp, n_const, kept));
-    else {
-        n_const = (unsigned long long)prefiltered_constant; kept = U;
-        if (!filt_ambig && U) SKX_TRY(ambiguous_split_planes(a, nullptr, nullptr, sp));
-        else {
-            sp.wpr = (U + 63) / 64;
-            SKX_TRY(sp.p.alloc((filt_ambig ? 4 : 8) * (uint64_t)S * std::max<uint64_t>(sp.wpr, 1)));
-            if (!U) SKX_TRY(sp.p.zero(st));                                     // (otherwise every word is written by the plane kernel)
-            launch_build_planes(a->matrix.p, a->pitch, S, U, sp.p.p, sp.wpr, filt_ambig, st);
-        }
-    }
+    SKX_TRY(banded_planes(a, min_freq, filt_ambig, prefiltered_constant, sp, n_const, kept));
     if (constant) *constant = (int64_t)n_const;
     if (rows_used) *rows_used = kept;
     // a --closest list orders by (key, partner) in one 64-bit word: the key, at most 36 per swept row, must stay below 2^32
     if (nearest && kept >= (1ull << 32) / 36) { set_error("distance select: closest is not available above %llu rows", (1ull << 32) / 36); return SKX_EUNSUP; }
     const SelCriteria crit{filt_ambig, (double)n_const, spec->max_snps < 0.0 ? ~0ull : select_kmax(spec->max_snps, filt_ambig), spec->max_mismatches < 0.0 ? -1.0 : spec->max_mismatches};
-    uint64_t band = (uint64_t)spec->band_rows;
-    if (!band) band = std::max<uint64_t>(64, ((1ull << 30) / ((uint64_t)S * DIST_NCOUNT * 8)) / 64 * 64);
-    band = std::min<uint64_t>(band, (uint64_t)S);
+    const uint64_t band = banded_rows(spec->band_rows, S);
     const uint64_t bands = ((uint64_t)S + band - 1) / band;
     DevBuf<unsigned long long> cnt;
     SKX_TRY(cnt.alloc(band * S * DIST_NCOUNT));
@@ -2548,17 +2568,15 @@ static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, 
         DevBuf<uint32_t> d_n; DevBuf<uint64_t> d_off; DevBuf<SelRecord> d_rec;
         SKX_TRY(d_n.alloc(band)); SKX_TRY(d_off.alloc(band + 1));
         std::vector<uint32_t> h_n(band); std::vector<uint64_t> h_off(band + 1);
-        for (uint64_t b = 0; b < bands; b++) {
-            const int lo = (int)(b * band), hi = (int)std::min<uint64_t>((uint64_t)S, (b + 1) * band), rows = hi - lo;
-            SKX_TRY(cnt.zero(st));
-            SKX_TRY(sweep_band(ctx, sp, S, filt_ambig, cnt.p, lo, hi));
+        SKX_TRY(for_each_band(ctx, sp, S, filt_ambig, cnt, band, [&](int lo, int hi) -> int {
+            const int rows = hi - lo;
             launch_select_count(cnt.p, S, lo, hi, crit, d_n.p, st);
             SKX_HIP(hipMemcpyAsync(h_n.data(), d_n.p, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
             SKX_HIP(hipStreamSynchronize(st));
             h_off[0] = 0;
             for (int r = 0; r < rows; r++) h_off[r + 1] = h_off[r] + h_n[r];
             const uint64_t n = h_off[rows];
-            if (!n) continue;
+            if (!n) return SKX_OK;
             if (d_rec.n < n) SKX_TRY(d_rec.alloc(n));
             SKX_HIP(hipMemcpyAsync(d_off.p, h_off.data(), (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, st));
             launch_select_write(cnt.p, S, lo, hi, crit, d_off.p, d_rec.p, st);
@@ -2566,7 +2584,8 @@ static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, 
             rec.resize(at + n);
             SKX_HIP(hipMemcpyAsync(rec.data() + at, d_rec.p, n * sizeof(SelRecord), hipMemcpyDeviceToHost, st));
             SKX_HIP(hipStreamSynchronize(st));                                  // (h_off is reused by the next band)
-        }
+            return SKX_OK;
+        }));
         SKX_HIP(hipGetLastError());
         candidates = rec.size();
     } else {
@@ -2574,12 +2593,10 @@ static int array_distance_select(skx_array *a, double min_freq, int filt_ambig, 
         DevBuf<SelNear> lists; DevBuf<unsigned long long> d_cand;
         SKX_TRY(lists.alloc((uint64_t)S * K)); SKX_TRY(d_cand.alloc(1)); SKX_TRY(d_cand.zero(st));
         SKX_HIP(hipMemsetAsync(lists.p, 0xFF, (uint64_t)S * K * sizeof(SelNear), st));          // every place unused
-        for (uint64_t b = 0; b < bands; b++) {
-            const int lo = (int)(b * band), hi = (int)std::min<uint64_t>((uint64_t)S, (b + 1) * band);
-            SKX_TRY(cnt.zero(st));
-            SKX_TRY(sweep_band(ctx, sp, S, filt_ambig, cnt.p, lo, hi));
+        SKX_TRY(for_each_band(ctx, sp, S, filt_ambig, cnt, band, [&](int lo, int hi) -> int {
             launch_select_nearest(cnt.p, S, lo, hi, crit, K, lists.p, d_cand.p, st);
-        }
+            return SKX_OK;
+        }));
         std::vector<SelNear> h_lists((uint64_t)S * K);
         SKX_HIP(hipMemcpyAsync(h_lists.data(), lists.p, h_lists.size() * sizeof(SelNear), hipMemcpyDeviceToHost, st));
         SKX_HIP(hipMemcpyAsync(&candidates, d_cand.p, 8, hipMemcpyDeviceToHost, st));
@@ -2617,6 +2634,118 @@ extern "C" int skx_array_distance_select_prefiltered(skx_array *a, int64_t const
     return skx_guarded([&]() -> int {
     if (constant < 0) { set_error("distance select: constant must be zero or more"); return SKX_EINVAL; }
     return array_distance_select(a, 0.0, filt_ambig, spec, constant, pairs, n_pairs, nullptr, nullptr, info);
+    });
+}
+
+// ---- `ska distance --no-table` (skx_array_distance_banded): the selection's planes and band loop, and after every band the consumers of
+// skx_banded.hip on its count buffer -- the union-find of the clusters and the neighbour-joining matrix stay on the device from the first band
+// to the last, S labels and S - 1 join records come back.
+// The clusters' thresholds are on the table's PRINTED values (skh_distance_clusters: strtod of "%.2f" / "%.5f").  Rounding to a fixed number of
+// decimals is monotone, so each rule is a down-set with a largest member: kmax among the integer keys, pmax among the doubles of [0, 1].  Both
+// are found by bisection against the very expressions (key_distance, snprintf, strtod); the device then compares key <= kmax and p <= pmax.
+static bool printed_passes(const char *fmt, double v, double threshold)
+{
+    char tmp[512];
+    snprintf(tmp, sizeof tmp, fmt, v);
+    return strtod(tmp, nullptr) <= threshold;
+}
+extern "C" int skh_cluster_cutoffs(double max_snps, double max_mismatches, int filt_ambig, uint64_t *kmax, double *pmax)
+{
+    if (!kmax || !pmax) { set_error("skh_cluster_cutoffs: bad arguments"); return SKX_EINVAL; }
+    if (std::isnan(max_snps) || std::isnan(max_mismatches) || max_snps < 0.0 || max_mismatches < 0.0) {
+        set_error("skh_cluster_cutoffs: a threshold is not a number or negative"); return SKX_EINVAL;
+    }
+    // key 0 prints 0.00 and p = 0 prints 0.00000: both pass every threshold >= 0, so the bisections start from a member
+    unsigned long long k_in = 0, k_out = 1ull << 62;                         // (no key reaches 2^62: at most 36 per swept row)
+    if (printed_passes("%.2f", key_distance(k_out, filt_ambig), max_snps)) k_in = k_out;
+    else while (k_out - k_in > 1) {
+        const unsigned long long mid = k_in + (k_out - k_in) / 2;
+        (printed_passes("%.2f", key_distance(mid, filt_ambig), max_snps) ? k_in : k_out) = mid;
+    }
+    // non-negative doubles are ordered as their bit patterns
+    auto of_bits = [](uint64_t b) { double d; memcpy(&d, &b, 8); return d; };
+    uint64_t p_in = 0, p_out = 0x3FF0000000000000ull;                          // 0.0, 1.0
+    if (printed_passes("%.5f", 1.0, max_mismatches)) p_in = p_out;
+    else while (p_out - p_in > 1) {
+        const uint64_t mid = p_in + (p_out - p_in) / 2;
+        (printed_passes("%.5f", of_bits(mid), max_mismatches) ? p_in : p_out) = mid;
+    }
+    *kmax = k_in; *pmax = of_bits(p_in);
+    return SKX_OK;
+}
+// prefiltered_constant: see banded_planes
+static int array_distance_banded(skx_array *a, double min_freq, int filt_ambig, const skx_banded_spec *spec, int64_t prefiltered_constant, uint32_t *labels,
+                                 skx_nj_join *joins, int64_t *constant, uint64_t *rows_used, skx_banded_info *info)
+{
+    if (!a || !spec) { set_error("distance banded: bad arguments"); return SKX_EINVAL; }
+    if (constant) *constant = 0;
+    if (rows_used) *rows_used = 0;
+    if (info) *info = skx_banded_info{0, 0, 0, 0, 0};
+    if (!labels && !joins) { set_error("distance banded: neither the labels nor the joins are asked for"); return SKX_EINVAL; }
+    if (labels && (std::isnan(spec->cluster_snps) || std::isnan(spec->cluster_mismatches) || spec->cluster_snps < 0.0 || spec->cluster_mismatches < 0.0)) {
+        set_error("distance banded: a cluster threshold is not a number or negative"); return SKX_EINVAL;
+    }
+    if (spec->band_rows < 0) { set_error("distance banded: band_rows must be zero (the engine's choice) or more"); return SKX_EINVAL; }
+    const int S = (int)a->names.size();
+    if (joins) SKX_TRY(nj_check_n(S));
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    if (S < 2) {                                                              // (labels only: the joins need two samples)
+        for (int i = 0; i < S; i++) labels[i] = (uint32_t)i;
+        if (info) info->clusters = (uint64_t)S;
+        return SKX_OK;
+    }
+    std::optional<StageTimer> t(std::in_place, ctx, &ctx->tm.distance);
+    PhaseTimer tp("distance.pair_sweep");                                     // what the table's phase of that name covers: planes, sweep, and here the consumers
+    SweepPlanes sp; uint64_t kept = 0; unsigned long long n_const = 0;
+    SKX_TRY(banded_planes(a, min_freq, filt_ambig, prefiltered_constant, sp, n_const, kept));
+    if (constant) *constant = (int64_t)n_const;
+    if (rows_used) *rows_used = kept;
+    SelCriteria crit{filt_ambig, (double)n_const, 0, 0.0};
+    if (labels) { uint64_t kmax = 0; SKX_TRY(skh_cluster_cutoffs(spec->cluster_snps, spec->cluster_mismatches, filt_ambig, &kmax, &crit.pmax)); crit.kmax = kmax; }
+    const uint64_t band = banded_rows(spec->band_rows, S);
+    const uint64_t bands = ((uint64_t)S + band - 1) / band, cnt_bytes = band * (uint64_t)S * DIST_NCOUNT * 8, pitch = nj_pitch((uint64_t)S);
+    // everything is allocated before the first band: a matrix that does not fit is refused here, with its message
+    if (joins) SKX_TRY(nj_fits(ctx, (uint64_t)S, cnt_bytes));
+    DevBuf<unsigned long long> cnt, d_n; DevBuf<double> D; DevBuf<uint32_t> parent, d_label;
+    SKX_TRY(cnt.alloc(band * S * DIST_NCOUNT));
+    if (joins) { SKX_TRY(D.alloc(pitch * S)); SKX_TRY(D.zero(st)); }         // (the diagonal and the pad column of an odd S stay zero)
+    unsigned long long h_n[2] = {0, 0};                                       // edges, roots
+    const bool per_edge = knob("union_per_edge") != 0;                        // (the plain union, for the comparison)
+    if (labels) {
+        SKX_TRY(parent.alloc((uint64_t)S)); SKX_TRY(d_label.alloc((uint64_t)S)); SKX_TRY(d_n.alloc(2)); SKX_TRY(d_n.zero(st));
+        launch_cluster_init(parent.p, S, st);
+    }
+    SKX_TRY(for_each_band(ctx, sp, S, filt_ambig, cnt, band, [&](int lo, int hi) -> int {
+        if (labels) launch_cluster_union(cnt.p, S, lo, hi, crit, parent.p, d_n.p, per_edge, st);
+        if (joins) launch_dist_fill(cnt.p, S, lo, hi, filt_ambig, D.p, pitch, st);
+        return SKX_OK;
+    }));
+    if (labels) {
+        launch_cluster_labels(parent.p, S, d_label.p, d_n.p + 1, st);
+        SKX_HIP(hipMemcpyAsync(labels, d_label.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipMemcpyAsync(h_n, d_n.p, sizeof h_n, hipMemcpyDeviceToHost, st));
+    }
+    SKX_HIP(hipGetLastError());
+    SKX_HIP(hipStreamSynchronize(st));
+    tp.stop(); t.reset();
+    cnt.release(); sp = SweepPlanes();                                        // (the joins need the matrix only)
+    if (joins) { PhaseTimer tn("distance.nj"); SKX_TRY(nj_run_device(ctx, D, pitch, (uint32_t)S, joins)); }
+    if (info) *info = skx_banded_info{bands, band, cnt_bytes, h_n[0], h_n[1]};
+    return SKX_OK;
+}
+extern "C" int skx_array_distance_banded(skx_array *a, double min_freq, int filt_ambig, const skx_banded_spec *spec, uint32_t *labels, skx_nj_join *joins,
+                                         int64_t *constant, uint64_t *rows_used, skx_banded_info *info)
+{
+    return skx_guarded([&]() -> int { return array_distance_banded(a, min_freq, filt_ambig, spec, -1, labels, joins, constant, rows_used, info); });
+}
+extern "C" int skx_array_distance_banded_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_banded_spec *spec, uint32_t *labels,
+                                                     skx_nj_join *joins, skx_banded_info *info)
+{
+    return skx_guarded([&]() -> int {
+    if (constant < 0) { set_error("distance banded: constant must be zero or more"); return SKX_EINVAL; }
+    return array_distance_banded(a, 0.0, filt_ambig, spec, constant, labels, joins, nullptr, nullptr, info);
     });
 }
 

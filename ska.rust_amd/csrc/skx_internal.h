@@ -352,6 +352,28 @@ struct SelRecord { uint32_t i, j; unsigned long long mism, m, key; };
 struct SelNear { unsigned long long sort_key, mism, m, key; };
 // kmax: the largest key whose distance passes --max-snps (~0: no threshold); pmax: --max-mismatches (< 0: none)
 struct SelCriteria { int filt_ambig; double constant; unsigned long long kmax; double pmax; };
+// the distance of a pair from its key, the exact numerator (over 1 with filt_ambig, over 36 without): one expression for the table (finish_counts),
+// the thresholds' derivation and the matrix the banded form fills on the device
+__host__ __device__ inline double key_distance(unsigned long long key, int filt_ambig) { return filt_ambig ? (double)key : (double)key / 36.0; }
+// counts of one pair -> its integers (the first half of finish_pair, skx_api.cpp); true when the pair passes the thresholds.  The mismatch
+// threshold is finish_pair's expression in float64: a file that calls this is compiled with -ffp-contract=off (Makefile)
+struct SelPair { unsigned long long mism, m, key; };
+__device__ inline bool sel_pair(const unsigned long long *c, int filt_ambig, double constant, unsigned long long kmax, double pmax, SelPair &o)
+{
+    o.mism = c[0];
+    if (filt_ambig) { o.m = c[2]; o.key = c[2] - c[3]; }
+    else {
+        unsigned long long m = 0, num = 0;
+#pragma unroll
+        for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)pair_class_num(q); }
+        o.m = m; o.key = 36ull * c[1] - num;
+    }
+    if (o.key > kmax) return false;
+    if (pmax < 0.0) return true;
+    const double mismatches = (double)o.mism, matches = constant + (double)o.m;
+    const double p = (matches + mismatches) == 0.0 ? 0.0 : mismatches / (matches + mismatches);
+    return p <= pmax;
+}
 constexpr uint32_t SEL_MAX_K = 1024;                                 // places of a --closest list the kernels' LDS is sized for
 // n_row[r] = candidates (j > i) of row i_lo + r; then the records at row_off[r] .. row_off[r + 1], ascending j (out holds row_off[i_hi - i_lo] of them)
 void launch_select_count(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t *n_row, hipStream_t st);
@@ -360,6 +382,23 @@ void launch_select_write(const unsigned long long *cnt, int S, int i_lo, int i_h
 // *n_candidates += the band's candidate pairs
 void launch_select_nearest(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t K, SelNear *lists, unsigned long long *n_candidates,
                            hipStream_t st);
+// ---- the banded consumers that keep their result on the device (skx_banded.hip; driver: array_distance_banded in skx_api.cpp), over the same buffer
+// parent[S] = 0 .. S-1: every sample its own tree
+void launch_cluster_init(uint32_t *parent, int S, hipStream_t st);
+// links the two trees of every pair (i in [i_lo, i_hi), j > i) that passes c, the higher root under the lower (32-bit atomicMin on parent[]): no
+// cycle, a component's root is its lowest sample, and the final labels do not depend on the order of lanes, workgroups or bands
+// per_edge: one link per passing pair instead of one per distinct root of a wave's part of the row (the form kept for comparison)
+void launch_cluster_union(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t *parent, unsigned long long *n_edges, bool per_edge,
+                          hipStream_t st);
+// after the last band: label[i] = the root of i; *n_roots (zeroed by the caller) = how many samples are their own root
+void launch_cluster_labels(const uint32_t *parent, int S, uint32_t *label, unsigned long long *n_roots, hipStream_t st);
+// D[i][j] = D[j][i] = the distance of the pair's key (finish_counts' expression) for i in [i_lo, i_hi), j > i, in the pitched matrix nj_run takes
+void launch_dist_fill(const unsigned long long *cnt, int S, int i_lo, int i_hi, int filt_ambig, double *D, uint64_t pitch, hipStream_t st);
+// neighbour joining (skx_nj.hip) on a matrix that is on the device already: pitch = nj_pitch(S) doubles a row, zero diagonal and pad, symmetric
+uint64_t nj_pitch(uint64_t S);
+int nj_check_n(int n);
+int nj_fits(skx_ctx *ctx, uint64_t S, uint64_t extra);
+int nj_run_device(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, skx_nj_join *joins);
 // bit planes of the rows flagged 1 in keep (4 planes with filt, else 8): every word written; rows = how many
 // (order: launch_build_planes_keep's, device memory or nullptr)
 int planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows, const int *order = nullptr);

@@ -173,6 +173,8 @@ __global__ void nj_last_kernel(const double *D, uint64_t pitch, const uint32_t *
 
 inline unsigned nj_grid(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
+}  // namespace
+
 // the matrix of S nodes on the device, pitch doubles per row (even, so that every row starts on 16 bytes)
 uint64_t nj_pitch(uint64_t S) { return (S + 1) & ~(uint64_t)1; }
 
@@ -192,7 +194,7 @@ int nj_fits(skx_ctx *ctx, uint64_t S, uint64_t extra)
 }
 
 // D: the S x S matrix on the device (destroyed by the run); joins: S - 1 records on the host
-int nj_run(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, skx_nj_join *joins)
+static int nj_run(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, skx_nj_join *joins)
 {
     hipStream_t st = ctx->stream;
     PhaseTimer ts("nj.steps");
@@ -222,8 +224,9 @@ int nj_check_n(int n)
     if (n > 65535) { set_error("neighbour joining: %d samples; at most 65535", n); return SKX_EUNSUP; }
     return SKX_OK;
 }
+// the entry of the banded form (skx_api.cpp), which fills the matrix on the device itself
+int nj_run_device(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, skx_nj_join *joins) { return nj_run(ctx, D, pitch, S, joins); }
 
-}  // namespace
 }  // namespace skx
 
 using namespace skx;

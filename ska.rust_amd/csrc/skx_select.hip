@@ -25,25 +25,7 @@ namespace {
 constexpr int SEL_NT = 256;                       // threads of every workgroup here
 constexpr unsigned long long SEL_NONE = ~0ull;    // an unused place of a list
 
-struct SelPair { unsigned long long mism, m, key; };
-
-// counts of one pair -> its integers; true when the pair passes the thresholds (kmax: largest key allowed; pmax < 0: none)
-__device__ inline bool sel_pair(const unsigned long long *c, int filt_ambig, double constant, unsigned long long kmax, double pmax, SelPair &o)
-{
-    o.mism = c[0];
-    if (filt_ambig) { o.m = c[2]; o.key = c[2] - c[3]; }
-    else {
-        unsigned long long m = 0, num = 0;
-#pragma unroll
-        for (int q = 0; q < 10; q++) { m += c[2 + q]; num += c[2 + q] * (unsigned long long)pair_class_num(q); }
-        o.m = m; o.key = 36ull * c[1] - num;
-    }
-    if (o.key > kmax) return false;
-    if (pmax < 0.0) return true;
-    const double mismatches = (double)o.mism, matches = constant + (double)o.m;
-    const double p = (matches + mismatches) == 0.0 ? 0.0 : mismatches / (matches + mismatches);
-    return p <= pmax;
-}
+// (a pair's integers and the threshold test: sel_pair of skx_internal.h, shared with skx_banded.hip)
 
 __global__ __launch_bounds__(SEL_NT) void select_count_kernel(const unsigned long long *cnt, int S, int i_lo, int i_hi, int filt_ambig, double constant,
                                                               unsigned long long kmax, double pmax, uint32_t *n_row)

@@ -377,6 +377,49 @@ extern "C" int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, doubl
     });
 }
 
+// `ska distance --no-table`: the extras' files from the banded sweep (x names at least one).  What reaches the host is S labels and S - 1 joins
+extern "C" int skh_distance_banded_files(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *x)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !skf_file || !x || (!x->tree && !x->clusters)) { skx_set_error("skh_distance_banded_files: bad arguments"); return SKX_EINVAL; }
+    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
+    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
+    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
+    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
+    if (r != SKX_OK) return r;
+    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
+    skx_array_info_t info; skx_array_info(a, &info);
+    const int S = (int)info.n_samples;
+    std::vector<const char *> names(info.n_samples);
+    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
+    std::vector<uint32_t> labels((size_t)std::max(S, 1)); std::vector<skx_nj_join> joins((size_t)std::max(S - 1, 1));
+    const skx_banded_spec spec{x->cluster_snps, x->cluster_mismatches, 0};
+    skx_banded_info bi{0, 0, 0, 0, 0};
+    // (the phases distance.pair_sweep and distance.nj are recorded by the call itself: both happen inside it)
+    if ((r = skx_array_distance_banded_prefiltered(a, constant, filt_ambig, &spec, x->clusters ? labels.data() : nullptr, x->tree ? joins.data() : nullptr, &bi)) != SKX_OK) return r;
+    char msg[200];
+    snprintf(msg, sizeof msg, "No table: %llu bands of %llu samples, count buffer of %llu bytes; %llu pairs within the cluster thresholds, %llu clusters",
+             (unsigned long long)bi.bands, (unsigned long long)bi.band_rows, (unsigned long long)bi.count_buffer_bytes, (unsigned long long)bi.edges, (unsigned long long)bi.clusters);
+    skh_log(2, "ska::generic_modes", msg);
+    if (x->tree) {
+        Phase pt("distance.tree_text");
+        char *buf = nullptr; uint64_t len = 0;
+        if ((r = skh_nj_newick(names.data(), joins.data(), S, &buf, &len)) != SKX_OK) return r;
+        r = write_text_file(x->tree, buf, len);
+        skx_free(buf);
+        if (r != SKX_OK) return r;
+    }
+    if (x->clusters) {
+        Phase pc("distance.clusters");
+        char *csv = nullptr; uint64_t nc = 0;
+        if ((r = skh_clusters_csv(names.data(), labels.data(), S, &csv, &nc)) != SKX_OK) return r;
+        r = write_text_file(std::string(x->clusters) + ".clusters.csv", csv, nc);
+        skx_free(csv);
+    }
+    return r;
+    });
+}
+
 extern "C" int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
                                    double min_freq, int filter_ambig_as_missing, int fd)
 {
@@ -1257,6 +1300,19 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (v.find_first_not_of("0123456789") != std::string::npos || v.empty()) return clap_invalid(v, "--threads <THREADS>", ("`" + v + "` isn't a valid number of cores").c_str());
         if (atoi(v.c_str()) < 1) return clap_invalid(v, "--threads <THREADS>", "Threads must be one or higher");
     }
+    if (cmd == "distance" && a.has("--no-table")) {
+        // the tree and the clusters from the banded sweep, on one device, and nothing else: refused as clap refuses arguments that conflict and
+        // a required group that is missing
+        const std::pair<const char *, const char *> others[] = {{"-o", "-o <OUTPUT>"}, {"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"},
+                                                                {"--closest", "--closest <K>"}, {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"},
+                                                                {"--query-skf", "--query-skf <FILE>"}, {"--gpus", "--gpus <GPUS>"}};
+        for (auto &o : others)
+            if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
+                fprintf(stderr, "error: the argument '--no-table' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
+                return 2;
+            }
+        if (!a.has("--tree") && !a.has("--clusters")) return clap_missing("distance", "<--tree <FILE>|--clusters <PREFIX>>");
+    }
     if (cmd == "distance" && has_select(a)) {
         // the selection runs on one device and never forms the table the tree, the clusters and the query cut are taken from: refused as clap
         // refuses arguments that conflict, the earliest selection option named first
@@ -1390,7 +1446,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1488,6 +1544,9 @@ extern "C" int skh_main(int argc, char **argv)
             if (skh_distance_query_tsv(ctx, a.pos[0].c_str(), a.has("--query-skf") ? qskf.c_str() : nullptr, cn.data(), (int)cn.size(), mf, !a.has("--allow-ambiguous"), &buf, &len) != SKX_OK)
                 rcode = engine_fail();
             else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
+        }
+        else if (a.has("--no-table")) {
+            if (skh_distance_banded_files(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get()) != SKX_OK) rcode = engine_fail();
         }
         else if (has_select(a)) {
             const skx_select_spec sp = select_spec(a);

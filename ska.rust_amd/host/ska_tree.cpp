@@ -125,6 +125,30 @@ extern "C" int skh_nj_newick(const char *const *names, const skx_nj_join *joins,
     return text_out(o, buf, len);
 }
 
+extern "C" int skh_clusters_csv(const char *const *names, const uint32_t *labels, int n_, char **csv, uint64_t *csv_len)
+{
+    if (!names || !labels || n_ < 1 || !csv || !csv_len) { skx_set_error("skh_clusters_csv: bad arguments"); return SKX_EINVAL; }
+    const uint32_t n = (uint32_t)n_;
+    for (uint32_t i = 0; i < n; i++)
+        if (labels[i] > i || labels[labels[i]] != labels[i]) { skx_set_error("skh_clusters_csv: label %u of sample %u is not the lowest sample of a cluster", labels[i], i); return SKX_EINVAL; }
+    // clusters by size descending, ties by their lowest sample
+    std::vector<uint32_t> size(n, 0), roots;
+    for (uint32_t i = 0; i < n; i++) size[labels[i]]++;
+    for (uint32_t i = 0; i < n; i++) if (labels[i] == i) roots.push_back(i);
+    std::stable_sort(roots.begin(), roots.end(), [&](uint32_t x, uint32_t y) { return size[x] > size[y]; });
+    std::vector<std::vector<uint32_t>> members(n);
+    for (uint32_t i = 0; i < n; i++) members[labels[i]].push_back(i);
+    std::string c = "id,Cluster__autocolour\n";
+    for (size_t k = 0; k < roots.size(); k++)
+        for (uint32_t i : members[roots[k]]) {
+            const std::string s = names[i];
+            if (s.find_first_of(",\"\n\r") != std::string::npos) { c += '"'; for (char ch : s) { if (ch == '"') c += '"'; c += ch; } c += '"'; }
+            else c += s;
+            c += "," + std::to_string(k + 1) + "\n";
+        }
+    return text_out(c, csv, csv_len);
+}
+
 extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d, int n_, double max_snps, double max_mismatches,
                                      char **csv, uint64_t *csv_len, char **dot, uint64_t *dot_len)
 {
@@ -149,23 +173,9 @@ extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d
             if (a != b) up[std::max(a, b)] = std::min(a, b);       // the root of a cluster is its lowest sample
         }
     g += "}\n";
-    // clusters by size descending, ties by their lowest sample
-    std::vector<uint32_t> size(n, 0), roots, number(n, 0);
-    for (uint32_t i = 0; i < n; i++) size[find(i)]++;
-    for (uint32_t i = 0; i < n; i++) if (find(i) == i) roots.push_back(i);
-    std::stable_sort(roots.begin(), roots.end(), [&](uint32_t x, uint32_t y) { return size[x] > size[y]; });
-    std::vector<std::vector<uint32_t>> members(n);
-    for (uint32_t i = 0; i < n; i++) members[find(i)].push_back(i);
-    std::string c = "id,Cluster__autocolour\n";
-    for (size_t k = 0; k < roots.size(); k++)
-        for (uint32_t i : members[roots[k]]) {
-            const std::string s = names[i];
-            if (s.find_first_of(",\"\n\r") != std::string::npos) { c += '"'; for (char ch : s) { if (ch == '"') c += '"'; c += ch; } c += '"'; }
-            else c += s;
-            c += "," + std::to_string(k + 1) + "\n";
-        }
+    for (uint32_t i = 0; i < n; i++) up[i] = find(i);
     int r = SKX_OK;
-    if (csv) r = text_out(c, csv, csv_len);
+    if (csv) r = skh_clusters_csv(names, up.data(), n_, csv, csv_len);
     if (r == SKX_OK && dot) r = text_out(g, dot, dot_len);
     return r;
 }

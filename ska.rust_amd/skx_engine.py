@@ -75,6 +75,16 @@ class SelectInfo(C.Structure):
     _fields_ = [("bands", C.c_uint64), ("band_rows", C.c_uint64), ("count_buffer_bytes", C.c_uint64), ("candidates", C.c_uint64)]
 
 
+class BandedSpec(C.Structure):
+    """skx_banded_spec (include/skx.h): the cluster thresholds of `ska distance --no-table --clusters` and the band of its sweep"""
+    _fields_ = [("cluster_snps", C.c_double), ("cluster_mismatches", C.c_double), ("band_rows", C.c_int32)]
+
+
+class BandedInfo(C.Structure):
+    """skx_banded_info (include/skx.h)"""
+    _fields_ = [("bands", C.c_uint64), ("band_rows", C.c_uint64), ("count_buffer_bytes", C.c_uint64), ("edges", C.c_uint64), ("clusters", C.c_uint64)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[skx {code}] {msg}")
@@ -96,7 +106,8 @@ skh_apply_filters skh_align skh_align_fd skh_distance_tsv skh_nk skh_save_skf sk
 skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_graph_free skh_lo
 skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras
 skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv
-skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv""".split()
+skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv
+skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files""".split()
 
 _lib = None
 
@@ -132,6 +143,11 @@ def load_library():
     lib.skx_array_distance_select.argtypes = [vp, d, i, C.POINTER(SelectSpec), pp, C.POINTER(u64), C.POINTER(C.c_int64), C.POINTER(u64), C.POINTER(SelectInfo)]
     lib.skx_array_distance_select_prefiltered.argtypes = [vp, C.c_int64, i, C.POINTER(SelectSpec), pp, C.POINTER(u64), C.POINTER(SelectInfo)]
     lib.skh_distance_select_tsv.argtypes = [vp, cp, d, i, C.POINTER(SelectSpec), pp, C.POINTER(u64)]
+    lib.skx_array_distance_banded.argtypes = [vp, d, i, C.POINTER(BandedSpec), vp, vp, C.POINTER(C.c_int64), C.POINTER(u64), C.POINTER(BandedInfo)]
+    lib.skx_array_distance_banded_prefiltered.argtypes = [vp, C.c_int64, i, C.POINTER(BandedSpec), vp, vp, C.POINTER(BandedInfo)]
+    lib.skh_clusters_csv.argtypes = [C.POINTER(cp), vp, i, pp, C.POINTER(u64)]
+    lib.skh_cluster_cutoffs.argtypes = [d, d, i, C.POINTER(u64), C.POINTER(d)]
+    lib.skh_distance_banded_files.argtypes = [vp, cp, d, i, C.POINTER(DistExtras)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -450,6 +466,11 @@ class Context:
         _check(_lib.skh_distance_select_tsv(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n)))
         return _take(p, n)
 
+    def distance_banded_files(self, skf_file, min_freq=0.0, filt_ambig=True, tree=None, clusters=None, cluster_snps=10.0, cluster_mismatches=1.0):
+        """`ska distance <skf> --no-table [--tree FILE] [--clusters PREFIX ...]` (skh_distance_banded_files): the files, no table"""
+        x = DistExtras(tree.encode() if tree else None, clusters.encode() if clusters else None, cluster_snps, cluster_mismatches)
+        _check(_lib.skh_distance_banded_files(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(x)))
+
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.skx_ctx_destroy(self.h)
@@ -493,6 +514,27 @@ def distance_clusters(names, dist, max_snps=10.0, max_mismatches=1.0):
     pc, nc, pd, nd = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
     _check(_lib.skh_distance_clusters(arr, _np_ptr(d) if d.size else None, n, max_snps, max_mismatches, C.byref(pc), C.byref(nc), C.byref(pd), C.byref(nd)))
     return _take(pc, nc).decode(), _take(pd, nd).decode()
+
+
+def clusters_csv(names, labels):
+    """skh_clusters_csv: clusters.csv text of labels[i] = the lowest sample of i's cluster (host only)"""
+    load_library()
+    n = len(names)
+    lab = np.ascontiguousarray(labels, np.uint32)
+    if lab.size != n:
+        raise ValueError("one label per name is required")
+    arr = (C.c_char_p * n)(*[x.encode() for x in names])
+    p, ln = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_clusters_csv(arr, _np_ptr(lab), n, C.byref(p), C.byref(ln)))
+    return _take(p, ln).decode()
+
+
+def cluster_cutoffs(max_snps, max_mismatches, filt_ambig=True):
+    """skh_cluster_cutoffs: the printed-value rules of skh_distance_clusters as (largest key, largest float64 proportion) that pass (host only)"""
+    load_library()
+    kmax, pmax = C.c_uint64(), C.c_double()
+    _check(_lib.skh_cluster_cutoffs(float(max_snps), float(max_mismatches), int(filt_ambig), C.byref(kmax), C.byref(pmax)))
+    return kmax.value, pmax.value
 
 
 def record_stream(records):
@@ -1019,6 +1061,31 @@ class Array:
         if p:
             _lib.skx_free(p)
         return pairs, {f: getattr(info, f) for f, _ in SelectInfo._fields_}
+
+    def _banded_outputs(self, labels, tree):
+        s = self.nsamples
+        lab = np.zeros(max(s, 1), np.uint32) if labels else None
+        joins = np.zeros(max(s - 1, 1), NJ_DT) if tree else None
+        return s, lab, joins
+
+    def distance_banded(self, min_freq=0.0, filt_ambig=True, labels=True, tree=False, cluster_snps=10.0, cluster_mismatches=1.0, band_rows=0):
+        """skx_array_distance_banded: the clusters and / or the neighbour-joining joins of `distance_filtered`'s table from the banded sweep,
+        the table never formed -> (labels (uint32: the lowest sample of each sample's cluster) or None, joins (NJ_DT) or None, constant sites,
+        rows used, info dict)"""
+        s, lab, joins = self._banded_outputs(labels, tree)
+        spec, cst, rows, info = BandedSpec(float(cluster_snps), float(cluster_mismatches), int(band_rows)), C.c_int64(), C.c_uint64(), BandedInfo()
+        _check(_lib.skx_array_distance_banded(self.h, float(min_freq), int(filt_ambig), C.byref(spec), _np_ptr(lab) if labels else None,
+                                              _np_ptr(joins) if tree else None, C.byref(cst), C.byref(rows), C.byref(info)))
+        return (lab[:s] if labels else None, joins[: max(s - 1, 0)] if tree else None, cst.value, rows.value,
+                {f: getattr(info, f) for f, _ in BandedInfo._fields_})
+
+    def distance_banded_prefiltered(self, constant=0, filt_ambig=True, labels=True, tree=False, cluster_snps=10.0, cluster_mismatches=1.0, band_rows=0):
+        """skx_array_distance_banded_prefiltered: the same of `distance`'s table (every row, `constant` added) -> (labels, joins, info dict)"""
+        s, lab, joins = self._banded_outputs(labels, tree)
+        spec, info = BandedSpec(float(cluster_snps), float(cluster_mismatches), int(band_rows)), BandedInfo()
+        _check(_lib.skx_array_distance_banded_prefiltered(self.h, int(constant), int(filt_ambig), C.byref(spec), _np_ptr(lab) if labels else None,
+                                                          _np_ptr(joins) if tree else None, C.byref(info)))
+        return lab[:s] if labels else None, joins[: max(s - 1, 0)] if tree else None, {f: getattr(info, f) for f, _ in BandedInfo._fields_}
 
     def distance_planes(self, filt_ambig=True):
         """device pointer to this array's bit planes [n_planes][n_samples][words_per_row] -> (ptr, words_per_row, n_planes)"""
