@@ -304,6 +304,21 @@ int  skx_array_merge(skx_ctx *ctx, skx_array *const *arrays, int n_arrays, skx_a
 /* MergeSkaArray::delete_samples (merge_ska_array.rs:231-271) incl. update_counts(false): rows no remaining sample has are
  * dropped.  SKX_EINVAL "Invalid number of samples to remove" / "Could not find sample(s): {..}" where it panics. */
 int  skx_array_delete_samples(skx_array *a, const char *const *names, int n_names);
+/* `ska align --groups / --samples`: the alignment of a subset of the samples without the .skf in between -- MergeSkaArray::delete_samples of
+ * everybody else (merge_ska_array.rs:231-271, with its update_counts(false), :139-163: rows no sample of the subset has are dropped and the
+ * counts become the cells present) followed by generic_modes::apply_filters (generic_modes.rs:112-131: threshold ceil(n_samples * min_freq)
+ * over the subset, update_kmers = false) = MergeSkaArray::filter (merge_ska_array.rs:289-402), decided per row in one pass over the subset's
+ * cells.  samples = n_samples distinct indices into `a` in any order; *out = a new array on a's context holding the kept rows in a's row
+ * order and the subset's samples in ascending index (as the delete leaves them), mask_ambig applied.  Like the result of
+ * skx_array_load_filtered it has no split k-mers: save / merge / weed / map on it fail with SKX_EINVAL; write_fasta / fasta / info / name work.
+ * info (may be NULL): rows_present = rows left by the delete (what `ska nk` would print), removed = the filter's return value, silent = rows
+ * update_counts(true) drops uncounted (filter_ambig_as_missing: no unambiguous cell), sites = rows of *out.  out may be NULL: the counts alone.
+ * `a` keeps its content (an array held as pieces or lazily is materialised first); both key widths are taken; a subset of all samples is
+ * allowed.  The n_samples x rows matrix of the unfiltered subset is never allocated.  SKX_EINVAL with a message that begins "subset:" for
+ * n_samples < 1, an index out of range, a repeated index, two_stage != 0, min_freq outside [0, 1] or NaN. */
+typedef struct { uint64_t rows_present, removed, silent, sites; } skx_subset_info;
+int  skx_array_subset_filtered(skx_array *a, const int *samples, int n_samples, const skx_filter_spec *f,
+                               skx_array **out, skx_subset_info *info);
 /* MergeSkaArray::weed (merge_ska_array.rs:452-487): rows whose split k-mer is (reverse: is not) in `weed` are removed;
  * `weed` = the split k-mers of the weed FASTA (RefSka::new + kmer_iter, ska_ref.rs:189-262,541), i.e. the key set of its
  * dictionary: skx_dictset_build_files (1 sample) -> skx_keyset_union. */

@@ -23,6 +23,27 @@ int skh_align_fd(skx_array *a, int filter_type, int mask_ambig, int ignore_const
  * one-pass load + filter (skx_array_load_filtered), several sequence files through build_and_merge with the CLI defaults */
 int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
                         double min_freq, int filter_ambig_as_missing, int fd);
+/* `ska align <inputs> --groups FILE -o PREFIX [--min-group-size N]` (no counterpart in the reference, whose users run `ska delete` of everybody
+ * else, generic_modes.rs:192-210, and `ska align`, :22-50, once per group): the inputs are loaded once (skh_load_array: one .skf, or sequence
+ * files built with the CLI defaults); every group of at least min_group_size (>= 1) samples goes through skx_array_subset_filtered and
+ * skx_array_write_fasta into <PREFIX>.<label>.aln -- the bytes `ska delete` + `ska align` with the same options write.  Names are matched to
+ * samples as skx_array_delete_samples matches them (first match wins; "Could not find sample(s): {..}"); samples the file does not list
+ * belong to no group.  <PREFIX>.groups.tsv: header "Group\tSamples\tSplit k-mers\tRemoved\tSites\tFile", a line per group in file order
+ * (Split k-mers = rows left by the delete, what `ska nk` prints), "-" in the last three columns of a group that was too small.
+ * Phases: align.groups_load / groups_verdicts / groups_rows / groups_write. */
+int skh_align_groups(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
+                     double min_freq, int filter_ambig_as_missing, const char *groups_file, int min_group_size, const char *out_prefix);
+/* `ska align <inputs> --samples NAMES | --samples-file FILE`: the one subset `names` (repeats collapse), its alignment streamed to fd */
+int skh_align_samples_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
+                         double min_freq, int filter_ambig_as_missing, const char *const *names, int n_names, int fd);
+/* the groups file of skh_align_groups (host only, no device): two columns, sample name and group label, separated by a tab (when the line
+ * holds one outside quotes) or else by a comma; <prefix>.clusters.csv as skh_clusters_csv writes it is taken as it is -- its header line
+ * "id,Cluster__autocolour" is skipped when it comes first, names in double quotes with inner quotes doubled may hold , " and line breaks.
+ * Blank lines and a trailing carriage return are ignored.  *buf (malloc'd) = the pairs as "name\0label\0", group by group in the order
+ * the labels first appear and in file order within a group; *n_pairs (may be NULL) = how many.  SKX_EINVAL with "groups file <path>: line
+ * <n>: ..." for a line without exactly two fields, an empty name or label, a label holding '/' or a NUL or equal to "." or "..", a sample
+ * name listed twice; SKX_EIO when the file cannot be read. */
+int skh_read_groups(const char *path, char **buf, uint64_t *len, uint64_t *n_pairs);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

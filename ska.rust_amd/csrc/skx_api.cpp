@@ -2075,6 +2075,79 @@ extern "C" int skx_array_delete_samples(skx_array *a, const char *const *del_nam
     });
 }
 
+// delete_samples(everybody else) + apply_filters for a sample list, as a new array: one pass over the list's cells decides every row
+// (launch_subset_verdicts), the scan places the kept ones and the compaction reads them through the list -- the n x pitch sub-matrix of
+// the unfiltered rows is never made.  Device memory beside `a`: U bytes of keep, 8 (U + 1) of pos, the kept matrix.
+extern "C" int skx_array_subset_filtered(skx_array *a, const int *samples, int n_samples, const skx_filter_spec *f, skx_array **out, skx_subset_info *info)
+{
+    return skx_guarded([&]() -> int {
+    if (out) *out = nullptr;
+    if (!a || !f || (n_samples > 0 && !samples)) { set_error("subset: bad arguments"); return SKX_EINVAL; }
+    const size_t S = a->names.size();
+    if (n_samples < 1) { set_error("subset: at least one sample is required"); return SKX_EINVAL; }
+    if (f->two_stage != 0) { set_error("subset: the two-stage filter of `ska distance` does not apply to a subset"); return SKX_EINVAL; }
+    if (!(f->min_freq >= 0.0 && f->min_freq <= 1.0)) { set_error("subset: min_freq must be between 0 and 1 (inclusive)"); return SKX_EINVAL; }
+    std::vector<int> order(samples, samples + n_samples);
+    for (int s : order) if (s < 0 || (size_t)s >= S) { set_error("subset: sample index %d out of range (the array has %zu samples)", s, S); return SKX_EINVAL; }
+    std::sort(order.begin(), order.end());                                    // delete_samples leaves the columns in the array's order (:256-268)
+    for (int i = 1; i < n_samples; i++) if (order[i] == order[i - 1]) { set_error("subset: sample index %d given twice", order[i]); return SKX_EINVAL; }
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    const uint64_t U = a->n_rows, n = (uint64_t)n_samples;
+    const uint64_t thr = (uint64_t)std::ceil((double)n * f->min_freq);         // generic_modes.rs:118
+    DevBuf<int> d_order, d_bad; DevBuf<uint8_t> keep; DevBuf<uint64_t> pos; DevBuf<unsigned long long> d_cnt;
+    uint64_t kept = 0; unsigned long long cnt[3] = {0, 0, 0}; int bad = 0;
+    {
+        PhaseTimer pv("align.groups_verdicts");
+        StageTimer t(ctx, &ctx->tm.filter);
+        SKX_TRY(d_order.alloc(n)); SKX_TRY(d_bad.alloc(1)); SKX_TRY(d_bad.zero(st)); SKX_TRY(d_cnt.alloc(3)); SKX_TRY(d_cnt.zero(st));
+        SKX_TRY(keep.alloc(U)); SKX_TRY(pos.alloc(U + 1));
+        SKX_HIP(hipMemcpyAsync(d_order.p, order.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_subset_verdicts(a->matrix.p, a->pitch, d_order.p, n_samples, U, thr, f->filter_ambig_as_missing != 0, f->filter_type, f->ignore_const_gaps != 0,
+                               keep.p, d_cnt.p, d_bad.p, st);
+        DevBuf<uint32_t> sc_sums; DevBuf<uint64_t> sc_offs;
+        SKX_TRY(sc_sums.alloc(scan_u8_blocks(U))); SKX_TRY(sc_offs.alloc(scan_u8_blocks(U) + 1));
+        if (out) {
+            launch_scan_u8(keep.p, pos.p, U, sc_sums.p, sc_offs.p, st);
+            SKX_HIP(hipMemcpyAsync(&kept, pos.p + U, 8, hipMemcpyDeviceToHost, st));
+        }
+        SKX_HIP(hipMemcpyAsync(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipStreamSynchronize(st));                                     // (order[] is the host's again)
+    }
+    if (bad) { set_error("variants contain a byte outside -ACGTMRWSYKVHDBN (not supported on the device path)"); return SKX_EUNSUP; }
+    const uint64_t rows_present = U - cnt[0];
+    if (!out) kept = rows_present - cnt[1] - cnt[2];
+    if (info) { info->rows_present = rows_present; info->removed = cnt[2]; info->silent = cnt[1]; info->sites = kept; }
+    if (!out) { SKX_HIP(hipGetLastError()); return SKX_OK; }
+    if (kept != rows_present - cnt[1] - cnt[2]) { set_error("subset: internal error: %llu rows placed, %llu counted", (unsigned long long)kept, (unsigned long long)(rows_present - cnt[1] - cnt[2])); return SKX_EINVAL; }
+    PhaseTimer pr("align.groups_rows");
+    std::unique_ptr<skx_array> b(new skx_array());
+    b->ctx = ctx; b->k = a->k; b->rc = a->rc; b->k_bits = a->k_bits; b->hp = a->hp; b->wh = a->wh; b->version = a->version;
+    for (int s : order) b->names.push_back(a->names[s]);
+    // no split k-mers, as after skx_array_load_filtered; their number is what the chain's would be (update_kmers = false keeps the delete's,
+    // update_counts(true) follows the rows)
+    b->engine_order = false; b->keys_absent = true; b->n_kmers = f->filter_ambig_as_missing ? kept : rows_present;
+    b->n_rows = kept; b->pitch = pitch_for(kept);
+    {
+        StageTimer t(ctx, &ctx->tm.compact);
+        SKX_TRY(b->matrix.alloc(n * b->pitch));
+        SKX_TRY(b->present.alloc(kept)); SKX_TRY(b->unambig.alloc(kept)); SKX_TRY(b->mask.alloc(kept)); SKX_TRY(b->vcount.alloc(kept));
+        if (kept) {
+            launch_compact_matrix(a->matrix.p, a->pitch, b->matrix.p, b->pitch, n_samples, U, keep.p, pos.p, f->mask_ambig != 0, st, d_order.p);
+            // the statistics of the kept rows from the kept cells (after mask_ambig, like launch_mask_ambig_stats leaves them)
+            launch_col_stats(b->matrix.p, b->pitch, n_samples, kept, b->present.p, b->unambig.p, b->mask.p, d_bad.p, st);
+            SKX_HIP(hipMemcpyAsync(b->vcount.p, f->filter_ambig_as_missing ? b->unambig.p : b->present.p, kept * 4, hipMemcpyDeviceToDevice, st));
+        }
+        SKX_HIP(hipStreamSynchronize(st));
+    }
+    SKX_HIP(hipGetLastError());
+    *out = b.release();
+    return SKX_OK;
+    });
+}
+
 extern "C" int skx_array_weed(skx_array *a, skx_keyset *weed, int reverse, uint64_t *removed)
 {
     return skx_guarded([&]() -> int {

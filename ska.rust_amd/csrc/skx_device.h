@@ -223,8 +223,13 @@ void launch_compact_rm(const uint8_t *cells, uint64_t S, uint64_t nr, const uint
 uint64_t scan_u8_blocks(uint64_t n);      // scratch of launch_scan_u8: sums[blocks] u32 + offs[blocks + 1] u64, owned by the caller
 void launch_scan_u8(const uint8_t *flags, uint64_t *pos, uint64_t n, uint32_t *sums, uint64_t *offs, hipStream_t st);   // pos[n] = total
 // out[s][pos[c]] = in[s][c] for kept c (optionally ambiguous -> 'N'); also compacts the stat/key arrays
+// order (device memory, or nullptr: the identity): output row s = input row order[s]
 void launch_compact_matrix(const uint8_t *in, uint64_t in_pitch, uint8_t *out, uint64_t out_pitch, int n_samples,
-                           uint64_t n_cols, const uint8_t *keep, const uint64_t *pos, int mask_ambig, hipStream_t st);
+                           uint64_t n_cols, const uint8_t *keep, const uint64_t *pos, int mask_ambig, hipStream_t st, const int *order = nullptr);
+// delete_samples of everybody outside order[0..n) + the filter, per column of the matrix: keep[c] = 1 kept, 0 removed, 2 silent or absent;
+// counts[0..2] (zeroed by the caller) += absent, silent, removed columns; *bad_byte = 1 for a cell outside the alphabet
+void launch_subset_verdicts(const uint8_t *matrix, uint64_t pitch, const int *order, int n, uint64_t n_cols, uint64_t min_count, int ambig_as_missing,
+                            int filter_type, int ignore_const_gaps, uint8_t *keep, unsigned long long *counts, int *bad_byte, hipStream_t st);
 void launch_compact_u32(const uint32_t *in, uint32_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
 void launch_compact_u64(const uint64_t *in, uint64_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
 void launch_compact_u128(const uint64_t *in, uint64_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);

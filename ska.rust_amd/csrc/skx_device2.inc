@@ -48,6 +48,18 @@ void launch_col_stats(const uint8_t *matrix, uint64_t pitch, int n_samples, uint
 
 // MergeSkaArray::filter (merge_ska_array.rs:289-402) decided from the column statistics.
 // keep: 1 kept, 0 removed (counts towards the return value), 2 dropped by update_counts(true) (:139-163, not counted)
+// the filter_type cases of the rule for a row that passed the frequency test (m: the row's set of IUPAC codes, bit c = code c occurs):
+// one function for filter_flags_kernel and subset_verdict_kernel
+__device__ static inline uint8_t filter_type_keep(int filter_type, int ignore_const_gaps, uint32_t m, bool has_gap)
+{
+    const uint32_t acgt = (1u << 1) | (1u << 2) | (1u << 4) | (1u << 8);
+    switch (filter_type) {
+    case 0: return 1;
+    case 1: return (__popc(m) + ((has_gap && !ignore_const_gaps) ? 1 : 0)) > 1;           // NoConst :322-334
+    case 2: return (m & ~acgt) == 0;                                                        // NoAmbig :335-344
+    default: return (__popc(m & acgt) + ((has_gap && !ignore_const_gaps) ? 1 : 0)) > 1;   // NoAmbigOrConst :345-367
+    }
+}
 __global__ void filter_flags_kernel(FilterArgs a)
 {
     const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,16 +74,7 @@ __global__ void filter_flags_kernel(FilterArgs a)
     }
     else if (a.ambig_as_missing && count == 0) keep = 2;
     else if ((uint64_t)count < a.min_count) keep = 0;
-    else {
-        const bool has_gap = present < a.n_samples;
-        const uint32_t acgt = (1u << 1) | (1u << 2) | (1u << 4) | (1u << 8);
-        switch (a.filter_type) {
-        case 0: keep = 1; break;
-        case 1: keep = (__popc(m) + ((has_gap && !a.ignore_const_gaps) ? 1 : 0)) > 1; break;          // NoConst :322-334
-        case 2: keep = (m & ~acgt) == 0; break;                                                       // NoAmbig :335-344
-        default: keep = (__popc(m & acgt) + ((has_gap && !a.ignore_const_gaps) ? 1 : 0)) > 1; break;  // NoAmbigOrConst :345-367
-        }
-    }
+    else keep = filter_type_keep(a.filter_type, a.ignore_const_gaps, m, present < a.n_samples);
     a.keep[c] = keep;
 }
 void launch_filter_flags(const FilterArgs &a, hipStream_t st)
@@ -88,9 +91,12 @@ __device__ static inline uint8_t mask_ambig_byte(uint8_t b)
 // One workgroup = 4096 columns x 32 samples.  Threads read 16 columns at a time (16-B loads), drop the filtered ones and
 // park the kept bytes of all 32 rows in LDS; the rows are then written with 16-B stores (the kept columns of a block are
 // consecutive in the output because pos is a prefix sum), byte stores only at the unaligned ends.
+// ORD (the subset alignments): output row s holds input row order[s]; the identity instantiation does not read `order`.
 constexpr int CMP_ROWS = 4;
+template <bool ORD = false>
 __global__ __launch_bounds__(256) void compact_matrix_kernel(const uint8_t *in, uint64_t in_pitch, uint8_t *out, uint64_t out_pitch,
-                                                             int n_samples, uint64_t n_cols, const uint8_t *keep, const uint64_t *pos, int mask_ambig)
+                                                             int n_samples, uint64_t n_cols, const uint8_t *keep, const uint64_t *pos, int mask_ambig,
+                                                             const int *order)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_buf[];       // [CMP_ROWS][stride]
     __shared__ uint32_t s_tmp[17];
@@ -115,7 +121,7 @@ __global__ __launch_bounds__(256) void compact_matrix_kernel(const uint8_t *in, 
         const uint8_t *src = in + (uint64_t)s0 * in_pitch + c;
 #pragma unroll 2
         for (int s = s0; s < s1; s++, src += in_pitch) {
-            const uint4 x4 = *reinterpret_cast<const uint4 *>(src);
+            const uint4 x4 = *reinterpret_cast<const uint4 *>(ORD ? in + (uint64_t)order[s] * in_pitch + c : src);
             const uint32_t xw[4] = {x4.x, x4.y, x4.z, x4.w};
             unsigned char *d = s_buf + (size_t)(s - s0) * stride + shift + lofs;
             uint32_t o = 0;
@@ -136,14 +142,90 @@ __global__ __launch_bounds__(256) void compact_matrix_kernel(const uint8_t *in, 
     }
 }
 void launch_compact_matrix(const uint8_t *in, uint64_t in_pitch, uint8_t *out, uint64_t out_pitch, int n_samples, uint64_t n_cols,
-                           const uint8_t *keep, const uint64_t *pos, int mask_ambig, hipStream_t st)
+                           const uint8_t *keep, const uint64_t *pos, int mask_ambig, hipStream_t st, const int *order)
 {
     if (!n_cols || !n_samples) return;
     const uint64_t groups = (n_cols + 15) / 16;
     const size_t lds = (size_t)CMP_ROWS * ((4096 + 32 + 15) & ~15u);
-    (void)hipFuncSetAttribute((const void *)compact_matrix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(compact_matrix_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)((n_samples + CMP_ROWS - 1) / CMP_ROWS)), dim3(256),
-                       lds, st, in, in_pitch, out, out_pitch, n_samples, n_cols, keep, pos, mask_ambig);
+    const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)((n_samples + CMP_ROWS - 1) / CMP_ROWS));
+    if (order) {
+        (void)hipFuncSetAttribute((const void *)compact_matrix_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(compact_matrix_kernel<true>, grid, dim3(256), lds, st, in, in_pitch, out, out_pitch, n_samples, n_cols, keep, pos, mask_ambig, order);
+        return;
+    }
+    (void)hipFuncSetAttribute((const void *)compact_matrix_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(compact_matrix_kernel<false>, grid, dim3(256), lds, st, in, in_pitch, out, out_pitch, n_samples, n_cols, keep, pos, mask_ambig, order);
+}
+
+// ---- subset alignments (`ska align --groups / --samples`): delete_samples (merge_ska_array.rs:231-271, update_counts(false) :139-163) of
+// everybody outside a sample list followed by the filter (:289-402), decided per column (= row of the reference) in one pass over the list's
+// cells, without the sub-matrix and without per-column statistics in memory.  A thread takes 16 columns (one 16-byte load per sample), keeps
+// present | unambig << 16 and the set of codes of each in registers, and writes keep[c] alone: 1 kept, 0 removed, 2 silent (update_counts(true))
+// or absent (no sample of the list has the row: delete_samples drops it).  counts[0..2] += absent, silent, removed: wave sums by shuffles,
+// the workgroup's through LDS, one atomic per workgroup and count.  The stored variant_count is not read: after the delete it is `present`.
+__global__ __launch_bounds__(256) void subset_verdict_kernel(const uint8_t *matrix, uint64_t pitch, const int *order, int n, uint64_t n_cols, uint64_t min_count,
+                                                             int ambig_as_missing, int filter_type, int ignore_const_gaps, uint8_t *keep,
+                                                             unsigned long long *counts, int *bad_byte)
+{
+    __shared__ uint8_t s_lut[256];
+    __shared__ uint32_t s_cnt[4][3];
+    s_lut[threadIdx.x] = (uint8_t)set_code(threadIdx.x);
+    __syncthreads();
+    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    uint32_t n_absent = 0, n_silent = 0, n_removed = 0;
+    if (c0 < n_cols) {
+        uint32_t pu[16], m[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) { pu[i] = 0; m[i] = 0; }
+        uint32_t bad = 0;                                                     // bit i: column c0 + i holds a byte outside the alphabet
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const uint8_t *col = matrix + c0;                                     // rows are padded to the pitch (>= 256 bytes past n_cols): the load stays inside the row
+        u32x4 nx = *reinterpret_cast<const u32x4 *>(col + (uint64_t)order[0] * pitch);
+        for (int s = 0; s < n; s++) {
+            const u32x4 cur = nx;
+            if (s + 1 < n) nx = *reinterpret_cast<const u32x4 *>(col + (uint64_t)order[s + 1] * pitch);
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const uint32_t code = s_lut[(cur[i >> 2] >> (8 * (i & 3))) & 0xFFu];
+                if (code == 0xFF) { bad |= 1u << i; continue; }
+                if (code) { pu[i] += 1u + (((code & (code - 1)) == 0) ? 0x10000u : 0u); m[i] |= 1u << code; }
+            }
+        }
+        uint32_t kw[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const uint32_t present = pu[i] & 0xFFFFu, unambig = pu[i] >> 16, count = ambig_as_missing ? unambig : present;
+            uint32_t k;
+            if (present == 0) k = 2;
+            else if (ambig_as_missing && count == 0) k = 2;
+            else if ((uint64_t)count < min_count) k = 0;
+            else k = filter_type_keep(filter_type, ignore_const_gaps, m[i], present < (uint32_t)n);
+            if (c0 + i < n_cols) {
+                n_absent += present == 0; n_silent += present != 0 && k == 2; n_removed += k == 0;
+                kw[i >> 2] |= k << (8 * (i & 3));
+            }
+        }
+        if (c0 + 16 <= n_cols) {
+            *reinterpret_cast<u32x4 *>(keep + c0) = u32x4{kw[0], kw[1], kw[2], kw[3]};      // keep[] is 256-byte aligned, c0 % 16 == 0
+            if (bad) *bad_byte = 1;
+        } else {
+            for (int i = 0; i < 16 && c0 + i < n_cols; i++) { keep[c0 + i] = (uint8_t)(kw[i >> 2] >> (8 * (i & 3))); if ((bad >> i) & 1u) *bad_byte = 1; }
+        }
+    }
+    for (int d = 32; d; d >>= 1) { n_absent += __shfl_down(n_absent, d, 64); n_silent += __shfl_down(n_silent, d, 64); n_removed += __shfl_down(n_removed, d, 64); }
+    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = n_absent; s_cnt[threadIdx.x >> 6][1] = n_silent; s_cnt[threadIdx.x >> 6][2] = n_removed; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const uint32_t t = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+        if (t) atomicAdd(&counts[threadIdx.x], (unsigned long long)t);
+    }
+}
+void launch_subset_verdicts(const uint8_t *matrix, uint64_t pitch, const int *order, int n, uint64_t n_cols, uint64_t min_count, int ambig_as_missing,
+                            int filter_type, int ignore_const_gaps, uint8_t *keep, unsigned long long *counts, int *bad_byte, hipStream_t st)
+{
+    if (!n_cols || n <= 0) return;
+    hipLaunchKernelGGL(subset_verdict_kernel, dim3((unsigned)((n_cols + 4095) / 4096)), dim3(256), 0, st, matrix, pitch, order, n, n_cols, min_count,
+                       ambig_as_missing, filter_type, ignore_const_gaps, keep, counts, bad_byte);
 }
 template <typename T>
 __global__ void compact_vec_kernel(const T *in, T *out, uint64_t n, const uint8_t *keep, const uint64_t *pos)

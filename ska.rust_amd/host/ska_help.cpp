@@ -47,7 +47,11 @@ const std::vector<Cmd> &commands()
           {"--ambig-mask", "", "Mask any ambiguous bases in the alignment with 'N'"},
           {"--no-gap-only-sites", "", "Ignore gaps '-' in constant sites (for low coverage samples)"},
           {"--threads", "<THREADS>", THREADS},
-          {"--gpus", "<GPUS>", "(MI355X engine) Number of GPUs (with sequence files or -f and the build options)"}}},
+          {"--gpus", "<GPUS>", "(MI355X engine) Number of GPUs (with sequence files or -f and the build options)"},
+          {"--groups", "<FILE>", "(MI355X engine) One alignment per group from a single load: FILE lists sample name and group label (comma or tab separated; <PREFIX>.clusters.csv of `ska distance --clusters` is taken as it is); writes <OUTPUT>.<label>.aln per group and <OUTPUT>.groups.tsv"},
+          {"--min-group-size", "<N>", "(MI355X engine) With --groups: skip groups of fewer than N samples [default: 2]"},
+          {"--samples", "<NAMES>", "(MI355X engine) Align only these samples (comma separated), as `ska delete` of the others followed by `ska align` would"},
+          {"--samples-file", "<FILE>", "(MI355X engine) The same, sample names from a file (one per line)"}}},
         {"map", "Write an ordered alignment using a reference sequence", "ska map [OPTIONS] <REFERENCE> [INPUT]...",
          {{"<REFERENCE>", "", "Reference FASTA file to map to"}, {"[INPUT]...", "", "A .skf file, or list of .fasta files"}},
          {{"-o", "<OUTPUT>", "Output filename (omit to output to stdout)"},

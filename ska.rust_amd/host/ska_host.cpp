@@ -886,7 +886,8 @@ struct Args {
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
-                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", nullptr};
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest",
+                            "--groups", "--min-group-size", "--samples", "--samples-file", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -1024,6 +1025,21 @@ int read_query_names(const Args &a, std::vector<std::string> &names)
             std::string line;
             while (std::getline(in, line)) { std::istringstream ls(line); std::string t; if (ls >> t) add(t); }
         }
+    }
+    return 0;
+}
+// --groups / --min-group-size / --samples / --samples-file of `ska align`: alignments of subsets from one load (skh_align_groups, skh_align_samples_fd)
+const struct { const char *flag, *arg; } SUBSET_OPTS[] = {{"--groups", "--groups <FILE>"}, {"--min-group-size", "--min-group-size <N>"}, {"--samples", "--samples <NAMES>"},
+                                                          {"--samples-file", "--samples-file <FILE>"}};
+int read_subset_names(const Args &a, std::vector<std::string> &names)
+{
+    auto add = [&](const std::string &n) { if (!n.empty() && std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n); };
+    if (a.has("--samples")) { std::istringstream ls(a.get("--samples")); std::string t; while (std::getline(ls, t, ',')) add(t); }
+    else if (a.has("--samples-file")) {                                                // one name per line
+        std::ifstream in(a.get("--samples-file"));
+        if (!in) return fail("Unable to open file_list");
+        std::string line;
+        while (std::getline(in, line)) { while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back(); add(line); }
     }
     return 0;
 }
@@ -1300,6 +1316,30 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (v.find_first_not_of("0123456789") != std::string::npos || v.empty()) return clap_invalid(v, "--threads <THREADS>", ("`" + v + "` isn't a valid number of cores").c_str());
         if (atoi(v.c_str()) < 1) return clap_invalid(v, "--threads <THREADS>", "Threads must be one or higher");
     }
+    if (cmd == "align") {
+        // the subsets are cut from one device's array: refused as clap refuses arguments that conflict, values that do not parse and a missing requirement
+        const auto conflict = [](const char *x, const char *y) {
+            fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", x, y, skh_usage_line("align"));
+            return 2;
+        };
+        for (auto &q : SUBSET_OPTS) if (a.has(q.flag) && (a.has("--gpus") || multi)) return conflict(q.arg, "--gpus <GPUS>");
+        for (const char *o : {"--samples", "--samples-file"}) if (a.has("--groups") && a.has(o)) return conflict("--groups <FILE>", o[9] ? "--samples-file <FILE>" : "--samples <NAMES>");
+        if (a.has("--samples") && a.has("--samples-file")) return conflict("--samples <NAMES>", "--samples-file <FILE>");
+        if (a.has("--min-group-size")) {
+            if (!a.has("--groups")) return clap_missing("align", "--groups <FILE>");
+            const std::string v = a.get("--min-group-size");                                     // usize::from_str, then the range
+            if (v.empty()) return clap_invalid(v, "--min-group-size <N>", "cannot parse integer from empty string");
+            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--min-group-size <N>", "invalid digit found in string");
+            if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, "--min-group-size <N>", "must be one or higher");
+        }
+        for (auto &q : SUBSET_OPTS) if (a.has(q.flag) && a.get(q.flag).empty()) return clap_invalid("", q.arg, "a value is required");
+        if (a.has("--groups") && !a.has("-o")) return clap_missing("align", "-o <OUTPUT>");
+        if (a.has("--samples") || a.has("--samples-file")) {
+            std::vector<std::string> names;
+            if (int e = read_subset_names(a, names)) return e;
+            if (names.empty()) return clap_invalid(a.get("--samples", a.get("--samples-file")), a.has("--samples") ? "--samples <NAMES>" : "--samples-file <FILE>", "no sample names given");
+        }
+    }
     if (cmd == "distance" && a.has("--no-table")) {
         // the tree and the clusters from the banded sweep, on one device, and nothing else: refused as clap refuses arguments that conflict and
         // a required group that is missing
@@ -1444,7 +1484,7 @@ extern "C" int skh_main(int argc, char **argv)
     {   // clap rejects what a subcommand does not declare (cli.rs:109-330); -v / --verbose is global (cli.rs:103-104)
         static const struct { const char *cmd; const char *flags; } KNOWN[] = {
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
-            {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus "},
+            {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus --groups --min-group-size --samples --samples-file "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
             {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
@@ -1523,12 +1563,27 @@ extern "C" int skh_main(int argc, char **argv)
         if (filter < 0) return fail("invalid --filter");
         const double mf = atof(a.get("--min-freq", a.get("-m", "0.9")).c_str());
         if (mf < 0 || mf > 1) return fail("Frequency must be between 0 and 1 (inclusive)");
+        if (a.has("--groups")) {                                                                                  // -o is the prefix of the groups' files
+            const int min_size = (int)std::min<unsigned long long>(strtoull(a.get("--min-group-size", "2").c_str(), nullptr, 10), INT_MAX);
+            if (skh_align_groups(ctx, in.data(), (int)in.size(), threads, filter, a.has("--ambig-mask"), a.has("--no-gap-only-sites"), mf, a.has("--filter-ambig-as-missing"),
+                                 a.get("--groups").c_str(), min_size, a.get("-o").c_str()) != SKX_OK)
+                rcode = engine_fail();
+        } else {
         int fd = 1;                                                                                               // io_utils::set_ostream: stdout or -o
         if (a.has("-o")) { fd = open(a.get("-o").c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644)   /* read-write: the writer maps the file */; if (fd < 0) return fail("cannot create output file"); }
-        if (skh_align_inputs_fd(ctx, in.data(), (int)in.size(), threads, filter, a.has("--ambig-mask"), a.has("--no-gap-only-sites"), mf,
+        if (a.has("--samples") || a.has("--samples-file")) {
+            std::vector<std::string> names; std::vector<const char *> cn;
+            if (int e = read_subset_names(a, names)) return e;
+            for (auto &n : names) cn.push_back(n.c_str());
+            if (skh_align_samples_fd(ctx, in.data(), (int)in.size(), threads, filter, a.has("--ambig-mask"), a.has("--no-gap-only-sites"), mf, a.has("--filter-ambig-as-missing"),
+                                     cn.data(), (int)cn.size(), fd) != SKX_OK)
+                rcode = engine_fail();
+        }
+        else if (skh_align_inputs_fd(ctx, in.data(), (int)in.size(), threads, filter, a.has("--ambig-mask"), a.has("--no-gap-only-sites"), mf,
                                 a.has("--filter-ambig-as-missing"), fd) != SKX_OK)
             rcode = engine_fail();
         if (fd != 1) close(fd);
+        }
     } else if (cmd == "distance") {
         if (a.pos.size() != 1) return fail("one .skf file required");
         const char *in[1] = {a.pos[0].c_str()};

@@ -85,6 +85,11 @@ class BandedInfo(C.Structure):
     _fields_ = [("bands", C.c_uint64), ("band_rows", C.c_uint64), ("count_buffer_bytes", C.c_uint64), ("edges", C.c_uint64), ("clusters", C.c_uint64)]
 
 
+class SubsetInfo(C.Structure):
+    """skx_subset_info (include/skx.h): what Array.subset_filtered did"""
+    _fields_ = [("rows_present", C.c_uint64), ("removed", C.c_uint64), ("silent", C.c_uint64), ("sites", C.c_uint64)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[skx {code}] {msg}")
@@ -107,7 +112,8 @@ skx_array_lo_graph skx_lo_graph_info skx_lo_graph_export skx_lo_gather skx_lo_gr
 skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_tsv_extras
 skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv
 skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv
-skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files""".split()
+skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files
+skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd""".split()
 
 _lib = None
 
@@ -148,6 +154,10 @@ def load_library():
     lib.skh_clusters_csv.argtypes = [C.POINTER(cp), vp, i, pp, C.POINTER(u64)]
     lib.skh_cluster_cutoffs.argtypes = [d, d, i, C.POINTER(u64), C.POINTER(d)]
     lib.skh_distance_banded_files.argtypes = [vp, cp, d, i, C.POINTER(DistExtras)]
+    lib.skx_array_subset_filtered.argtypes = [vp, vp, i, C.POINTER(FilterSpec), pp, C.POINTER(SubsetInfo)]
+    lib.skh_read_groups.argtypes = [cp, pp, C.POINTER(u64), C.POINTER(u64)]
+    lib.skh_align_groups.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, cp, i, cp]
+    lib.skh_align_samples_fd.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, C.POINTER(cp), i, i]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -471,6 +481,24 @@ class Context:
         x = DistExtras(tree.encode() if tree else None, clusters.encode() if clusters else None, cluster_snps, cluster_mismatches)
         _check(_lib.skh_distance_banded_files(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(x)))
 
+    def align_groups(self, inputs, groups_file, out_prefix, min_group_size=2, threads=1, min_freq=0.9, filter_ambig_as_missing=False,
+                     filter_type=FILTER_NO_CONST, mask_ambig=False, ignore_const_gaps=False):
+        """`ska align <inputs> --groups FILE -o PREFIX` (skh_align_groups): PREFIX.<label>.aln per group and PREFIX.groups.tsv from one load"""
+        inputs = [inputs] if isinstance(inputs, str) else list(inputs)
+        arr = (C.c_char_p * len(inputs))(*[x.encode() for x in inputs])
+        _check(_lib.skh_align_groups(self.h, arr, len(inputs), int(threads), int(filter_type), int(mask_ambig), int(ignore_const_gaps), float(min_freq),
+                                     int(filter_ambig_as_missing), groups_file.encode(), int(min_group_size), out_prefix.encode()))
+
+    def align_samples(self, inputs, names, fd, threads=1, min_freq=0.9, filter_ambig_as_missing=False, filter_type=FILTER_NO_CONST, mask_ambig=False,
+                      ignore_const_gaps=False):
+        """`ska align <inputs> --samples NAMES` (skh_align_samples_fd): the alignment of that subset streamed to a file descriptor"""
+        inputs = [inputs] if isinstance(inputs, str) else list(inputs)
+        names = list(names)
+        arr = (C.c_char_p * len(inputs))(*[x.encode() for x in inputs])
+        nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+        _check(_lib.skh_align_samples_fd(self.h, arr, len(inputs), int(threads), int(filter_type), int(mask_ambig), int(ignore_const_gaps), float(min_freq),
+                                         int(filter_ambig_as_missing), nm, len(names), int(fd)))
+
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.skx_ctx_destroy(self.h)
@@ -527,6 +555,21 @@ def clusters_csv(names, labels):
     p, ln = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_clusters_csv(arr, _np_ptr(lab), n, C.byref(p), C.byref(ln)))
     return _take(p, ln).decode()
+
+
+def read_groups(path):
+    """skh_read_groups: the groups file of `ska align --groups` -> [(label, [sample names])] in the order the labels first appear (host only)"""
+    load_library()
+    p, ln, n = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    _check(_lib.skh_read_groups(os.fsencode(path), C.byref(p), C.byref(ln), C.byref(n)))
+    parts = _take(p, ln).split(b"\0")[:-1]
+    groups = []
+    for name, label in zip(parts[0::2], parts[1::2]):
+        label = label.decode()
+        if not groups or groups[-1][0] != label:
+            groups.append((label, []))
+        groups[-1][1].append(name.decode())
+    return groups
 
 
 def cluster_cutoffs(max_snps, max_mismatches, filt_ambig=True):
@@ -891,6 +934,16 @@ class Array:
     def delete_samples(self, names):
         nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
         _check(_lib.skx_array_delete_samples(self.h, nm, len(names)))
+
+    def subset_filtered(self, samples, min_freq=0.9, filter_ambig_as_missing=False, filter_type=FILTER_NO_CONST, mask_ambig=False, ignore_const_gaps=False,
+                        two_stage=False, counts_only=False):
+        """skx_array_subset_filtered: delete_samples(everybody else) + apply_filters as a new array, this one left as it is
+        -> (Array | None with counts_only, {"rows_present", "removed", "silent", "sites"}); samples = distinct column indices in any order"""
+        idx = np.ascontiguousarray(samples, np.int32)
+        fs = FilterSpec(min_freq, int(filter_ambig_as_missing), filter_type, int(mask_ambig), int(ignore_const_gaps), int(two_stage))
+        h, info = C.c_void_p(), SubsetInfo()
+        _check(_lib.skx_array_subset_filtered(self.h, _np_ptr(idx), len(idx), C.byref(fs), None if counts_only else C.byref(h), C.byref(info)))
+        return (None if counts_only else Array(h, self.ctx)), {n: getattr(info, n) for n, _ in SubsetInfo._fields_}
 
     def map(self, reference, fmt="aln", ambig_mask=False, repeat_mask=False, threads=0):
         """generic_modes::map: RefSka::new + map + write_aln | write_vcf -> text (generic_modes.rs:56-84)."""
