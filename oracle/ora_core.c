@@ -495,6 +495,34 @@ ora_array *ora_array_from_dicts(ora_dict *const *dicts, const char *const *names
     return arr;
 }
 
+/* An array from caller-supplied rows (the counterpart of the engine's skx_array_from_host): keys[n_rows], variants row-major
+ * [n_rows, n], counts optional -- without them a row's variant_count is its number of non-'-' cells, as MergeSkaArray::new
+ * leaves it (merge_ska_array.rs:172-175).  Rows stay in the given order; a 0 cell is stored as '-' (:175).  Lets the CPU suite
+ * put arbitrary matrices (stored counts that differ from the rows, all-'-' rows, no rows at all) through merge / delete / weed. */
+ora_array *ora_array_from_rows(int k, int rc, const char *const *names, int n, const ora_key *keys, const uint8_t *variants,
+                               const uint64_t *counts, size_t n_rows)
+{
+    if (n <= 0 || !names) { ora_set_error("no samples"); return NULL; }
+    if (k < 5 || k > 63 || !(k & 1)) { ora_set_error("K-mer must be an odd number between 5 and 63 (inclusive)"); return NULL; }
+    if (n_rows && (!keys || !variants)) { ora_set_error("rows without keys or variants"); return NULL; }
+    const size_t S = (size_t)n, U = n_rows;
+    ora_array *a = (ora_array *)calloc(1, sizeof *a);
+    a->k = k; a->rc = rc; a->k_bits = k <= 31 ? 64 : 128; a->nk = a->nrows = U; a->ns = S;
+    a->keys = (ora_key *)malloc((U ? U : 1) * sizeof(ora_key));
+    a->var = (uint8_t *)malloc(U * S + 1);
+    a->counts = (uint64_t *)calloc(U ? U : 1, 8);
+    a->names = (char **)malloc(S * sizeof(char *));
+    for (size_t s = 0; s < S; s++) a->names[s] = strdup(names[s]);
+    a->version = strdup("0.5.2");
+    for (size_t r = 0; r < U; r++) {
+        a->keys[r] = keys[r];
+        uint64_t c = 0;
+        for (size_t s = 0; s < S; s++) { const uint8_t b = variants[r * S + s] ? variants[r * S + s] : (uint8_t)'-'; a->var[r * S + s] = b; c += b != '-'; }
+        a->counts[r] = counts ? counts[r] : c;
+    }
+    return a;
+}
+
 /* ------------------------------------------------------- MergeSkaArray */
 void ora_array_free(ora_array *a)
 {

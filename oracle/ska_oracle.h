@@ -80,6 +80,10 @@ ora_array *ora_build_and_merge(const char *const *names, const char *const *file
                                int n, int k, int rc, const ora_qual *q, int threads, double proportion_reads);
 /* same, but from already-built per-sample dicts (append in index order) */
 ora_array *ora_array_from_dicts(ora_dict *const *dicts, const char *const *names, int n);
+/* from caller-supplied rows, like the engine's skx_array_from_host: variants row-major [n_rows, n]; counts NULL = the number of
+ * non-'-' cells of each row.  Rows keep the given order. */
+ora_array *ora_array_from_rows(int k, int rc, const char *const *names, int n, const ora_key *keys, const uint8_t *variants,
+                               const uint64_t *counts, size_t n_rows);
 ora_array *ora_array_load(const char *path, int want_bits /*64|128|0=either*/);
 int  ora_array_save(const ora_array *a, const char *path);
 void ora_array_free(ora_array *a);

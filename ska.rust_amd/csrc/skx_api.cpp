@@ -2148,6 +2148,8 @@ extern "C" int skx_array_subset_filtered(skx_array *a, const int *samples, int n
     });
 }
 
+// MergeSkaArray::weed (merge_ska_array.rs:452-487): rows whose split k-mer is (reverse: is not) in `weed` go.  variant_count is carried:
+// a kept row keeps its stored count (array_keep_rows compacts vcount as it is) -- unlike merge and delete_samples above, which recount.
 extern "C" int skx_array_weed(skx_array *a, skx_keyset *weed, int reverse, uint64_t *removed)
 {
     return skx_guarded([&]() -> int {

@@ -4,6 +4,12 @@
 // Rows are identified by their packed word (H(key) << 4 | 1), so "same split k-mer" is one 64-bit compare and every
 // set operation is a sort / search in the order of H.  The sort and the unique are the engine's own primitives
 // (skx_prims.hip: stable LSD radix sort, compaction; rocPRIM calls until round 5); the look-ups and the column scatter are below.
+// What each operation does to variant_count (the count a later filter's threshold reads):
+//   merge   recounts: the cells of the merged row that are not '-' (MergeSkaArray::new, merge_ska_array.rs:172); rows no sample has stay, with 0
+//   delete  recounts over the remaining columns and drops the rows that come to 0 (update_counts(false), :139-163,270)
+//   weed    carries: a kept row keeps the count it was stored with, even where that differs from its cells (:468-470); the filter that
+//           `ska weed` may run afterwards compares that stored count with floor(S * min_freq) (generic_modes.rs:249), and rewrites it
+//           only under --filter-ambig-as-missing (update_counts(true), :308-310)
 #include <algorithm>
 #include <cstring>
 #include "skx_internal.h"

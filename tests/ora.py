@@ -59,6 +59,8 @@ def _load():
     lib.ora_build_and_merge.argtypes = [C.POINTER(cp), C.POINTER(cp), C.POINTER(cp), i, i, i, C.POINTER(Qual), i, d]
     lib.ora_array_from_dicts.restype = vp
     lib.ora_array_from_dicts.argtypes = [C.POINTER(vp), C.POINTER(cp), i]
+    lib.ora_array_from_rows.restype = vp
+    lib.ora_array_from_rows.argtypes = [i, i, C.POINTER(cp), i, vp, vp, vp, sz]
     lib.ora_array_load.restype = vp
     lib.ora_array_load.argtypes = [cp, i]
     lib.ora_array_save.argtypes = [vp, cp]
@@ -225,6 +227,15 @@ class Array:
         hs = (C.c_void_p * n)(*[d.h for d in dicts])
         nm = (C.c_char_p * n)(*[x.encode() for x in names])
         return cls(lib.ora_array_from_dicts(hs, nm, n))
+
+    @classmethod
+    def from_rows(cls, k, rc, names, keys, variants, counts=None):
+        """an array from caller-supplied rows, like the engine's Array.from_host: variants [U, S]; counts None = non-'-' cells per row"""
+        keys = np.ascontiguousarray(keys, KEY_DT)
+        variants = np.ascontiguousarray(variants, np.uint8).reshape(len(keys), len(names))
+        counts = np.ascontiguousarray(counts, np.uint64) if counts is not None else None
+        nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        return cls(lib.ora_array_from_rows(k, int(rc), nm, len(names), _np_ptr(keys), _np_ptr(variants), _np_ptr(counts), len(keys)))
 
     @classmethod
     def load(cls, path, want_bits=0):
