@@ -189,7 +189,7 @@ int  skx_array_set_total_samples(skx_array *a, uint64_t total_samples);
 typedef struct { double distance, mismatch_prop; uint64_t match_count, mismatch_count; } skx_dist;
 /* MergeSkaArray::distance (merge_ska_array.rs:416-438,587-632): upper triangle, pairs (i<j) row-major.  filt_ambig = 0 (--allow-ambiguous):
  * rows in which no cell is ambiguous -- the array's row statistics say which -- are counted by the 4-plane sweep, the others by the
- * twelve-class one; the sums are the reference's per-row sums either way */
+ * twelve-class one; the sums are the reference's per-row sums either way.  SKX_EINVAL for a null array or table, like every form below */
 int  skx_array_distance(skx_array *a, double constant, int filt_ambig, skx_dist *out);
 /* generic_modes::distance (generic_modes.rs:136-189) in one call that leaves the array as it is: rows below ceil(n_samples *
  * min_freq) (when min_freq * n_samples >= 1) and constant rows are skipped while the bit planes are built (*constant = rows the

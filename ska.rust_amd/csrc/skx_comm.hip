@@ -648,8 +648,8 @@ extern "C" int skx_array_distance_sharded(skx_comm *c, skx_array *a, int filt_am
     skx_dist *mine_out = c->rank == 0 ? out : (band.resize(sizes[c->rank] / sizeof(skx_dist) + 1), band.data());
     {
         PhaseTimer pt("distance.pair_sweep");
-        if (hi > lo && !split) SKX_TRY(planes_distance(ctx, planes.p, (int)S, wpr, filt_ambig, constant, lo, hi, mine_out));
-        if (hi > lo && split) SKX_TRY(planes_distance_split(ctx, planes_c.p, wpr_c, rows_c, planes_d.p, wpr_d, rows_d, (int)S, constant, lo, hi, mine_out));
+        const PlanesView v = split ? PlanesView{{planes_c.p, wpr_c, rows_c}, {planes_d.p, wpr_d, rows_d}, true} : PlanesView{{planes.p, wpr, a->n_rows}, {}, false};
+        if (hi > lo) SKX_TRY(planes_table(ctx, v, (int)S, filt_ambig, constant, lo, hi, mine_out));
     }
     PhaseTimer pt("comm.pairs_to_rank0");
     return comm_gather_root_host(c, mine_out, sizes, out);

@@ -973,7 +973,7 @@ __global__ __launch_bounds__(256) void pair_fix_kernel(unsigned long long *out, 
 // equal -- what those classes are on rows where no cell is ambiguous (planes built with FILT over such rows: present = unambiguous there)
 // Returns 0, or the hipError_t of the allocation / launch that failed (nothing is left running).  A filt_ambig launch derives count [0] from
 // count [slot_u] (pair_fix_kernel: o[0] += |Ui| + |Uj| - 2 o[slot_u]): `out`'s slot_u must hold THIS launch's counts only, i.e. be zero on
-// entry -- one filtered launch per out buffer (planes_distance_split runs its filtered launch first, into a zeroed buffer).
+// entry -- one filtered launch per out buffer (sweep_band in skx_distance.cpp runs its filtered launch first, into a zeroed buffer).
 int launch_pair_counts(const uint64_t *planes, int n_samples, uint64_t wpr, int filt_ambig, unsigned long long *out, hipStream_t st, int i_lo, int i_hi)
 {
     if (n_samples < 2 || !wpr) return 0;

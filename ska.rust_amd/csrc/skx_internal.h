@@ -89,7 +89,20 @@ struct skx_ctx {
     std::string merge_path;          // which kernels the last merge on this context went through, and why (skx_ctx_merge_path)
 };
 
-namespace skx { uint64_t next_object_id(); }
+namespace skx {
+struct StageTimer {        // HIP-event bracket around one stage on the ctx stream
+    skx_ctx *c; double *slot;
+    StageTimer(skx_ctx *c_, double *s) : c(c_), slot(s) { if (c->timing) (void)hipEventRecord(c->ev[0], c->stream); }
+    ~StageTimer()
+    {
+        if (!c->timing) return;
+        (void)hipEventRecord(c->ev[1], c->stream);
+        (void)hipEventSynchronize(c->ev[1]);
+        float ms = 0; if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) *slot += ms;
+    }
+};
+uint64_t next_object_id();
+}
 struct skx_dictset {
     const uint64_t id = skx::next_object_id();   // what a key set's pieces / notes are matched to their dictset by (an address can be reused)
     skx_ctx *ctx = nullptr;
@@ -314,7 +327,7 @@ int skf_read_stream(const char *path, SkfMeta &m, std::vector<skx_key> &keys, st
                     const DevDecode *dev = nullptr);
 }  // namespace skx
 
-// helpers shared by the ABI translation units (skx_api.cpp, skx_build_files.cpp, skx_api_io.cpp)
+// helpers shared by the ABI translation units (skx_api.cpp, skx_build_files.cpp, skx_api_io.cpp, skx_distance.cpp)
 namespace skx {
 // the one or two paths of a sample, and what a look at a file tells (skx_build_files.cpp): each caller decides for itself what it makes of it
 struct SampleFiles { const char *f[2]; int n; const char *const *begin() const { return f; } const char *const *end() const { return f + n; } };
@@ -336,16 +349,16 @@ int reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std:
 int dictset_sort(skx_dictset *d);                                    // raw regions -> sorted, folded regions + sub-index (no-op when they are)
 int keyset_flatten(skx_keyset *ks);                                  // ks->flat = the rows as one compact list of packed words (engine order)
 int keyset_union_tables(skx_ctx *ctx, const uint64_t *words, const std::vector<uint64_t> &h_off, const std::vector<uint32_t> &h_cnt, int k, int rc, skx_keyset **out);
-struct QueryPlan;                                                    // skx_api.cpp: the query-first order of skx_array_distance_query (nullptr: the table's pairs)
-int planes_distance(skx_ctx *ctx, const uint64_t *planes, int S, uint64_t wpr, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out,
-                    const QueryPlan *qp = nullptr);
-// --allow-ambiguous with the rows split by whether one of their cells is ambiguous: planes_clean = 4 planes (FILT) of the rows without such a cell
-// (counts filed as classes 0-2), planes_dirty = 8 planes of the others; either may be absent (nullptr / 0 rows)
-int planes_distance_split(skx_ctx *ctx, const uint64_t *planes_clean, uint64_t wpr_clean, uint64_t rows_clean, const uint64_t *planes_dirty, uint64_t wpr_dirty,
-                          uint64_t rows_dirty, int S, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp = nullptr);
+// ---- distance (skx_distance.cpp).  What a pair sweep reads, not owned: one plane set (4 planes with filt_ambig, 8 without), or --allow-ambiguous
+// with the rows split by whether one of their cells is ambiguous: one = 4 planes (FILT) of the rows without such a cell (counts filed as classes
+// 0-2), dirty = 8 planes of the others.  A set without rows (or with p == nullptr) is not swept: its counts are zero
+struct PlanesView { struct Set { const uint64_t *p = nullptr; uint64_t wpr = 0, rows = 0; } one, dirty; bool split = false; };
+struct QueryPlan;                                                    // the query-first order of skx_array_distance_query (nullptr: the table's pairs)
+// VariantDist of the pairs (i in [i_lo, i_hi), j > i), row-major in out (qp: as skx_array_distance_query lays them out): count buffer, sweep, finish
+int planes_table(skx_ctx *ctx, const PlanesView &v, int S, int filt_ambig, double constant, int i_lo, int i_hi, skx_dist *out, const QueryPlan *qp = nullptr);
 // numerators over 36 of |S1 n S2| / (|S1||S2|) per pair class [2..11] of pair_counts_kernel<false> (constexpr: host and device code read the same table)
 constexpr int pair_class_num(int q) { constexpr int t[10] = {36, 18, 12, 9, 18, 6, 12, 4, 8, 12}; return t[q]; }
-// ---- line selection (skx_select.hip; driver: distance_select in skx_api.cpp) over a band's count buffer [i_hi - i_lo][S][DIST_NCOUNT]
+// ---- line selection (skx_select.hip; driver: array_distance_select in skx_distance.cpp) over a band's count buffer [i_hi - i_lo][S][DIST_NCOUNT]
 // a candidate pair as the device hands it over: the integers finish_counts turns into the table's skx_dist
 struct SelRecord { uint32_t i, j; unsigned long long mism, m, key; };
 // one place of a sample's --closest list: sort_key = key << 32 | partner (all ones: unused), ascending = (distance, partner index) ascending
@@ -355,7 +368,7 @@ struct SelCriteria { int filt_ambig; double constant; unsigned long long kmax; d
 // the distance of a pair from its key, the exact numerator (over 1 with filt_ambig, over 36 without): one expression for the table (finish_counts),
 // the thresholds' derivation and the matrix the banded form fills on the device
 __host__ __device__ inline double key_distance(unsigned long long key, int filt_ambig) { return filt_ambig ? (double)key : (double)key / 36.0; }
-// counts of one pair -> its integers (the first half of finish_pair, skx_api.cpp); true when the pair passes the thresholds.  The mismatch
+// counts of one pair -> its integers (the first half of finish_pair, skx_distance.cpp); true when the pair passes the thresholds.  The mismatch
 // threshold is finish_pair's expression in float64: a file that calls this is compiled with -ffp-contract=off (Makefile)
 struct SelPair { unsigned long long mism, m, key; };
 __device__ inline bool sel_pair(const unsigned long long *c, int filt_ambig, double constant, unsigned long long kmax, double pmax, SelPair &o)
@@ -382,7 +395,7 @@ void launch_select_write(const unsigned long long *cnt, int S, int i_lo, int i_h
 // *n_candidates += the band's candidate pairs
 void launch_select_nearest(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, uint32_t K, SelNear *lists, unsigned long long *n_candidates,
                            hipStream_t st);
-// ---- the banded consumers that keep their result on the device (skx_banded.hip; driver: array_distance_banded in skx_api.cpp), over the same buffer
+// ---- the banded consumers that keep their result on the device (skx_banded.hip; driver: array_distance_banded in skx_distance.cpp), over the same buffer
 // parent[S] = 0 .. S-1: every sample its own tree
 void launch_cluster_init(uint32_t *parent, int S, hipStream_t st);
 // links the two trees of every pair (i in [i_lo, i_hi), j > i) that passes c, the higher root under the lower (32-bit atomicMin on parent[]): no

@@ -224,7 +224,7 @@ int nj_check_n(int n)
     if (n > 65535) { set_error("neighbour joining: %d samples; at most 65535", n); return SKX_EUNSUP; }
     return SKX_OK;
 }
-// the entry of the banded form (skx_api.cpp), which fills the matrix on the device itself
+// the entry of the banded form (skx_distance.cpp), which fills the matrix on the device itself
 int nj_run_device(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, skx_nj_join *joins) { return nj_run(ctx, D, pitch, S, joins); }
 
 }  // namespace skx

@@ -2,7 +2,7 @@
 // the pairs of one band of the pair matrix that pass the thresholds, or every sample's K nearest candidates, picked on the device from the
 // band's count buffer [band][S][DIST_NCOUNT] as launch_pair_counts leaves it.  Only the picked pairs reach the host.
 //
-// A pair's integers restate the first half of finish_pair (skx_api.cpp): mismatches, m (what is added to the constant for the matches) and
+// A pair's integers restate the first half of finish_pair (skx_distance.cpp): mismatches, m (what is added to the constant for the matches) and
 // key, the exact numerator of the distance (distance = key with filt_ambig, key / 36 without).  `key <= kmax` is the SNP threshold in
 // integers (the host derives kmax from finish_pair's own expression); the mismatch threshold is finish_pair's expression in float64 --
 // this file is compiled with -ffp-contract=off (Makefile) so that the add and the divide stay two correctly rounded operations.

@@ -82,3 +82,15 @@ def test_skf_peek_k_reads_the_first_fields_only():
     assert found.get("merge_k41.skf") == 41 and found.get("merge_k9.skf") == 9 and found.get("merge.skf") == 17, found
     assert lib.skx_skf_peek_k(b"/nonexistent/file.skf") == 0
     assert lib.skx_skf_peek_k(__file__.encode()) == 0                      # not an .skf at all
+
+
+def test_distance_refuses_null_arguments():
+    """skx_array_distance and its query twin check their array and their table before anything else: an error and its message, not a crash.
+    No device is touched."""
+    lib = E.load_library()
+    out = (C.c_char * 32)()
+    query = (C.c_int * 1)(0)
+    for call in (lambda: lib.skx_array_distance(None, C.c_double(0.0), 1, out), lambda: lib.skx_array_distance_query(None, C.c_double(0.0), 1, query, 1, out)):
+        lib.skx_set_last_error(b"")
+        assert call() == E.EINVAL
+        assert lib.skx_last_error() == b"bad arguments"
