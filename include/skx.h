@@ -232,6 +232,27 @@ int  skx_array_distance_select(skx_array *a, double min_freq, int filt_ambig, co
  * skx_array_distance_query_filtered: every row is swept and `constant` (>= 0, else SKX_EINVAL) is added to every pair's matches. */
 int  skx_array_distance_select_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_select_spec *spec, skx_dist_pair **pairs,
                                            uint64_t *n_pairs, skx_select_info *info);
+/* The minimum spanning forest of that table (`ska distance --mst`): the candidates are the lines that pass max_snps / max_mismatches as for
+ * skx_array_distance_select (every line when neither is given); the lines are ordered by (distance, i, j) -- the distance, then the line's place
+ * in the table -- which is strict, so the forest is unique: n_samples - (connected components of the candidates) lines.  Cut at L it gives the
+ * single-linkage clusters of every threshold L at once.  Kept on the device across the bands of the same sweep (after a band: the forest of the
+ * bands so far; the next band merges its candidates in by Boruvka rounds), in O(n_samples) memory beside the band's count buffer.  The device
+ * orders by the exact integer numerator of the distance, which orders as the float64 value and as its two printed decimals do. */
+typedef struct { double max_snps, max_mismatches; int32_t band_rows; } skx_mst_spec;   /* thresholds as skx_select_spec: < 0 = not set; band_rows as there */
+/* what a call did: bands swept, first samples per band, bytes of the device count buffer, pairs that passed the thresholds, the forest's lines,
+ * its trees (n_samples - edges), the most rounds a band took to merge */
+typedef struct { uint64_t bands, band_rows, count_buffer_bytes, candidates, edges, components, rounds; } skx_mst_info;
+/* pairs: malloc'd (skx_free), n_pairs of them ascending by (i, j), every d bit for bit the full table's entry; constant / rows_used as
+ * skx_array_distance_filtered reports them; info may be NULL.  SKX_EINVAL with a message that begins "distance mst:" for a NaN threshold,
+ * max_mismatches > 1 or band_rows < 0; SKX_EUNSUP with the same beginning above 65 536 samples, or at 2^32 / 36 swept rows and more (an edge is
+ * one 64-bit word: the numerator, 16 bits a sample).  Fewer than two samples: zero pairs.  The array is left as it is; both key widths and arrays
+ * held as pieces are taken. */
+int  skx_array_distance_mst(skx_array *a, double min_freq, int filt_ambig, const skx_mst_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                            int64_t *constant, uint64_t *rows_used, skx_mst_info *info);
+/* The same on an array the two filters have been applied to already, as skx_array_distance_select_prefiltered is to skx_array_distance_select
+ * (constant >= 0, else SKX_EINVAL) */
+int  skx_array_distance_mst_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_mst_spec *spec, skx_dist_pair **pairs,
+                                        uint64_t *n_pairs, skx_mst_info *info);
 /* The two halves of skx_array_distance, so that a multi-GPU host can exchange the bit planes between them (SURVEY.md 8e:
  * "tile the pair matrix over ranks"): every rank builds the planes of its own samples over the (globally filtered) rows, the
  * planes are all-gathered (plane-major: planes[p][sample][word], 4 planes with filt_ambig, 8 without), and each rank

@@ -63,6 +63,15 @@ int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const char *query
 /* `ska distance <skf> --max-snps / --max-mismatches / --closest`: the header and exactly those lines of skh_distance_skf_tsv's table that
  * skx_array_distance_select keeps under `spec`, in the table's order and text.  The same one-pass filtered load; the full table is never formed. */
 int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_select_spec *spec, char **buf, uint64_t *len);
+/* `ska distance <skf> --mst`: the header and the lines of skh_distance_skf_tsv's table that form its minimum spanning forest under `spec`
+ * (skx_array_distance_mst), in the table's order and text.  The same one-pass filtered load; the full table is never formed. */
+int skh_distance_mst_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, char **buf, uint64_t *len);
+/* the clusters of a forest at a ladder of SNP thresholds (host only): for each of the n_levels levels L, in the order given, the connected
+ * components of the forest's lines whose distance as the table prints it ("%.2f") is <= L -- the single-linkage clusters of `--clusters
+ * --cluster-snps L` when the forest is the whole table's -- numbered 1, 2, ... in ascending order of their lowest sample.  csv: the header
+ * "id,snps_<L>,...,address" (every L printed "%g"), one line per sample in the array's order, names written as skh_clusters_csv writes them,
+ * `address` the level columns joined by '.'.  pairs: i < j < n, as skx_array_distance_mst returns them. */
+int skh_mst_levels_csv(const char *const *names, const skx_dist_pair *pairs, uint64_t n_pairs, int n, const double *levels, int n_levels, char **buf, uint64_t *len);
 /* the joins of skx_dist_nj / skx_matrix_nj over n leaves as one line of Newick (host only).  A negative raw length is written as 0 and the
  * difference moved to the sibling branch of the same join, so the distance between the two joined nodes is kept (Kuhner-Felsenstein).
  * Midpoint root: the two leaves with the largest path distance in the corrected tree (ties to the lowest (id, id)), the root half way

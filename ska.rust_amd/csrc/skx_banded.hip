@@ -15,28 +15,14 @@
 // the passing pairs -- and therefore every label is the same whatever the order of lanes, workgroups and bands.  No float atomics; the
 // mismatch threshold is finish_pair's add and divide in float64, each rounded once: this file is compiled with -ffp-contract=off (Makefile).
 #include "skx_internal.h"
+#include "skx_unionfind.h"
 
 namespace skx {
 namespace {
 
 constexpr int BND_NT = 256;                       // threads of the row workgroups
 
-__device__ inline uint32_t uf_root(const uint32_t *parent, uint32_t x)
-{
-    for (uint32_t p; (p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != x;) x = p;
-    return x;
-}
-__device__ inline void uf_link(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = uf_root(parent, a); b = uf_root(parent, b);
-        if (a == b) return;
-        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const uint32_t old = atomicMin(parent + hi, lo);
-        if (old == hi) return;                    // hi was a root and now hangs under lo
-        a = old; b = lo;                          // hi hangs under min(old, lo); the trees of old and lo are still to be joined
-    }
-}
+// (uf_root / uf_link: skx_unionfind.h, shared with skx_mst.hip)
 
 __global__ void cluster_init_kernel(uint32_t *parent, int S)
 {

@@ -393,6 +393,102 @@ extern "C" int skx_array_distance_select_prefiltered(skx_array *a, int64_t const
     });
 }
 
+// ---- `ska distance --mst` (skx_array_distance_mst): the selection's planes and band loop, and after every band the kernels of skx_mst.hip on its
+// count buffer -- the forest of the bands so far stays on the device (two buffers of S records, labels, a word per component), a band merges its
+// candidates into it by Boruvka rounds, and after the last band at most S - 1 records come back, to be finished as the selection's are.
+// Between rounds the host reads one word back, the new forest's length: a round that adds nothing ends the band (and S - 1 records end it at
+// once), so a band costs one small copy and wait per round, at most ceil(log2 S) + 2 of them, against a sweep of band x S pairs.
+// prefiltered / min_freq: see entry_planes
+static int array_distance_mst(skx_array *a, const double *prefiltered, double min_freq, int filt_ambig, const skx_mst_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                              int64_t *constant, uint64_t *rows_used, skx_mst_info *info)
+{
+    if (!a || !spec || !pairs || !n_pairs) { set_error("distance mst: bad arguments"); return SKX_EINVAL; }
+    *pairs = nullptr; *n_pairs = 0;
+    if (constant) *constant = 0;
+    if (rows_used) *rows_used = 0;
+    if (info) *info = skx_mst_info{0, 0, 0, 0, 0, 0, 0};
+    const int S = (int)a->names.size();
+    if (std::isnan(spec->max_snps) || std::isnan(spec->max_mismatches)) { set_error("distance mst: a threshold is not a number"); return SKX_EINVAL; }
+    if (spec->max_mismatches > 1.0) { set_error("distance mst: max_mismatches is a proportion, at most 1"); return SKX_EINVAL; }
+    if (spec->band_rows < 0) { set_error("distance mst: band_rows must be zero (the engine's choice) or more"); return SKX_EINVAL; }
+    // an edge is ordered by (key, i, j) in one 64-bit word, 16 bits a sample
+    if (S > MST_MAX_SAMPLES) { set_error("distance mst: not available above %d samples (the array has %d)", MST_MAX_SAMPLES, S); return SKX_EUNSUP; }
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_HIP(hipSetDevice(ctx->device));
+    SKX_TRY(array_materialize(a));
+    if (S < 2) { if (info) info->components = (uint64_t)S; return SKX_OK; }
+    StageTimer t(ctx, &ctx->tm.distance);
+    SweepPlanes sp; uint64_t kept = 0; double n_const = 0;
+    SKX_TRY(entry_planes(a, prefiltered, min_freq, filt_ambig, nullptr, sp, n_const, kept));
+    if (constant) *constant = (int64_t)n_const;
+    if (rows_used) *rows_used = kept;
+    // the key, at most 36 per swept row, must stay below 2^32 (the rule of --closest)
+    if (kept >= (1ull << 32) / 36) { set_error("distance mst: not available above %llu rows", (1ull << 32) / 36); return SKX_EUNSUP; }
+    const SelCriteria crit{filt_ambig, n_const, spec->max_snps < 0.0 ? ~0ull : select_kmax(spec->max_snps, filt_ambig), spec->max_mismatches < 0.0 ? -1.0 : spec->max_mismatches};
+    const uint64_t band = banded_rows(spec->band_rows, S);
+    const uint64_t bands = ((uint64_t)S + band - 1) / band;
+    DevBuf<unsigned long long> cnt, words, best, d_cand; DevBuf<uint32_t> comp, parent, d_n; DevBuf<SelRecord> forest[2];
+    SKX_TRY(cnt.alloc(band * S * DIST_NCOUNT)); SKX_TRY(words.alloc(band * S));
+    SKX_TRY(best.alloc((uint64_t)S)); SKX_TRY(comp.alloc((uint64_t)S)); SKX_TRY(parent.alloc((uint64_t)S));
+    SKX_TRY(forest[0].alloc((uint64_t)S)); SKX_TRY(forest[1].alloc((uint64_t)S));
+    SKX_TRY(d_n.alloc(1)); SKX_TRY(d_cand.alloc(1)); SKX_TRY(d_cand.zero(st));
+    int max_rounds = 1;                                                          // ceil(log2 S) + 1: every round that chooses at least halves the trees that still have an edge out
+    while ((1ll << (max_rounds - 1)) < (long long)S) max_rounds++;
+    uint32_t n_forest = 0; int cur = 0; uint64_t most_rounds = 0;
+    SKX_TRY(for_each_band(ctx, sp.view(), S, filt_ambig, cnt, band, [&](int lo, int hi) -> int {
+        SelRecord *old_f = forest[cur].p, *new_f = forest[cur ^ 1].p;
+        launch_mst_begin(comp.p, parent.p, best.p, S, st);
+        launch_mst_gather(cnt.p, S, lo, hi, crit, words.p, d_cand.p, st);
+        SKX_TRY(d_n.zero(st));
+        uint32_t n_new = 0; uint64_t rounds = 0;
+        for (int r = 0; n_new < (uint32_t)S - 1; r++) {
+            if (r > max_rounds) { set_error("distance mst: a band took more than %d rounds", max_rounds); return SKX_ENODEV; }
+            launch_mst_round(words.p, S, lo, hi, old_f, n_forest, comp.p, best.p, parent.p, new_f, (uint32_t)S, d_n.p, st);
+            uint32_t n_now = 0;
+            SKX_HIP(hipMemcpyAsync(&n_now, d_n.p, 4, hipMemcpyDeviceToHost, st));
+            SKX_HIP(hipStreamSynchronize(st));
+            if (n_now > (uint32_t)S - 1) { set_error("distance mst: %u lines in a forest of %d samples", n_now, S); return SKX_ENODEV; }
+            if (n_now == n_new) break;                                           // no component has an edge out
+            n_new = n_now; rounds++;
+            launch_mst_relabel(comp.p, parent.p, best.p, S, st);
+        }
+        launch_mst_finish(cnt.p, S, lo, hi, filt_ambig, new_f, n_new, st);
+        n_forest = n_new; cur ^= 1;
+        most_rounds = std::max(most_rounds, rounds);
+        return SKX_OK;
+    }));
+    std::vector<SelRecord> rec(n_forest);
+    unsigned long long candidates = 0;
+    if (n_forest) SKX_HIP(hipMemcpyAsync(rec.data(), forest[cur].p, (size_t)n_forest * sizeof(SelRecord), hipMemcpyDeviceToHost, st));
+    SKX_HIP(hipMemcpyAsync(&candidates, d_cand.p, 8, hipMemcpyDeviceToHost, st));
+    SKX_HIP(hipStreamSynchronize(st));
+    SKX_HIP(hipGetLastError());
+    std::sort(rec.begin(), rec.end(), [](const SelRecord &x, const SelRecord &y) { return x.i != y.i ? x.i < y.i : x.j < y.j; });
+    skx_dist_pair *out = (skx_dist_pair *)malloc(std::max<size_t>(rec.size(), 1) * sizeof(skx_dist_pair));
+    if (!out) { set_error("out of host memory"); return SKX_ENOMEM; }
+    for (size_t n = 0; n < rec.size(); n++) {
+        out[n].i = rec[n].i; out[n].j = rec[n].j;
+        finish_counts(rec[n].mism, rec[n].m, rec[n].key, n_const, filt_ambig, out[n].d);
+    }
+    *pairs = out; *n_pairs = rec.size();
+    if (info) *info = skx_mst_info{bands, band, band * (uint64_t)S * DIST_NCOUNT * 8, candidates, (uint64_t)rec.size(), (uint64_t)S - rec.size(), most_rounds};
+    return SKX_OK;
+}
+extern "C" int skx_array_distance_mst(skx_array *a, double min_freq, int filt_ambig, const skx_mst_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                                      int64_t *constant, uint64_t *rows_used, skx_mst_info *info)
+{
+    return skx_guarded([&]() -> int { return array_distance_mst(a, nullptr, min_freq, filt_ambig, spec, pairs, n_pairs, constant, rows_used, info); });
+}
+extern "C" int skx_array_distance_mst_prefiltered(skx_array *a, int64_t constant, int filt_ambig, const skx_mst_spec *spec, skx_dist_pair **pairs, uint64_t *n_pairs,
+                                                  skx_mst_info *info)
+{
+    return skx_guarded([&]() -> int {
+    if (constant < 0) { set_error("distance mst: constant must be zero or more"); return SKX_EINVAL; }
+    const double c = (double)constant;
+    return array_distance_mst(a, &c, 0.0, filt_ambig, spec, pairs, n_pairs, nullptr, nullptr, info);
+    });
+}
+
 // ---- `ska distance --no-table` (skx_array_distance_banded): the selection's planes and band loop, and after every band the consumers of
 // skx_banded.hip on its count buffer -- the union-find of the clusters and the neighbour-joining matrix stay on the device from the first band
 // to the last, S labels and S - 1 join records come back.

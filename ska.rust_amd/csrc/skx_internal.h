@@ -407,6 +407,22 @@ void launch_cluster_union(const unsigned long long *cnt, int S, int i_lo, int i_
 void launch_cluster_labels(const uint32_t *parent, int S, uint32_t *label, unsigned long long *n_roots, hipStream_t st);
 // D[i][j] = D[j][i] = the distance of the pair's key (finish_counts' expression) for i in [i_lo, i_hi), j > i, in the pitched matrix nj_run takes
 void launch_dist_fill(const unsigned long long *cnt, int S, int i_lo, int i_hi, int filt_ambig, double *D, uint64_t pitch, hipStream_t st);
+// ---- the minimum spanning forest of `ska distance --mst` (skx_mst.hip; driver: array_distance_mst in skx_distance.cpp), over the same buffer.  Edges are
+// ordered by (key, i, j) as one word key << 32 | i << 16 | j: S <= MST_MAX_SAMPLES and key < 2^32 are the driver's to check
+constexpr int MST_MAX_SAMPLES = 65536;
+// a band's start: comp[x] = parent[x] = x, best[x] = no edge (each [S])
+void launch_mst_begin(uint32_t *comp, uint32_t *parent, unsigned long long *best, int S, hipStream_t st);
+// words[(i - i_lo) * S + j] (j > i) = the word of the pair if it passes c, else all ones; *n_candidates += how many pass
+void launch_mst_gather(const unsigned long long *cnt, int S, int i_lo, int i_hi, const SelCriteria &c, unsigned long long *words, unsigned long long *n_candidates,
+                       hipStream_t st);
+// one round over the forest's n_forest records and the band's words: every component's smallest outgoing edge into best[] (comp[]: the labels the
+// round starts with), then every edge that is the smallest of either end appended to out (cap records; *n_out counts on) and its trees joined in parent[]
+void launch_mst_round(const unsigned long long *words, int S, int i_lo, int i_hi, const SelRecord *forest, uint32_t n_forest, const uint32_t *comp, unsigned long long *best,
+                      uint32_t *parent, SelRecord *out, uint32_t cap, uint32_t *n_out, hipStream_t st);
+// after a round that chose something: comp[x] = the root of x in parent[], best[x] = no edge
+void launch_mst_relabel(uint32_t *comp, const uint32_t *parent, unsigned long long *best, int S, hipStream_t st);
+// a band's end: the records with i in [i_lo, i_hi) take mism, m and key from the band's counters
+void launch_mst_finish(const unsigned long long *cnt, int S, int i_lo, int i_hi, int filt_ambig, SelRecord *forest, uint32_t n_forest, hipStream_t st);
 // neighbour joining (skx_nj.hip) on a matrix that is on the device already: pitch = nj_pitch(S) doubles a row, zero diagonal and pad, symmetric
 uint64_t nj_pitch(uint64_t S);
 int nj_check_n(int n);

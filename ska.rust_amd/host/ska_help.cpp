@@ -76,7 +76,10 @@ const std::vector<Cmd> &commands()
           {"--query-skf", "<FILE>", "(MI355X engine) Merge this .skf into <SKF_FILE> in memory and print the lines that name one of its samples"},
           {"--max-snps", "<N>", "(MI355X engine) Print only the lines whose SNP distance is at most N"},
           {"--max-mismatches", "<P>", "(MI355X engine) Print only the lines whose mismatch proportion is at most P"},
-          {"--closest", "<K>", "(MI355X engine) Print only the lines that join a sample to one of its K closest (among the lines the two thresholds keep)"}}},
+          {"--closest", "<K>", "(MI355X engine) Print only the lines that join a sample to one of its K closest (among the lines the two thresholds keep)"},
+          {"--mst", "", "(MI355X engine) Print only the lines of the table's minimum spanning forest (among the lines --max-snps / --max-mismatches keep; ties by the line's place in the table)"},
+          {"--mst-clusters", "<PREFIX>", "(MI355X engine) With --mst: write every sample's cluster at each level of --levels, and their address, to <PREFIX>.levels.csv"},
+          {"--levels", "<L1,L2,...>", "(MI355X engine) SNP distances at which --mst-clusters cuts the forest (1 to 16 numbers, comma separated) [default: 250,100,50,25,10,5,0]"}}},
         {"merge", "Combine multiple split k-mer files", "ska merge -o <OUTPUT> [SKF_FILES]...",
          {{"[SKF_FILES]...", "", "List of input split-kmer (.skf) files"}},
          {{"-o", "<OUTPUT>", "Output prefix"}}},

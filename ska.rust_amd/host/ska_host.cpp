@@ -377,6 +377,43 @@ extern "C" int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, doubl
     });
 }
 
+// `ska distance --mst`: the forest's lines as text, and with levels (n_levels > 0) the ladder's CSV from the same forest
+static int distance_mst_run(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, const double *levels, int n_levels, char **buf,
+                            uint64_t *len, char **csv, uint64_t *csv_len)
+{
+    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
+    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
+    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
+    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
+    if (r != SKX_OK) return r;
+    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
+    skx_array_info_t info; skx_array_info(a, &info);
+    std::vector<const char *> names(info.n_samples);
+    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
+    skx_dist_pair *pairs = nullptr; uint64_t n = 0;
+    skx_mst_info mi{0, 0, 0, 0, 0, 0, 0};
+    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance_mst_prefiltered(a, constant, filt_ambig, spec, &pairs, &n, &mi)) != SKX_OK) return r; }
+    char msg[260];
+    snprintf(msg, sizeof msg, "Spanning forest of %llu lines in %llu trees from %llu candidate pairs: %llu bands of %llu samples, count buffer of %llu bytes, at most %llu rounds a band",
+             (unsigned long long)mi.edges, (unsigned long long)mi.components, (unsigned long long)mi.candidates, (unsigned long long)mi.bands, (unsigned long long)mi.band_rows,
+             (unsigned long long)mi.count_buffer_bytes, (unsigned long long)mi.rounds);
+    skh_log(2, "ska::generic_modes", msg);
+    r = distance_select_text(names, pairs, n, buf, len);
+    if (r == SKX_OK && n_levels > 0 && info.n_samples) {
+        r = skh_mst_levels_csv(names.data(), pairs, n, (int)info.n_samples, levels, n_levels, csv, csv_len);
+        if (r != SKX_OK) { skx_free(*buf); *buf = nullptr; }
+    }
+    skx_free(pairs);
+    return r;
+}
+extern "C" int skh_distance_mst_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, char **buf, uint64_t *len)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !skf_file || !spec || !buf || !len) { skx_set_error("skh_distance_mst_tsv: bad arguments"); return SKX_EINVAL; }
+    return distance_mst_run(ctx, skf_file, min_freq, filt_ambig, spec, nullptr, 0, buf, len, nullptr, nullptr);
+    });
+}
+
 // `ska distance --no-table`: the extras' files from the banded sweep (x names at least one).  What reaches the host is S labels and S - 1 joins
 extern "C" int skh_distance_banded_files(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *x)
 {
@@ -886,7 +923,7 @@ struct Args {
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
-                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest",
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels",
                             "--groups", "--min-group-size", "--samples", "--samples-file", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
@@ -1013,6 +1050,29 @@ skx_select_spec select_spec(const Args &a)
     if (a.has("--max-mismatches")) sp.max_mismatches = strtod(a.get("--max-mismatches").c_str(), nullptr);
     if (a.has("--closest")) sp.closest = (int32_t)std::min<unsigned long long>(strtoull(a.get("--closest").c_str(), nullptr, 10), INT32_MAX);
     return sp;
+}
+// --mst / --mst-clusters / --levels of `ska distance`: the table's minimum spanning forest (skx_array_distance_mst) and its clusters at a ladder of levels
+const char *MST_LEVELS_ARG = "--levels <L1,L2,...>", *MST_DEFAULT_LEVELS = "250,100,50,25,10,5,0";
+constexpr size_t MST_MAX_LEVELS = 16;
+bool lo_float(const std::string &v);                                              // (below: what Rust's float parser takes)
+// the comma-separated levels -> out; nullptr, or why the list does not stand (the values are checked by validate_cli before they are used)
+const char *parse_levels(const std::string &v, std::vector<double> &out)
+{
+    out.clear();
+    size_t at = 0;
+    for (;;) {
+        const size_t end = std::min(v.find(',', at), v.size());
+        const std::string t = v.substr(at, end - at);
+        if (t.empty()) return "cannot parse float from empty string";
+        if (!lo_float(t)) return "invalid float literal";
+        const double x = strtod(t.c_str(), nullptr);
+        if (!(x >= 0.0)) return "a level must be zero or more";
+        if (std::find(out.begin(), out.end(), x) != out.end()) return "a level is given twice";
+        out.push_back(x);
+        if (out.size() > MST_MAX_LEVELS) return "at most 16 levels";
+        if (end == v.size()) return nullptr;
+        at = end + 1;
+    }
 }
 int read_query_names(const Args &a, std::vector<std::string> &names)
 {
@@ -1351,6 +1411,10 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
                 fprintf(stderr, "error: the argument '--no-table' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
                 return 2;
             }
+        if (a.has("--mst")) {
+            fprintf(stderr, "error: the argument '--mst' cannot be used with '--no-table'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
+            return 2;
+        }
         if (!a.has("--tree") && !a.has("--clusters")) return clap_missing("distance", "<--tree <FILE>|--clusters <PREFIX>>");
     }
     if (cmd == "distance" && has_select(a)) {
@@ -1364,6 +1428,10 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
                     fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", q.arg, o.second, skh_usage_line("distance"));
                     return 2;
                 }
+        if (a.has("--closest") && a.has("--mst")) {                                              // (the forest takes the two thresholds only)
+            fprintf(stderr, "error: the argument '--closest <K>' cannot be used with '--mst'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
+            return 2;
+        }
         for (auto &q : SELECT_OPTS) {
             if (!a.has(q.flag)) continue;
             const std::string v = a.get(q.flag);
@@ -1378,6 +1446,24 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
             if (!strcmp(q.flag, "--max-snps")) { if (!(t >= 0.0)) return clap_invalid(v, q.arg, "must be zero or more"); }
             else if (!(t >= 0.0 && t <= 1.0)) return clap_invalid(v, q.arg, "Proportion must be between 0 and 1 (inclusive)");
         }
+    }
+    if (cmd == "distance" && (a.has("--mst") || a.has("--mst-clusters") || a.has("--levels"))) {
+        // the forest comes from one device's banded sweep, which forms neither the table nor what is cut from it: refused as clap refuses
+        // arguments that conflict (--mst is named when no other selection option is: those were refused above), a missing requirement, a bad value
+        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"},
+                                                                {"--cluster-mismatches", "--cluster-mismatches <P>"}, {"--gpus", "--gpus <GPUS>"}, {"--query", "--query <NAMES>"},
+                                                                {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
+        if (a.has("--mst"))
+            for (auto &o : others)
+                if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
+                    fprintf(stderr, "error: the argument '--mst' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
+                    return 2;
+                }
+        if (!a.has("--mst")) return clap_missing("distance", a.has("--levels") && !a.has("--mst-clusters") ? "--mst\n  --mst-clusters <PREFIX>" : "--mst");
+        if (a.has("--levels") && !a.has("--mst-clusters")) return clap_missing("distance", "--mst-clusters <PREFIX>");
+        if (a.has("--mst-clusters") && a.get("--mst-clusters").empty()) return clap_invalid("", "--mst-clusters <PREFIX>", "a value is required");
+        std::vector<double> lv;
+        if (a.has("--levels")) if (const char *why = parse_levels(a.get("--levels"), lv)) return clap_invalid(a.get("--levels"), MST_LEVELS_ARG, why);
     }
     if (cmd == "distance" && has_query(a)) {
         // the query is cut from one device's table, and the tree and the clusters need all of it: refused as clap refuses arguments that conflict
@@ -1486,7 +1572,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus --groups --min-group-size --samples --samples-file "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table --mst --mst-clusters --levels "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1602,6 +1688,20 @@ extern "C" int skh_main(int argc, char **argv)
         }
         else if (a.has("--no-table")) {
             if (skh_distance_banded_files(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get()) != SKX_OK) rcode = engine_fail();
+        }
+        else if (a.has("--mst")) {
+            const skx_select_spec ss = select_spec(a);
+            const skx_mst_spec sp{ss.max_snps, ss.max_mismatches, 0};
+            std::vector<double> lv;
+            if (a.has("--mst-clusters")) (void)parse_levels(a.get("--levels", MST_DEFAULT_LEVELS), lv);      // (validate_cli took the list)
+            char *csv = nullptr; uint64_t csv_len = 0;
+            const int r = skx_guarded([&]() -> int { return distance_mst_run(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), &sp, lv.data(), (int)lv.size(), &buf, &len, &csv, &csv_len); });
+            if (r != SKX_OK) rcode = engine_fail();
+            else {
+                rcode = emit(a.get("-o"), buf, len); skx_free(buf);
+                if (csv && !rcode && write_text_file(a.get("--mst-clusters") + ".levels.csv", csv, csv_len) != SKX_OK) rcode = engine_fail();
+                skx_free(csv);
+            }
         }
         else if (has_select(a)) {
             const skx_select_spec sp = select_spec(a);

@@ -149,6 +149,43 @@ extern "C" int skh_clusters_csv(const char *const *names, const uint32_t *labels
     return text_out(c, csv, csv_len);
 }
 
+extern "C" int skh_mst_levels_csv(const char *const *names, const skx_dist_pair *pairs, uint64_t n_pairs, int n_, const double *levels, int n_levels, char **buf, uint64_t *len)
+{
+    if (!names || (!pairs && n_pairs) || n_ < 1 || !levels || n_levels < 1 || !buf || !len) { skx_set_error("skh_mst_levels_csv: bad arguments"); return SKX_EINVAL; }
+    const uint32_t n = (uint32_t)n_;
+    for (uint64_t p = 0; p < n_pairs; p++)
+        if (pairs[p].i >= pairs[p].j || pairs[p].j >= n) { skx_set_error("skh_mst_levels_csv: line %llu does not join two of the %u samples", (unsigned long long)p, n); return SKX_EINVAL; }
+    // the values the table shows, as skh_distance_clusters reads them
+    std::vector<double> printed(n_pairs);
+    char tmp[512];
+    for (uint64_t p = 0; p < n_pairs; p++) { snprintf(tmp, sizeof tmp, "%.2f", pairs[p].d.distance); printed[p] = strtod(tmp, nullptr); }
+    std::vector<std::vector<uint32_t>> column((size_t)n_levels, std::vector<uint32_t>(n));
+    std::string c = "id";
+    for (int l = 0; l < n_levels; l++) {
+        snprintf(tmp, sizeof tmp, ",snps_%g", levels[l]); c += tmp;
+        std::vector<uint32_t> up(n), number(n, 0);
+        std::iota(up.begin(), up.end(), 0u);
+        auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
+        for (uint64_t p = 0; p < n_pairs; p++) {
+            if (!(printed[p] <= levels[l])) continue;
+            const uint32_t a = find(pairs[p].i), b = find(pairs[p].j);
+            if (a != b) up[std::max(a, b)] = std::min(a, b);       // the root of a cluster is its lowest sample
+        }
+        uint32_t next = 0;
+        for (uint32_t i = 0; i < n; i++) { const uint32_t r = find(i); if (r == i) number[i] = ++next; column[l][i] = number[r]; }      // (r <= i: numbered already)
+    }
+    c += ",address\n";
+    for (uint32_t i = 0; i < n; i++) {
+        const std::string s = names[i];
+        if (s.find_first_of(",\"\n\r") != std::string::npos) { c += '"'; for (char ch : s) { if (ch == '"') c += '"'; c += ch; } c += '"'; }
+        else c += s;
+        std::string address;
+        for (int l = 0; l < n_levels; l++) { const std::string v = std::to_string(column[l][i]); c += "," + v; address += (l ? "." : "") + v; }
+        c += "," + address + "\n";
+    }
+    return text_out(c, buf, len);
+}
+
 extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d, int n_, double max_snps, double max_mismatches,
                                      char **csv, uint64_t *csv_len, char **dot, uint64_t *dot_len)
 {

@@ -75,6 +75,20 @@ class SelectInfo(C.Structure):
     _fields_ = [("bands", C.c_uint64), ("band_rows", C.c_uint64), ("count_buffer_bytes", C.c_uint64), ("candidates", C.c_uint64)]
 
 
+class MstSpec(C.Structure):
+    """skx_mst_spec (include/skx.h): the thresholds of `ska distance --mst` (a negative one = not given) and the band of its sweep"""
+    _fields_ = [("max_snps", C.c_double), ("max_mismatches", C.c_double), ("band_rows", C.c_int32)]
+
+    @classmethod
+    def of(cls, max_snps=None, max_mismatches=None, band_rows=0):
+        return cls(-1.0 if max_snps is None else float(max_snps), -1.0 if max_mismatches is None else float(max_mismatches), int(band_rows))
+
+
+class MstInfo(C.Structure):
+    """skx_mst_info (include/skx.h)"""
+    _fields_ = [(f, C.c_uint64) for f in ("bands", "band_rows", "count_buffer_bytes", "candidates", "edges", "components", "rounds")]
+
+
 class BandedSpec(C.Structure):
     """skx_banded_spec (include/skx.h): the cluster thresholds of `ska distance --no-table --clusters` and the band of its sweep"""
     _fields_ = [("cluster_snps", C.c_double), ("cluster_mismatches", C.c_double), ("band_rows", C.c_int32)]
@@ -113,7 +127,8 @@ skx_dist_nj skx_matrix_nj skh_nj_newick skh_distance_clusters skh_distance_skf_t
 skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_tsv
 skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv
 skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files
-skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd""".split()
+skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd
+skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv""".split()
 
 _lib = None
 
@@ -154,6 +169,10 @@ def load_library():
     lib.skh_clusters_csv.argtypes = [C.POINTER(cp), vp, i, pp, C.POINTER(u64)]
     lib.skh_cluster_cutoffs.argtypes = [d, d, i, C.POINTER(u64), C.POINTER(d)]
     lib.skh_distance_banded_files.argtypes = [vp, cp, d, i, C.POINTER(DistExtras)]
+    lib.skx_array_distance_mst.argtypes = [vp, d, i, C.POINTER(MstSpec), pp, C.POINTER(u64), C.POINTER(C.c_int64), C.POINTER(u64), C.POINTER(MstInfo)]
+    lib.skx_array_distance_mst_prefiltered.argtypes = [vp, C.c_int64, i, C.POINTER(MstSpec), pp, C.POINTER(u64), C.POINTER(MstInfo)]
+    lib.skh_distance_mst_tsv.argtypes = [vp, cp, d, i, C.POINTER(MstSpec), pp, C.POINTER(u64)]
+    lib.skh_mst_levels_csv.argtypes = [C.POINTER(cp), vp, u64, i, vp, i, pp, C.POINTER(u64)]
     lib.skx_array_subset_filtered.argtypes = [vp, vp, i, C.POINTER(FilterSpec), pp, C.POINTER(SubsetInfo)]
     lib.skh_read_groups.argtypes = [cp, pp, C.POINTER(u64), C.POINTER(u64)]
     lib.skh_align_groups.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, cp, i, cp]
@@ -476,6 +495,13 @@ class Context:
         _check(_lib.skh_distance_select_tsv(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n)))
         return _take(p, n)
 
+    def distance_mst_tsv(self, skf_file, min_freq=0.0, filt_ambig=True, max_snps=None, max_mismatches=None, band_rows=0):
+        """`ska distance <skf> --mst [--max-snps N] [--max-mismatches P]` (skh_distance_mst_tsv) -> the header and the lines of the table's minimum spanning forest"""
+        spec = MstSpec.of(max_snps, max_mismatches, band_rows)
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.skh_distance_mst_tsv(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n)))
+        return _take(p, n)
+
     def distance_banded_files(self, skf_file, min_freq=0.0, filt_ambig=True, tree=None, clusters=None, cluster_snps=10.0, cluster_mismatches=1.0):
         """`ska distance <skf> --no-table [--tree FILE] [--clusters PREFIX ...]` (skh_distance_banded_files): the files, no table"""
         x = DistExtras(tree.encode() if tree else None, clusters.encode() if clusters else None, cluster_snps, cluster_mismatches)
@@ -554,6 +580,19 @@ def clusters_csv(names, labels):
     arr = (C.c_char_p * n)(*[x.encode() for x in names])
     p, ln = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_clusters_csv(arr, _np_ptr(lab), n, C.byref(p), C.byref(ln)))
+    return _take(p, ln).decode()
+
+
+def mst_levels_csv(names, pairs, levels):
+    """skh_mst_levels_csv: levels.csv text -- every sample's cluster at each level (the forest's lines whose printed distance is <= the level) and its
+    address; pairs as Array.distance_mst returns them (host only)"""
+    load_library()
+    n = len(names)
+    pr = np.ascontiguousarray(pairs, PAIR_DT)
+    lv = np.ascontiguousarray(levels, np.float64)
+    arr = (C.c_char_p * max(n, 1))(*[x.encode() for x in names])
+    p, ln = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_mst_levels_csv(arr, _np_ptr(pr) if pr.size else None, pr.size, n, _np_ptr(lv) if lv.size else None, lv.size, C.byref(p), C.byref(ln)))
     return _take(p, ln).decode()
 
 
@@ -1114,6 +1153,27 @@ class Array:
         if p:
             _lib.skx_free(p)
         return pairs, {f: getattr(info, f) for f, _ in SelectInfo._fields_}
+
+    def distance_mst(self, min_freq=0.0, filt_ambig=True, max_snps=None, max_mismatches=None, band_rows=0):
+        """skx_array_distance_mst: the lines of `distance_filtered`'s table that form its minimum spanning forest under the order (distance, i, j),
+        among the lines the thresholds keep, held on the device band by band -> (pairs (PAIR_DT, ascending (i, j)), constant sites, rows used, info dict)"""
+        spec = MstSpec.of(max_snps, max_mismatches, band_rows)
+        p, n, cst, rows, info = C.c_void_p(), C.c_uint64(), C.c_int64(), C.c_uint64(), MstInfo()
+        _check(_lib.skx_array_distance_mst(self.h, float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n), C.byref(cst), C.byref(rows), C.byref(info)))
+        pairs = np.frombuffer(C.string_at(p, n.value * PAIR_DT.itemsize), PAIR_DT).copy() if n.value else np.zeros(0, PAIR_DT)
+        if p:
+            _lib.skx_free(p)
+        return pairs, cst.value, rows.value, {f: getattr(info, f) for f, _ in MstInfo._fields_}
+
+    def distance_mst_prefiltered(self, constant=0, filt_ambig=True, max_snps=None, max_mismatches=None, band_rows=0):
+        """skx_array_distance_mst_prefiltered: the same of `distance`'s table (every row, `constant` added) -> (pairs, info dict)"""
+        spec = MstSpec.of(max_snps, max_mismatches, band_rows)
+        p, n, info = C.c_void_p(), C.c_uint64(), MstInfo()
+        _check(_lib.skx_array_distance_mst_prefiltered(self.h, int(constant), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n), C.byref(info)))
+        pairs = np.frombuffer(C.string_at(p, n.value * PAIR_DT.itemsize), PAIR_DT).copy() if n.value else np.zeros(0, PAIR_DT)
+        if p:
+            _lib.skx_free(p)
+        return pairs, {f: getattr(info, f) for f, _ in MstInfo._fields_}
 
     def _banded_outputs(self, labels, tree):
         s = self.nsamples
