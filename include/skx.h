@@ -441,6 +441,10 @@ int  skx_ctx_timings(skx_ctx *ctx, skx_timings *t, int reset);
  * unsorted regions, merge_ska_dict.rs:77-109, for u64 / u128 keys) or "sorted: <why the pass was not taken>" (per-sample sort +
  * union + assemble); "" before the first merge.  The reference has no counterpart: its append is one code path. */
 const char *skx_ctx_merge_path(skx_ctx *ctx);
+/* what the statistics pass of the last skx_array_filter on this context left unread: a filter at min_count >= 2 over an array still
+ * held as the merge's pieces counts only the first-seen ranks that enough samples reach (the rest cannot pass).  *ranks = ranks not
+ * read, *blocks = row blocks that had such ranks; both 0 when the pass was the full one.  The reference has no counterpart. */
+int  skx_ctx_filter_cut(skx_ctx *ctx, uint64_t *ranks, uint64_t *blocks);
 
 #ifdef __cplusplus
 }

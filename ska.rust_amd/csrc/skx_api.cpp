@@ -249,6 +249,32 @@ extern "C" int skx_ctx_sync(skx_ctx *c) { SKX_HIP(hipSetDevice(c->device)); SKX_
 extern "C" void *skx_ctx_stream(skx_ctx *c) { return (void *)c->stream; }
 uint64_t skx::next_object_id() { static std::atomic<uint64_t> n{0}; return ++n; }
 extern "C" const char *skx_ctx_merge_path(skx_ctx *c) { return c ? c->merge_path.c_str() : ""; }
+extern "C" int skx_ctx_filter_cut(skx_ctx *c, uint64_t *ranks, uint64_t *blocks)
+{
+    if (!c) { set_error("bad arguments"); return SKX_EINVAL; }
+    if (ranks) *ranks = c->cut_ranks;
+    if (blocks) *blocks = c->cut_blocks;
+    return SKX_OK;
+}
+// test hook (not declared in include/skx.h, like skx_debug_fastq_frame; tests/test_gpu_rank_cut.py binds it): pieces_cut_kernel alone -- out[j] = the
+// min_count-th largest of plen[j * n_samples .. + n_samples) (host arrays; values <= cap), 0 when min_count > n_samples
+extern "C" int skx_debug_pieces_cut(skx_ctx *ctx, const uint16_t *plen, int n_samples, int n_blocks, uint32_t cap, uint32_t min_count, uint32_t *out)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !plen || !out || n_samples < 1 || n_samples > 65535 || n_blocks < 1 || cap < 32u || cap % 32u || cap > 12032u) { set_error("bad arguments"); return SKX_EINVAL; }
+    SKX_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = (uint64_t)n_blocks * (uint64_t)n_samples;
+    DevBuf<uint16_t> d_pl; DevBuf<uint32_t> d_cut;
+    SKX_TRY(d_pl.alloc(n)); SKX_TRY(d_cut.alloc((size_t)n_blocks));
+    SKX_HIP(hipMemcpyAsync(d_pl.p, plen, n * 2, hipMemcpyHostToDevice, st));
+    launch_pieces_cut(d_pl.p, n_samples, cap, min_count, nullptr, nullptr, 0, n_blocks, d_cut.p, nullptr, st);
+    SKX_HIP(hipMemcpyAsync(out, d_cut.p, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, st));
+    SKX_HIP(hipStreamSynchronize(st));
+    SKX_HIP(hipGetLastError());
+    return SKX_OK;
+    });
+}
 extern "C" int skx_ctx_timings(skx_ctx *c, skx_timings *t, int reset)
 {
     return skx_guarded([&]() -> int {
@@ -1230,11 +1256,43 @@ extern "C" int skx_array_assemble_lazy(skx_ctx *ctx, skx_dictset *d, skx_keyset 
     return array_make_lazy(ctx, d, rows, names, out);
     });
 }
+// The statistics pass over an array's pieces.  min_count >= 2: the pass of a frequency filter at that count -- ranks that fewer samples reach
+// are not read and their rows leave with zeros (pieces_cut_kernel, pieces_stats_kernel), so the caller must NOT set stats_ready; 0: every rank.
+static int pieces_stats_pass(skx_array *a, uint64_t min_count)
+{
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    const skx_pieces *pc = a->pieces; const skx_keyset *blk = a->lazy_rows;
+    const int S = (int)a->names.size(), nb = 1 << pc->logQ;
+    ctx->cut_ranks = ctx->cut_blocks = 0;
+    if (!a->n_rows) return SKX_OK;
+    const uint32_t stage = min_count >= 2 ? pieces_stats_bound(pc->cap) : 0u;
+    DevBuf<uint32_t> r_cut; DevBuf<unsigned long long> tally;
+    if (stage) { SKX_TRY(r_cut.alloc((size_t)nb)); SKX_TRY(tally.alloc(2)); SKX_TRY(tally.zero(st)); }
+    unsigned long long h_tally[2] = {0, 0};
+    {
+        StageTimer t(ctx, &ctx->tm.assemble);
+        KernelTimer kt(ctx, &ctx->tm.pieces_stats);
+        if (stage) launch_pieces_cut(pc->plen.p, S, pc->cap, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFEull), pc->nrank.p, blk->ncnt.p, stage, nb, r_cut.p, tally.p, st);
+        launch_pieces_stats(pc->data.p, pc->plen.p, pc->perm.p, pc->nrank.p, blk->ncnt.p, blk->roff.p, pc->cap, S, nb, a->present.p, a->unambig.p, a->mask.p, a->vcount.p, st,
+                            stage ? r_cut.p : nullptr);
+        if (stage) SKX_HIP(hipMemcpyAsync(h_tally, tally.p, 16, hipMemcpyDeviceToHost, st));
+    }
+    SKX_HIP(hipStreamSynchronize(st));                                 // (h_tally, r_cut)
+    SKX_HIP(hipGetLastError());
+    ctx->cut_ranks = h_tally[0]; ctx->cut_blocks = h_tally[1];
+    if (stage && getenv("SKX_DEBUG")) fprintf(stderr, "[skx] filter: min_count %llu, the rank bound left %llu ranks unread over %llu of %d row blocks\n", (unsigned long long)min_count, h_tally[0], h_tally[1], nb);
+    return SKX_OK;
+}
 int skx::array_lazy_stats(skx_array *a)
 {
     if (!a->lazy() || a->stats_ready) return SKX_OK;
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     SKX_HIP(hipSetDevice(ctx->device));
+    if (a->pieces) {                                                   // an append pass's own rows: counted from the pieces, every rank
+        SKX_TRY(pieces_stats_pass(a, 0));
+        a->stats_ready = true;
+        return SKX_OK;
+    }
     DevBuf<int> d_flag; SKX_TRY(d_flag.alloc(1)); SKX_TRY(d_flag.zero(st));
     if (a->n_rows) {
         AssembleArgs aa = lazy_args(a, d_flag.p);
@@ -1250,6 +1308,7 @@ int skx::array_materialize(skx_array *a)
     if (!a->lazy()) return SKX_OK;
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     SKX_HIP(hipSetDevice(ctx->device));
+    if (a->pieces) SKX_TRY(array_lazy_stats(a));                       // (the pieces are dropped below: the statistics are counted from them first)
     const uint64_t U = a->n_rows; const size_t S = a->names.size();
     a->pitch = pitch_for(U);
     SKX_TRY(a->matrix.alloc((uint64_t)S * a->pitch));
@@ -1463,7 +1522,12 @@ static int array_over_pieces(skx_ctx *ctx, const skx_dictset *d, skx_keyset *ks,
         if (src->wide) launch_gather_keys_wide((const u128 *)src->stage.p, src->stride, g ? g->ncnt.p : blk->ncnt.p, g ? g->roff.p : blk->roff.p, 1 << src->logN, (u128 *)a->keys.p, st);
         else launch_gather_keys(src->stage.p, src->stride, g ? g->ncnt.p : blk->ncnt.p, g ? g->roff.p : blk->roff.p, 1 << src->logN, a->keys.p, 0, src->hp, st);
         if (g) { SKX_TRY(a->present.zero(st)); SKX_TRY(a->unambig.zero(st)); SKX_TRY(a->mask.zero(st)); SKX_TRY(a->vcount.zero(st)); }
-        // the rows' statistics, counted from the pieces
+    }
+    // the rows' statistics, counted from the pieces: at once for a sharded job's rows (skx_array_reduce_stats reads every row next) and with
+    // SKX_KNOBS=stats_eager (the A/B, the differential tests); a pass's own rows get them when first asked for -- `ska align` filters next, and
+    // its pass reads only the ranks that can reach min_count (array_lazy_stats, skx_array_filter)
+    if (!g && !knob("stats_eager")) a->stats_ready = false;
+    else if (U) {
         StageTimer t(ctx, &ctx->tm.assemble);
         KernelTimer kt(ctx, &ctx->tm.pieces_stats);
         launch_pieces_stats(pc->data.p, pc->plen.p, pc->perm.p, pc->nrank.p, blk->ncnt.p, blk->roff.p, pc->cap, S, 1 << logQ, a->present.p, a->unambig.p, a->mask.p, a->vcount.p, st);
@@ -1813,6 +1877,7 @@ static int array_compact(skx_array *a, DevBuf<uint8_t> &keep, DevBuf<uint64_t> &
     const uint64_t U = a->n_rows; const size_t S = a->names.size();
     const bool filter_ambig_as_missing = vcount_from_unambig;
     if (kept == U && !mask_ambig) {                 // nothing goes: no 2 x U x S bytes of traffic, no second matrix
+        a->stats_ready = true;                      // (every row kept: every row was counted, also by a filter's bounded pass)
         if (filter_ambig_as_missing && U) SKX_HIP(hipMemcpyAsync(a->vcount.p, a->unambig.p, U * 4, hipMemcpyDeviceToDevice, st));
         SKX_HIP(hipStreamSynchronize(st));
         return SKX_OK;
@@ -1825,7 +1890,7 @@ static int array_compact(skx_array *a, DevBuf<uint8_t> &keep, DevBuf<uint64_t> &
         if (a->pieces) {
             // the kept rows straight from the pieces: the unfiltered rows x samples matrix is never written
             PiecesRowsArgs pa = pieces_args(a);
-            pa.out = nm.p; pa.pitch = np; pa.keep = keep.p; pa.kpos = pos.p; pa.mask_ambig = mask_ambig;
+            pa.out = nm.p; pa.pitch = np; pa.keep = keep.p; pa.kpos = pos.p; pa.mask_ambig = mask_ambig; pa.full_pieces = knob("stats_eager") ? 1 : 0;
             KernelTimer kt(ctx, &ctx->tm.pieces_rows);
             launch_pieces_rows(pa, 1u << a->pieces->logQ, st);
         } else if (a->lazy()) {
@@ -1837,11 +1902,12 @@ static int array_compact(skx_array *a, DevBuf<uint8_t> &keep, DevBuf<uint64_t> &
             SKX_TRY(lazy_check_missing(a, d_flag));
         } else
             launch_compact_matrix(a->matrix.p, a->pitch, nm.p, np, (int)S, U, keep.p, pos.p, mask_ambig, st);
-        launch_compact_u32(a->present.p, p2.p, U, keep.p, pos.p, st);
-        launch_compact_u32(a->unambig.p, u2.p, U, keep.p, pos.p, st);
-        launch_compact_u32(a->mask.p, m2.p, U, keep.p, pos.p, st);
-        // update_counts(true) rewrites variant_count with the unambiguous counts (merge_ska_array.rs:139-163)
-        launch_compact_u32(filter_ambig_as_missing ? a->unambig.p : a->vcount.p, v2.p, U, keep.p, pos.p, st);
+        {   // the four statistics in one pass over keep / pos
+            // update_counts(true) rewrites variant_count with the unambiguous counts (merge_ska_array.rs:139-163)
+            const uint32_t *const in[4] = {a->present.p, a->unambig.p, a->mask.p, filter_ambig_as_missing ? a->unambig.p : a->vcount.p};
+            uint32_t *const out[4] = {p2.p, u2.p, m2.p, v2.p};
+            launch_compact_stats(in, out, U, keep.p, pos.p, st);
+        }
         if (mask_ambig) launch_mask_ambig_stats(m2.p, kept, st);
         // update_counts(true) (merge_ska_array.rs:139-163) rewrites counts AND split_kmers whenever it ran
         if (a->n_kmers == U && keys_follow) {
@@ -1867,6 +1933,7 @@ static int array_compact(skx_array *a, DevBuf<uint8_t> &keep, DevBuf<uint64_t> &
         a->matrix = std::move(nm); a->present = std::move(p2); a->unambig = std::move(u2); a->mask = std::move(m2); a->vcount = std::move(v2);
         a->pitch = np; a->n_rows = kept;
         a->drop_lazy();
+        a->stats_ready = true;                      // (kept rows: counted in full, also by a filter's bounded pass -- skx_array_filter)
     }
     return SKX_OK;
 }
@@ -1878,7 +1945,15 @@ extern "C" int skx_array_filter(skx_array *a, uint64_t min_count, int filter_amb
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     SKX_HIP(hipSetDevice(ctx->device));
     const uint64_t U = a->n_rows; const size_t S = a->names.size();
-    SKX_TRY(array_lazy_stats(a));
+    // An array still over its pieces, not yet counted: the pass counts only the first-seen ranks that min_count samples reach.  The rows of
+    // the others come out with count 0 < min_count and go; the rows that stay are counted in full, and the compaction below leaves only
+    // them.  Not with filter_ambig_as_missing (the silent rows, keep == 2, are told by the unambiguous count of EVERY row, and `removed`
+    // depends on them), not below min_count 2 (a zero count would pass), not for a sharded job's slab (its counts are the job's, not its own).
+    ctx->cut_ranks = ctx->cut_blocks = 0;
+    if (a->pieces && !a->stats_ready && !filter_ambig_as_missing && min_count >= 2 && a->total_samples == 0 && !knob("stats_eager"))
+        SKX_TRY(pieces_stats_pass(a, min_count));                      // (stats_ready stays false until the compaction has dropped the uncounted rows)
+    else
+        SKX_TRY(array_lazy_stats(a));
     DevBuf<uint8_t> keep; DevBuf<uint64_t> pos;
     SKX_TRY(keep.alloc(U)); SKX_TRY(pos.alloc(U + 1));
     uint64_t kept = 0, silent = 0;

@@ -603,6 +603,59 @@ void launch_append(const AppendArgs &a, uint32_t region_cap, hipStream_t st) { (
 void launch_append_probe(const AppendArgs &a, uint32_t region_cap, unsigned blocks, hipStream_t st) { (void)region_cap; launch_append_t<true>(a, blocks, st); }
 
 // ------------------------------------------------------------------------------------------------
+// The rank bound of a frequency filter.  Pieces are indexed by first-seen rank and a sample's piece holds exactly plen ranks, so rank r of row
+// block j has a cell in at most #{ s : plen[j][s] > r } samples.  r_cut[j] = the min_count-th largest of plen[j][0..S) (0 when min_count > S)
+// is the smallest r at which that number falls below min_count: no rank at or beyond it can reach min_count, whatever its cells hold, and
+// every row a filter at min_count keeps has a rank below it.  One workgroup per row block: a histogram of the lengths (<= cap) in LDS, the
+// threads' shares of it summed, the share that holds the answer walked down from its top.
+// `stage` (with ncnt): a block with more rows than the statistics pass stages is not bounded there (0xFFFFFFFF); tally[0] += the ranks
+// whose 16-byte columns the bounded pass leaves unread, tally[1] += the blocks that have such ranks.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pieces_cut_kernel(const uint16_t *plen, int S, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt,
+                                                         uint32_t stage, uint32_t *r_cut, unsigned long long *tally)
+{
+    extern __shared__ uint32_t s_hist[];                              // [cap + 1]
+    __shared__ uint32_t s_sum[256];
+    __shared__ uint32_t s_cut;
+    const uint64_t j = blockIdx.x;
+    const uint32_t tid = threadIdx.x, nbin = cap + 1u, share = (nbin + 255u) / 256u;
+    for (uint32_t i = tid; i < nbin; i += 256) s_hist[i] = 0;
+    if (tid == 0) s_cut = 0;                                          // (min_count > S, or no sample: nothing can pass)
+    __syncthreads();
+    const uint16_t *pl = plen + j * (uint64_t)S;
+    for (int s = (int)tid; s < S; s += 256) { const uint32_t v = pl[s]; atomicAdd(&s_hist[v < cap ? v : cap], 1u); }
+    __syncthreads();
+    const uint32_t b0 = tid * share, b1 = b0 + share < nbin ? b0 + share : nbin;
+    uint32_t own = 0;
+    for (uint32_t b = b0; b < b1; b++) own += s_hist[b];
+    s_sum[tid] = own;
+    __syncthreads();
+    uint32_t above = 0;                                               // samples with a length beyond this thread's share
+    for (uint32_t t = tid + 1; t < 256; t++) above += s_sum[t];
+    if (min_count >= 1u && above < min_count && min_count <= above + own) {      // the one share that holds the min_count-th largest
+        uint32_t acc = above;
+        for (uint32_t b = b1; b-- > b0;) { acc += s_hist[b]; if (acc >= min_count) { s_cut = b; break; } }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t rc = min_count ? s_cut : 0xFFFFFFFFu;                // (min_count 0: every rank passes the count test)
+        if (ncnt && ncnt[j] > stage) rc = 0xFFFFFFFFu;
+        r_cut[j] = rc;
+        if (tally && nrank) {
+            const uint32_t nr = nrank[j], lim = nr < rc ? nr : rc;
+            const uint64_t seen = (uint64_t)((lim + 31u) / 32u) * 32u;
+            if (seen < nr) { atomicAdd(&tally[0], (unsigned long long)(nr - seen)); atomicAdd(&tally[1], 1ull); }
+        }
+    }
+}
+void launch_pieces_cut(const uint16_t *plen, int n_samples, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt, uint32_t stage, int n_blocks,
+                       uint32_t *r_cut, unsigned long long *tally, hipStream_t st)
+{
+    if (n_blocks <= 0) return;
+    hipLaunchKernelGGL(pieces_cut_kernel, dim3((unsigned)n_blocks), dim3(256), ((size_t)cap + 1) * 4, st, plen, n_samples, cap, min_count, nrank, ncnt, stage, r_cut, tally);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Row statistics from the finished pieces: per first-seen rank of a row block the number of samples with a cell (present), with an
 // unambiguous one, and the set of IUPAC codes that occur (merge_ska_array.rs:139-186 counts the same from the rows).  A thread owns one
 // 16-byte column of the block's pieces -- 32 ranks, 4 bits each -- and walks the samples: nibble-parallel counters (a byte per rank, folded
@@ -614,12 +667,15 @@ void launch_append_probe(const AppendArgs &a, uint32_t region_cap, unsigned bloc
 // this kernel writes (round 5 stored them from the ranks' threads, 4 bytes at a time through perm: 3.5 GB of write traffic for 0.36 GB of
 // results, profiles/r05_final_pmc_traffic.txt).  A block with more rows than the stage holds (global rows of a sharded job over unrelated
 // samples) or split over several workgroups (never at the append pass's capacities) stores per rank as before.
+// r_cut (optional; pieces_cut_kernel): the pass of a frequency filter.  Only the columns that start below min(nrank, r_cut[j]) are read and
+// only their ranks walked; the block's other rows leave with present = unambiguous = code set = 0, which the filter's count test drops.  This
+// rests on the staged form's zero fill: the launcher does not bound a launch that stores per rank, and pieces_cut_kernel not a block that would.
 // ------------------------------------------------------------------------------------------------
 // (the stage is as large as the launch's piece capacity -- a pass's own rows: nrows <= nrank <= cap -- so that 3 072-rank blocks of 128-bit keys
 // keep their occupancy: a fixed 36 KB cost the k = 41 form more than the stores had, profiles/r05v_ab_stats_staged.log)
 __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt,
                                                            const uint64_t *roff, uint32_t cap, int S, uint32_t *o_present, uint32_t *o_unambig, uint32_t *o_mask,
-                                                           uint32_t *o_vcount, int force_direct, uint32_t stage)
+                                                           uint32_t *o_vcount, int force_direct, uint32_t stage, const uint32_t *r_cut)
 {
     constexpr int W = 4;                                              // dwords per thread: one 16-byte load per sample (append_kernel writes the pieces 16 bytes -- 32 ranks -- at a time,
                                                                       // so such a piece of a sample's piece is either written whole or not at all)
@@ -640,7 +696,11 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     const uint16_t *pl = plen + j * (uint64_t)S;
     const uint4 *col = reinterpret_cast<const uint4 *>(pieces + j * (uint64_t)S * (cap / 2)) + d;
     const uint32_t step = cap / 32;                                   // 16-byte pieces from one sample's piece to the next
-    const bool mine = d * 32u < nr;
+    uint32_t lim = nr;                                                // ranks that need statistics: columns that start at or beyond it are not read
+    if (r_cut && staged) { const uint32_t rc = r_cut[j]; if (rc < lim) lim = rc; }
+    const uint32_t nseen = (lim + 31u) / 32u * 32u < nr ? (lim + 31u) / 32u * 32u : nr;      // the ranks of the columns read
+    const bool mine = d * 32u < lim;
+    const bool wave_has = (d - (uint32_t)(threadIdx.x & 63)) * 32u < lim;                    // (a wave whose 64 columns all lie beyond: no walk over the samples)
     uint32_t pN[W], aN[W];                                            // nibble counters (a rank each): present / ambiguous cells, folded into the byte counters every 12 samples
     uint32_t pE[W], pO[W], aE[W], aO[W], uni[W];                      // byte counters: present / ambiguous cells of the even and odd ranks; OR of the cells
     uint32_t PE0[W], PE1[W], PO0[W], PO1[W], AE0[W], AE1[W], AO0[W], AO1[W];      // the same, 16 bits per rank
@@ -673,7 +733,7 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     };
     // 64 samples at a time: their piece lengths arrive as one vector load (a lane each) and are handed round with v_readlane; four 16-byte loads in
     // flight per lane (a dword per lane and load made 27 M small requests of this pass: 2.7 ms); the byte counters are folded every 192 samples
-    for (int s0 = 0, since = 0, nib = 0; s0 < S; s0 += 64) {
+    for (int s0 = 0, since = 0, nib = 0; wave_has && s0 < S; s0 += 64) {
         const uint32_t plv = s0 + lane < S ? (uint32_t)pl[s0 + lane] : 0u;
         const int n = S - s0 < 64 ? S - s0 : 64;
 #pragma unroll 1
@@ -727,7 +787,7 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     if (!staged) __threadfence();                                      // (the walk below reads what the ranks' threads stored)
     __syncthreads();
     // rows with an ambiguous cell: their code sets cell by cell, a wave per row, found by a walk over the workgroup's ranks (64 at a time)
-    const uint32_t rk0 = blockIdx.y * 256u * 8u * W, rk1 = rk0 + 256u * 8u * W < nr ? rk0 + 256u * 8u * W : nr;
+    const uint32_t rk0 = blockIdx.y * 256u * 8u * W, rk1 = rk0 + 256u * 8u * W < nseen ? rk0 + 256u * 8u * W : nseen;
     for (uint32_t rb = rk0 + (uint32_t)wv * 64u; rb < rk1; rb += 256u) {
         const uint32_t rr = rb + (uint32_t)lane;
         uint32_t pp = 0xFFFFu; bool hit = false;
@@ -763,16 +823,27 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
         o_unambig[r0 + p] = s_un[p]; o_mask[r0 + p] = s_mk[p];
     }
 }
+// how a statistics launch at this piece capacity runs: the one place that decides it, for the launcher and for who bounds it
+namespace {
+struct StatsLaunch { unsigned gy; int direct; uint32_t stage; bool bounded() const { return gy == 1 && !direct; } };
+StatsLaunch stats_launch(uint32_t cap)
+{
+    static const int direct = knob("stats_direct") ? 1 : 0;           // (tests: the per-rank stores of blocks the stage does not hold)
+    // stage: <= 6 016 (12 032 with gy > 1, where nothing is staged): <= 36 KB
+    return {(cap / 32 + 255u) / 256u, direct, (cap + 63u) / 64u * 64u};
+}
+}
 void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt, const uint64_t *roff, uint32_t cap,
-                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st)
+                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, const uint32_t *r_cut)
 {
     if (n_blocks <= 0) return;
-    const unsigned gy = (cap / 32 + 255u) / 256u;
-    static const int direct = knob("stats_direct") ? 1 : 0;           // (tests: the per-rank stores of blocks the stage does not hold)
-    const uint32_t stage = (cap + 63u) / 64u * 64u;                    // <= 6 016 (12 032 with gy > 1, where nothing is staged): <= 36 KB
-    hipLaunchKernelGGL(pieces_stats_kernel, dim3((unsigned)n_blocks, gy), dim3(256), (size_t)stage * 6, st, pieces, plen, perm, nrank, ncnt, roff, cap, n_samples, present, unambig, mask, vcount,
-                       direct, stage);
+    const StatsLaunch l = stats_launch(cap);
+    if (!l.bounded()) r_cut = nullptr;                                 // (per-rank stores fill no zeros: such a launch is never bounded)
+    hipLaunchKernelGGL(pieces_stats_kernel, dim3((unsigned)n_blocks, l.gy), dim3(256), (size_t)l.stage * 6, st, pieces, plen, perm, nrank, ncnt, roff, cap, n_samples, present, unambig, mask, vcount,
+                       l.direct, l.stage, r_cut);
 }
+// the rows a bounded pass may stage per block (what pieces_cut_kernel is told), 0: a launch at this capacity stores per rank and is not bounded
+uint32_t pieces_stats_bound(uint32_t cap) { const StatsLaunch l = stats_launch(cap); return l.bounded() ? l.stage : 0u; }
 // split k-mers per sample (SkaDict::ksize): the cells of its pieces that are not empty; a wave per piece
 __global__ __launch_bounds__(256) void pieces_cells_kernel(const uint8_t *pieces, const uint16_t *plen, uint32_t cap, int S, unsigned long long *out)
 {
@@ -854,14 +925,19 @@ __global__ __launch_bounds__(64 * PR_WAVES) void pieces_rows_kernel(PiecesRowsAr
     const int s_lo = blockIdx.y * a.samples_per_wg, s_hi = s_lo + a.samples_per_wg < S ? s_lo + a.samples_per_wg : S;
     uint32_t *pc = s_piece + (size_t)wv * (cap / 8 + 4);
     const unsigned char *pcb = reinterpret_cast<const unsigned char *>(pc);
-    const uint32_t nrw = (nr + 7u) / 8u;                                      // piece words that ranks of this block can name
+    // piece words that this pass's columns can name: all the block's ranks, or (kept rows) up to the largest rank listed -- the rows a
+    // frequency filter keeps were first seen in the early samples, so their ranks end well before the block's (full = the former: the A/B)
+    __shared__ uint32_t s_top;
+    uint32_t nrw = (nr + 7u) / 8u;
     if (lane < 4) pc[cap / 8 + lane] = 0u;                                    // (rank `cap`: no cell)
     // The block's output columns are taken `cap` at a time (one pass when they are the block's own rows; the rows of a sharded job's hash
     // range -- all ranks' rows, most of them without a cell here -- may be several times as many).  sc = shift + column: the index into the
     // aligned dwords.
     for (uint32_t t0 = 0; t0 < nout + shift; t0 += cap) {
         for (uint32_t i = tid; i < cap + 16u; i += blockDim.x) s_src[i] = (uint16_t)cap;
+        if (KEPT && tid == 0) s_top = 0;
         __syncthreads();
+        uint32_t top = 0;                                                     // 1 + the largest rank this thread listed
         for (uint32_t r = tid; r < nr; r += blockDim.x) {
             const uint32_t p = pj[r];
             if (p == 0xFFFFu || p >= n) continue;
@@ -869,9 +945,11 @@ __global__ __launch_bounds__(64 * PR_WAVES) void pieces_rows_kernel(PiecesRowsAr
             if (!KEPT) sc = shift + p;
             else if (a.keep[r0 + p] == 1) sc = shift + (uint32_t)(a.kpos[r0 + p] - k0);
             else continue;
-            if (sc >= t0 && sc < t0 + cap) s_src[sc - t0] = (uint16_t)r;
+            if (sc >= t0 && sc < t0 + cap) { s_src[sc - t0] = (uint16_t)r; top = r + 1u; }
         }
+        if (KEPT && top) atomicMax(&s_top, top);
         __syncthreads();
+        if (KEPT && !a.full_pieces) nrw = (s_top + 7u) / 8u;
         const uint32_t v_lo = t0 / 4u, v_hi = (t0 + cap) / 4u < ndw ? (t0 + cap) / 4u : ndw;      // this pass's dwords
         for (int s = s_lo + wv; s < s_hi; s += PR_WAVES) {
             const uint32_t pl = a.plen[j * (uint64_t)S + s];

@@ -183,7 +183,13 @@ void launch_append_wide(const AppendArgs &a, hipStream_t st);
 void launch_append_wide_probe(const AppendArgs &a, unsigned blocks, hipStream_t st);
 // row statistics from the pieces (present, unambiguous, code set, variant_count), written to the rows in the order of H
 void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt, const uint64_t *roff, uint32_t cap,
-                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st);
+                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, const uint32_t *r_cut = nullptr);
+// r_cut[j] = the min_count-th largest piece length of row block j (0: min_count > samples): no rank at or beyond it can reach min_count.
+// ncnt / stage (pieces_stats_bound; ncnt may be null): blocks the bounded statistics pass would not stage get 0xFFFFFFFF; tally (optional, zeroed):
+// [0] += ranks in 16-byte columns the bounded pass leaves unread, [1] += blocks with any
+void launch_pieces_cut(const uint16_t *plen, int n_samples, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt, uint32_t stage, int n_blocks,
+                       uint32_t *r_cut, unsigned long long *tally, hipStream_t st);
+uint32_t pieces_stats_bound(uint32_t cap);                               // rows per block the statistics pass stages; 0: launches at this capacity are not bounded
 void launch_pieces_cells(const uint8_t *pieces, const uint16_t *plen, uint32_t cap, int n_samples, int n_blocks, unsigned long long *out, hipStream_t st);
 void launch_region_totals(const uint32_t *raw, int n_samples, int logB, unsigned long long *out, hipStream_t st);
 struct PiecesRowsArgs {
@@ -193,6 +199,7 @@ struct PiecesRowsArgs {
     uint32_t j_base = 0; uint64_t col_base = 0;                          // all rows: block j's rows land at columns roff[j] - col_base
     const uint8_t *keep = nullptr; const uint64_t *kpos = nullptr;        // kept rows only: row r (keep[r] == 1) lands at column kpos[r]
     int mask_ambig = 0;                                                  // ambiguous cells are written as 'N'
+    int full_pieces = 0;                                                 // kept rows: copy a piece up to the block's last rank, not the last kept one (SKX_KNOBS=stats_eager)
     int samples_per_wg = 0;                                              // (set by the launcher)
 };
 void launch_pieces_rows(const PiecesRowsArgs &a, uint32_t n_blocks, hipStream_t st);      // blocks [j_base, j_base + n_blocks)
@@ -231,6 +238,8 @@ void launch_compact_matrix(const uint8_t *in, uint64_t in_pitch, uint8_t *out, u
 void launch_subset_verdicts(const uint8_t *matrix, uint64_t pitch, const int *order, int n, uint64_t n_cols, uint64_t min_count, int ambig_as_missing,
                             int filter_type, int ignore_const_gaps, uint8_t *keep, unsigned long long *counts, int *bad_byte, hipStream_t st);
 void launch_compact_u32(const uint32_t *in, uint32_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
+// the four row statistics of an array in one pass over keep / pos
+void launch_compact_stats(const uint32_t *const in[4], uint32_t *const out[4], uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
 void launch_compact_u64(const uint64_t *in, uint64_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
 void launch_compact_u128(const uint64_t *in, uint64_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st);
 void launch_mask_ambig_stats(uint32_t *mask, uint64_t n, hipStream_t st);

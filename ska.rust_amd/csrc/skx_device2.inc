@@ -239,6 +239,24 @@ void launch_compact_u32(const uint32_t *in, uint32_t *out, uint64_t n, const uin
     uint64_t g = (n + 255) / 256; if (g > 8192) g = 8192;
     hipLaunchKernelGGL(compact_vec_kernel<uint32_t>, dim3((unsigned)g), dim3(256), 0, st, in, out, n, keep, pos);
 }
+struct CompactStats { const uint32_t *in[4]; uint32_t *out[4]; };
+__global__ void compact_stats_kernel(CompactStats a, uint64_t n, const uint8_t *keep, const uint64_t *pos)
+{
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (uint64_t)gridDim.x * blockDim.x)
+        if (keep[c] == 1) {
+            const uint64_t o = pos[c];
+#pragma unroll
+            for (int i = 0; i < 4; i++) a.out[i][o] = a.in[i][c];
+        }
+}
+void launch_compact_stats(const uint32_t *const in[4], uint32_t *const out[4], uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st)
+{
+    if (!n) return;
+    CompactStats a;
+    for (int i = 0; i < 4; i++) { a.in[i] = in[i]; a.out[i] = out[i]; }
+    uint64_t g = (n + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(compact_stats_kernel, dim3((unsigned)g), dim3(256), 0, st, a, n, keep, pos);
+}
 void launch_compact_u64(const uint64_t *in, uint64_t *out, uint64_t n, const uint8_t *keep, const uint64_t *pos, hipStream_t st)
 {
     if (!n) return;

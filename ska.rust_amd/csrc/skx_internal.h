@@ -87,6 +87,7 @@ struct skx_ctx {
     skx_timings tm{};
     bool timing = true;
     std::string merge_path;          // which kernels the last merge on this context went through, and why (skx_ctx_merge_path)
+    uint64_t cut_ranks = 0, cut_blocks = 0;   // the last filter's statistics pass: ranks it left unread under the rank bound, row blocks with any (skx_ctx_filter_cut)
 };
 
 namespace skx {
@@ -194,7 +195,9 @@ struct skx_array {
     // assembled; the dictionaries and the row keyset are kept instead.  `ska build` streams such an array into its .skf window
     // by window and `ska align *.fa` filters it before any cell is written, so neither ever holds the unfiltered matrix;
     // every other operation assembles it first (skx::array_materialize).
-    // Or (arrays merged by the append pass): the pieces and the row blocks (lazy_rows: ncnt / roff), statistics ready.
+    // Or (arrays merged by the append pass): the pieces and the row blocks (lazy_rows: ncnt / roff).  A sharded job's array has its statistics
+    // from the start; a pass's own gets them when first asked for (array_lazy_stats) -- or never in full: a frequency filter counts only the
+    // ranks that can reach its min_count (skx_array_filter).  Until stats_ready the four arrays hold nothing a reader may use.
     skx_dictset *lazy_dict = nullptr; skx_keyset *lazy_rows = nullptr; skx_pieces *pieces = nullptr;
     bool stats_ready = true;         // present / unambig / mask / vcount filled (lazy arrays get them from a statistics-only pass)
     bool lazy() const { return lazy_dict != nullptr || pieces != nullptr; }
@@ -437,7 +440,8 @@ bool mappable_output_fd(int fd, off_t *pos);                         // regular 
 int array_wide_words(skx_array *a, DevBuf<uint64_t> &tmp, const u128 **words);   // k > 31: the rows' packed 128-bit words on the device (tmp backs them for loaded arrays)
 int array_host_keys(skx_array *a, std::vector<skx_key> &hk);         // the array's split k-mers as the reference stores them, in row order
 int array_materialize(skx_array *a);                                 // a lazily held array gets its matrix (no-op otherwise)
-int array_lazy_stats(skx_array *a);                                  // a lazily held array gets its per-row statistics
+int array_lazy_stats(skx_array *a);                                  // a lazily held array gets its per-row statistics: the gate every reader of present / unambig / mask / vcount
+                                                                     // passes first, directly or through array_materialize
 // rows [r0, r0 + nr) of a lazily held array as a sample-major window: cell (s, r) at win + s * wpitch + (r - r0)
 int array_lazy_window(skx_array *a, uint64_t r0, uint64_t nr, DevBuf<uint8_t> &buf, const uint8_t **win, uint64_t *wpitch);
 inline uint64_t pitch_for(uint64_t cols) { return ((cols + 255) / 256) * 256 + 256; }

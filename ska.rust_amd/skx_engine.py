@@ -128,7 +128,8 @@ skx_array_distance_query skx_array_distance_query_filtered skh_distance_query_ts
 skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_select_tsv
 skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files
 skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd
-skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv""".split()
+skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv
+skx_ctx_filter_cut""".split()
 
 _lib = None
 
@@ -184,6 +185,7 @@ def load_library():
     lib.skx_ctx_timings.argtypes = [vp, C.POINTER(Timings), i]
     lib.skx_ctx_merge_path.argtypes = [vp]
     lib.skx_ctx_merge_path.restype = C.c_char_p
+    lib.skx_ctx_filter_cut.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     lib.skx_dictset_build.argtypes = [vp, C.POINTER(Stream), i, i, i, i, C.POINTER(Qual), pp]
     lib.skx_dictset_build_files.argtypes = [vp, C.POINTER(cp), C.POINTER(cp), i, i, i, C.POINTER(Qual), i, d, pp]
     lib.skx_dictset_free.argtypes = [vp]
@@ -445,6 +447,12 @@ class Context:
     def merge_path(self):
         """'append64' / 'append128' / 'sorted: <why>': the kernels the last merge on this context went through"""
         return _lib.skx_ctx_merge_path(self.h).decode()
+
+    def filter_cut(self):
+        """(ranks, row blocks): what the statistics pass of the last filter on this context left unread under its rank bound -- (0, 0): the full pass"""
+        r, b = C.c_uint64(0), C.c_uint64(0)
+        _check(_lib.skx_ctx_filter_cut(self.h, C.byref(r), C.byref(b)))
+        return int(r.value), int(b.value)
 
     def lo_graph(self, array):
         """skx_array_lo_graph: `ska lo`'s coloured de Bruijn graph of `array` (a device Array on this context)"""
