@@ -256,7 +256,7 @@ extern "C" int skx_ctx_filter_cut(skx_ctx *c, uint64_t *ranks, uint64_t *blocks)
     if (blocks) *blocks = c->cut_blocks;
     return SKX_OK;
 }
-// test hook (not declared in include/skx.h, like skx_debug_fastq_frame; tests/test_gpu_rank_cut.py binds it): pieces_cut_kernel alone -- out[j] = the
+// test hook (not declared in include/skx.h, like skx_debug_fastq_frame; tests bind it): pieces_cut_kernel alone (the filter takes the cut inside its statistics pass) -- out[j] = the
 // min_count-th largest of plen[j * n_samples .. + n_samples) (host arrays; values <= cap), 0 when min_count > n_samples
 extern "C" int skx_debug_pieces_cut(skx_ctx *ctx, const uint16_t *plen, int n_samples, int n_blocks, uint32_t cap, uint32_t min_count, uint32_t *out)
 {
@@ -1257,30 +1257,25 @@ extern "C" int skx_array_assemble_lazy(skx_ctx *ctx, skx_dictset *d, skx_keyset 
     });
 }
 // The statistics pass over an array's pieces.  min_count >= 2: the pass of a frequency filter at that count -- ranks that fewer samples reach
-// are not read and their rows leave with zeros (pieces_cut_kernel, pieces_stats_kernel), so the caller must NOT set stats_ready; 0: every rank.
-static int pieces_stats_pass(skx_array *a, uint64_t min_count)
+// are not read and their rows leave with zeros (pieces_stats_kernel), so the caller must NOT set stats_ready; it gives `tally` (two words,
+// alive until its own synchronise), which receives what skx_ctx_filter_cut reports, and the pass does not wait.  0: every rank, finished on return.
+static int pieces_stats_pass(skx_array *a, uint64_t min_count, DevBuf<unsigned long long> *tally = nullptr)
 {
     skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
     const skx_pieces *pc = a->pieces; const skx_keyset *blk = a->lazy_rows;
     const int S = (int)a->names.size(), nb = 1 << pc->logQ;
     ctx->cut_ranks = ctx->cut_blocks = 0;
     if (!a->n_rows) return SKX_OK;
-    const uint32_t stage = min_count >= 2 ? pieces_stats_bound(pc->cap) : 0u;
-    DevBuf<uint32_t> r_cut; DevBuf<unsigned long long> tally;
-    if (stage) { SKX_TRY(r_cut.alloc((size_t)nb)); SKX_TRY(tally.alloc(2)); SKX_TRY(tally.zero(st)); }
-    unsigned long long h_tally[2] = {0, 0};
+    const bool bounded = min_count >= 2 && tally && pieces_stats_bound(pc->cap);
+    if (bounded) { SKX_TRY(tally->alloc(2)); SKX_TRY(tally->zero(st)); }
     {
         StageTimer t(ctx, &ctx->tm.assemble);
         KernelTimer kt(ctx, &ctx->tm.pieces_stats);
-        if (stage) launch_pieces_cut(pc->plen.p, S, pc->cap, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFEull), pc->nrank.p, blk->ncnt.p, stage, nb, r_cut.p, tally.p, st);
         launch_pieces_stats(pc->data.p, pc->plen.p, pc->perm.p, pc->nrank.p, blk->ncnt.p, blk->roff.p, pc->cap, S, nb, a->present.p, a->unambig.p, a->mask.p, a->vcount.p, st,
-                            stage ? r_cut.p : nullptr);
-        if (stage) SKX_HIP(hipMemcpyAsync(h_tally, tally.p, 16, hipMemcpyDeviceToHost, st));
+                            bounded ? (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFEull) : 0u, bounded ? tally->p : nullptr);
     }
-    SKX_HIP(hipStreamSynchronize(st));                                 // (h_tally, r_cut)
+    if (!bounded) SKX_HIP(hipStreamSynchronize(st));
     SKX_HIP(hipGetLastError());
-    ctx->cut_ranks = h_tally[0]; ctx->cut_blocks = h_tally[1];
-    if (stage && getenv("SKX_DEBUG")) fprintf(stderr, "[skx] filter: min_count %llu, the rank bound left %llu ranks unread over %llu of %d row blocks\n", (unsigned long long)min_count, h_tally[0], h_tally[1], nb);
     return SKX_OK;
 }
 int skx::array_lazy_stats(skx_array *a)
@@ -1950,8 +1945,10 @@ extern "C" int skx_array_filter(skx_array *a, uint64_t min_count, int filter_amb
     // them.  Not with filter_ambig_as_missing (the silent rows, keep == 2, are told by the unambiguous count of EVERY row, and `removed`
     // depends on them), not below min_count 2 (a zero count would pass), not for a sharded job's slab (its counts are the job's, not its own).
     ctx->cut_ranks = ctx->cut_blocks = 0;
+    DevBuf<unsigned long long> tally;                                  // (the bounded pass's: read back with `kept` below)
+    unsigned long long h_tally[2] = {0, 0};
     if (a->pieces && !a->stats_ready && !filter_ambig_as_missing && min_count >= 2 && a->total_samples == 0 && !knob("stats_eager"))
-        SKX_TRY(pieces_stats_pass(a, min_count));                      // (stats_ready stays false until the compaction has dropped the uncounted rows)
+        SKX_TRY(pieces_stats_pass(a, min_count, &tally));              // (stats_ready stays false until the compaction has dropped the uncounted rows)
     else
         SKX_TRY(array_lazy_stats(a));
     DevBuf<uint8_t> keep; DevBuf<uint64_t> pos;
@@ -1965,6 +1962,7 @@ extern "C" int skx_array_filter(skx_array *a, uint64_t min_count, int filter_amb
         SKX_TRY(sc_sums.alloc(scan_u8_blocks(U))); SKX_TRY(sc_offs.alloc(scan_u8_blocks(U) + 1));
         launch_scan_u8(keep.p, pos.p, U, sc_sums.p, sc_offs.p, st);
         SKX_HIP(hipMemcpyAsync(&kept, pos.p + U, 8, hipMemcpyDeviceToHost, st));
+        if (tally.p) SKX_HIP(hipMemcpyAsync(h_tally, tally.p, 16, hipMemcpyDeviceToHost, st));
         if (filter_ambig_as_missing) {
             DevBuf<unsigned long long> d_sil; SKX_TRY(d_sil.alloc(1)); SKX_TRY(d_sil.zero(st));
             launch_count_u8(keep.p, U, 2, d_sil.p, st);
@@ -1975,6 +1973,8 @@ extern "C" int skx_array_filter(skx_array *a, uint64_t min_count, int filter_amb
         }
         SKX_HIP(hipStreamSynchronize(st));
     }
+    ctx->cut_ranks = h_tally[0]; ctx->cut_blocks = h_tally[1];
+    if (tally.p && getenv("SKX_DEBUG")) fprintf(stderr, "[skx] filter: min_count %llu, the rank bound left %llu ranks unread over %llu of %d row blocks\n", (unsigned long long)min_count, h_tally[0], h_tally[1], 1 << a->pieces->logQ);
     SKX_TRY(array_compact(a, keep, pos, kept, mask_ambig, filter_ambig_as_missing != 0, update_kmers || filter_ambig_as_missing));
     SKX_HIP(hipGetLastError());
     if (removed) *removed = (int32_t)(U - kept - silent);

@@ -604,48 +604,62 @@ void launch_append_probe(const AppendArgs &a, uint32_t region_cap, unsigned bloc
 
 // ------------------------------------------------------------------------------------------------
 // The rank bound of a frequency filter.  Pieces are indexed by first-seen rank and a sample's piece holds exactly plen ranks, so rank r of row
-// block j has a cell in at most #{ s : plen[j][s] > r } samples.  r_cut[j] = the min_count-th largest of plen[j][0..S) (0 when min_count > S)
-// is the smallest r at which that number falls below min_count: no rank at or beyond it can reach min_count, whatever its cells hold, and
-// every row a filter at min_count keeps has a rank below it.  One workgroup per row block: a histogram of the lengths (<= cap) in LDS, the
-// threads' shares of it summed, the share that holds the answer walked down from its top.
-// `stage` (with ncnt): a block with more rows than the statistics pass stages is not bounded there (0xFFFFFFFF); tally[0] += the ranks
-// whose 16-byte columns the bounded pass leaves unread, tally[1] += the blocks that have such ranks.
+// block j has a cell in at most #{ s : plen[j][s] > r } samples.  The cut of block j = the min_count-th largest of plen[j][0..S) (0 when
+// min_count > S) is the smallest r at which that number falls below min_count: no rank at or beyond it can reach min_count, whatever its
+// cells hold, and every row a filter at min_count keeps has a rank below it.
+// pieces_cut_block: a workgroup of 256 threads over one block's lengths -- a histogram of the lengths (<= cap) in LDS, a suffix scan of the
+// threads' shares of it (within a wave by shuffles, the four waves' totals through LDS), the one share that holds the answer walked down
+// from its top.  Returns the cut to every thread; s_hist ([cap + 1]) is free again when it returns.
+// pieces_cut_tally: tally[0] += the ranks whose 16-byte columns a pass bounded at `rc` leaves unread, tally[1] += the blocks that have such ranks.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pieces_cut_kernel(const uint16_t *plen, int S, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt,
-                                                         uint32_t stage, uint32_t *r_cut, unsigned long long *tally)
+__device__ static inline uint32_t pieces_cut_block(const uint16_t *pl, int S, uint32_t cap, uint32_t min_count, uint32_t *s_hist)
 {
-    extern __shared__ uint32_t s_hist[];                              // [cap + 1]
-    __shared__ uint32_t s_sum[256];
+    __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_cut;
-    const uint64_t j = blockIdx.x;
-    const uint32_t tid = threadIdx.x, nbin = cap + 1u, share = (nbin + 255u) / 256u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, nbin = cap + 1u, share = (nbin + 255u) / 256u;
     for (uint32_t i = tid; i < nbin; i += 256) s_hist[i] = 0;
     if (tid == 0) s_cut = 0;                                          // (min_count > S, or no sample: nothing can pass)
     __syncthreads();
-    const uint16_t *pl = plen + j * (uint64_t)S;
     for (int s = (int)tid; s < S; s += 256) { const uint32_t v = pl[s]; atomicAdd(&s_hist[v < cap ? v : cap], 1u); }
     __syncthreads();
-    const uint32_t b0 = tid * share, b1 = b0 + share < nbin ? b0 + share : nbin;
+    const uint32_t b0 = tid * share < nbin ? tid * share : nbin, b1 = b0 + share < nbin ? b0 + share : nbin;
     uint32_t own = 0;
     for (uint32_t b = b0; b < b1; b++) own += s_hist[b];
-    s_sum[tid] = own;
+    uint32_t incl = own;                                              // this share and the shares above it in the wave
+#pragma unroll
+    for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o = (uint32_t)__shfl_down((int)incl, dd, 64); if (lane + (uint32_t)dd < 64u) incl += o; }
+    if (lane == 0) s_wave[wv] = incl;
     __syncthreads();
-    uint32_t above = 0;                                               // samples with a length beyond this thread's share
-    for (uint32_t t = tid + 1; t < 256; t++) above += s_sum[t];
+    uint32_t above = incl - own;                                      // samples with a length beyond this thread's share
+    for (uint32_t w = wv + 1; w < 4; w++) above += s_wave[w];
     if (min_count >= 1u && above < min_count && min_count <= above + own) {      // the one share that holds the min_count-th largest
         uint32_t acc = above;
         for (uint32_t b = b1; b-- > b0;) { acc += s_hist[b]; if (acc >= min_count) { s_cut = b; break; } }
     }
     __syncthreads();
-    if (tid == 0) {
-        uint32_t rc = min_count ? s_cut : 0xFFFFFFFFu;                // (min_count 0: every rank passes the count test)
+    const uint32_t rc = s_cut;
+    __syncthreads();                                                  // (s_cut and s_hist may be written again)
+    return rc;
+}
+__device__ static inline void pieces_cut_tally(uint32_t nr, uint32_t rc, unsigned long long *tally)
+{
+    const uint32_t lim = nr < rc ? nr : rc;
+    const uint64_t seen = (uint64_t)((lim + 31u) / 32u) * 32u;
+    if (seen < nr) { atomicAdd(&tally[0], (unsigned long long)(nr - seen)); atomicAdd(&tally[1], 1ull); }
+}
+// the cut alone (skx_debug_pieces_cut; the filter's pass takes it inside pieces_stats_kernel): r_cut[j], 0xFFFFFFFF for min_count 0 (every rank
+// passes the count test) and, with `stage` and ncnt, for a block with more rows than the statistics pass stages (not bounded there)
+__global__ __launch_bounds__(256) void pieces_cut_kernel(const uint16_t *plen, int S, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt,
+                                                         uint32_t stage, uint32_t *r_cut, unsigned long long *tally)
+{
+    extern __shared__ uint32_t s_hist[];                              // [cap + 1]
+    const uint64_t j = blockIdx.x;
+    const uint32_t cut = pieces_cut_block(plen + j * (uint64_t)S, S, cap, min_count, s_hist);
+    if (threadIdx.x == 0) {
+        uint32_t rc = min_count ? cut : 0xFFFFFFFFu;
         if (ncnt && ncnt[j] > stage) rc = 0xFFFFFFFFu;
         r_cut[j] = rc;
-        if (tally && nrank) {
-            const uint32_t nr = nrank[j], lim = nr < rc ? nr : rc;
-            const uint64_t seen = (uint64_t)((lim + 31u) / 32u) * 32u;
-            if (seen < nr) { atomicAdd(&tally[0], (unsigned long long)(nr - seen)); atomicAdd(&tally[1], 1ull); }
-        }
+        if (tally && nrank) pieces_cut_tally(nrank[j], rc, tally);
     }
 }
 void launch_pieces_cut(const uint16_t *plen, int n_samples, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt, uint32_t stage, int n_blocks,
@@ -667,15 +681,19 @@ void launch_pieces_cut(const uint16_t *plen, int n_samples, uint32_t cap, uint32
 // this kernel writes (round 5 stored them from the ranks' threads, 4 bytes at a time through perm: 3.5 GB of write traffic for 0.36 GB of
 // results, profiles/r05_final_pmc_traffic.txt).  A block with more rows than the stage holds (global rows of a sharded job over unrelated
 // samples) or split over several workgroups (never at the append pass's capacities) stores per rank as before.
-// r_cut (optional; pieces_cut_kernel): the pass of a frequency filter.  Only the columns that start below min(nrank, r_cut[j]) are read and
-// only their ranks walked; the block's other rows leave with present = unambiguous = code set = 0, which the filter's count test drops.  This
-// rests on the staged form's zero fill: the launcher does not bound a launch that stores per rank, and pieces_cut_kernel not a block that would.
+// min_count >= 1 (with tally): the pass of a frequency filter.  A staged workgroup takes its block's cut first (pieces_cut_block, the histogram
+// in the stage's bytes).  Only the columns that start below min(nrank, cut) are read and only their ranks walked; the block's other rows leave
+// with present = unambiguous = code set = 0, which the filter's count test drops.  This rests on the staged form's zero fill: the launcher does
+// not bound a launch that stores per rank, nor the kernel a block that would.
+// Sample slices: a staged workgroup whose columns fill G < 4 waves gives the other waves samples instead -- wave w takes column group w % G and
+// slice w / G of P = 4 / G (a power of two, and no more than the exchange below has room for); slice p walks the 64-sample groups p, p + P, ...
+// The slices' 16-bit counters and cell ORs are summed pairwise through the stage's bytes (before its zero fill) into slice 0, which stages them.
 // ------------------------------------------------------------------------------------------------
 // (the stage is as large as the launch's piece capacity -- a pass's own rows: nrows <= nrank <= cap -- so that 3 072-rank blocks of 128-bit keys
 // keep their occupancy: a fixed 36 KB cost the k = 41 form more than the stores had, profiles/r05v_ab_stats_staged.log)
 __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt,
                                                            const uint64_t *roff, uint32_t cap, int S, uint32_t *o_present, uint32_t *o_unambig, uint32_t *o_mask,
-                                                           uint32_t *o_vcount, int force_direct, uint32_t stage, const uint32_t *r_cut)
+                                                           uint32_t *o_vcount, int force_direct, uint32_t stage, uint32_t min_count, unsigned long long *tally)
 {
     constexpr int W = 4;                                              // dwords per thread: one 16-byte load per sample (append_kernel writes the pieces 16 bytes -- 32 ranks -- at a time,
                                                                       // so such a piece of a sample's piece is either written whole or not at all)
@@ -685,22 +703,30 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     const uint64_t j = blockIdx.x;
     const uint32_t nr = nrank[j], nrows = ncnt[j];
     const uint64_t r0 = roff[j];
-    const uint32_t d = blockIdx.y * 256u + threadIdx.x;              // 16-byte column: ranks 32 d .. 32 d + 31
     if (blockIdx.y * 256u * 8u * W >= nr && !(blockIdx.y == 0 && nrows)) return;
     const bool staged = gridDim.y == 1 && nrows <= PS_STAGE && !force_direct;
-    if (staged) {
-        for (uint32_t p = threadIdx.x; p < nrows; p += 256) { s_pr[p] = 0; s_un[p] = 0; s_mk[p] = 0; }      // (a row without a rank here: no cell in these samples)
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave: the same in every lane)
     const uint16_t *pl = plen + j * (uint64_t)S;
+    uint32_t lim = nr;                                                // ranks that need statistics: columns that start at or beyond it are not read
+    if (min_count && staged) {                                        // (the stage holds cap + 1 dwords: launch_pieces_stats)
+        const uint32_t rc = pieces_cut_block(pl, S, cap, min_count, reinterpret_cast<uint32_t *>(s_stage));
+        if (threadIdx.x == 0 && tally) pieces_cut_tally(nr, rc, tally);
+        if (rc < lim) lim = rc;
+    }
+    const uint32_t nseen = (lim + 31u) / 32u * 32u < nr ? (lim + 31u) / 32u * 32u : nr;      // the ranks of the columns read
+    // column groups of 64 and sample slices (staged only; per-rank stores keep a column per thread and one slice)
+    const uint32_t ncol = (lim + 31u) / 32u, ncg = ncol < 64u ? ncol : 64u;                   // columns read; the most that one group holds
+    uint32_t G = 4, P = 1;
+    if (staged && ncol) {
+        G = (ncol + 63u) / 64u;
+        for (P = 4u / G; P > 1u && (P / 2u) * G * 36u * 4u * ncg > PS_STAGE * 6u; P >>= 1) { }      // (4 / G is 4, 2 or 1; the exchange: P / 2 x G areas)
+    }
+    const uint32_t grp = (uint32_t)wv % G, slice = (uint32_t)wv / G;
+    const uint32_t d = blockIdx.y * 256u + grp * 64u + (uint32_t)lane;            // 16-byte column: ranks 32 d .. 32 d + 31
     const uint4 *col = reinterpret_cast<const uint4 *>(pieces + j * (uint64_t)S * (cap / 2)) + d;
     const uint32_t step = cap / 32;                                   // 16-byte pieces from one sample's piece to the next
-    uint32_t lim = nr;                                                // ranks that need statistics: columns that start at or beyond it are not read
-    if (r_cut && staged) { const uint32_t rc = r_cut[j]; if (rc < lim) lim = rc; }
-    const uint32_t nseen = (lim + 31u) / 32u * 32u < nr ? (lim + 31u) / 32u * 32u : nr;      // the ranks of the columns read
-    const bool mine = d * 32u < lim;
-    const bool wave_has = (d - (uint32_t)(threadIdx.x & 63)) * 32u < lim;                    // (a wave whose 64 columns all lie beyond: no walk over the samples)
+    bool mine = slice < P && d * 32u < lim;
+    const bool wave_has = slice < P && (d - (uint32_t)lane) * 32u < lim;          // (a wave without columns or a slice: no walk over the samples)
     uint32_t pN[W], aN[W];                                            // nibble counters (a rank each): present / ambiguous cells, folded into the byte counters every 12 samples
     uint32_t pE[W], pO[W], aE[W], aO[W], uni[W];                      // byte counters: present / ambiguous cells of the even and odd ranks; OR of the cells
     uint32_t PE0[W], PE1[W], PO0[W], PO1[W], AE0[W], AE1[W], AO0[W], AO1[W];      // the same, 16 bits per rank
@@ -733,7 +759,7 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     };
     // 64 samples at a time: their piece lengths arrive as one vector load (a lane each) and are handed round with v_readlane; four 16-byte loads in
     // flight per lane (a dword per lane and load made 27 M small requests of this pass: 2.7 ms); the byte counters are folded every 192 samples
-    for (int s0 = 0, since = 0, nib = 0; wave_has && s0 < S; s0 += 64) {
+    for (int s0 = (int)slice * 64, since = 0, nib = 0; wave_has && s0 < S; s0 += 64 * (int)P) {
         const uint32_t plv = s0 + lane < S ? (uint32_t)pl[s0 + lane] : 0u;
         const int n = S - s0 < 64 ? S - s0 : 64;
 #pragma unroll 1
@@ -754,6 +780,37 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
         if (since >= 192) { fold(); since = 0; nib = 0; }
     }
     fold();
+    // the slices' results into slice 0: halves in turn, the upper half's 36 dwords a column through LDS ([area][dword][column of the group])
+    if (P > 1u) {
+        uint32_t *const xch = reinterpret_cast<uint32_t *>(s_stage);
+        for (uint32_t half = P >> 1; half >= 1u; half >>= 1) {
+            if (mine && slice >= half && slice < 2u * half) {
+                uint32_t *const xa = xch + ((size_t)((slice - half) * G + grp) * 36u) * ncg + (uint32_t)lane;
+#pragma unroll
+                for (int w = 0; w < W; w++) {
+                    uint32_t *q = xa + (size_t)w * 9u * ncg;
+                    q[0] = PE0[w]; q[ncg] = PE1[w]; q[2 * ncg] = PO0[w]; q[3 * ncg] = PO1[w]; q[4 * ncg] = AE0[w]; q[5 * ncg] = AE1[w]; q[6 * ncg] = AO0[w]; q[7 * ncg] = AO1[w];
+                    q[8 * ncg] = uni[w];
+                }
+            }
+            __syncthreads();
+            if (mine && slice < half) {                               // (16 bits a rank: the sum over all slices is at most S <= 65 535)
+                const uint32_t *const xb = xch + ((size_t)(slice * G + grp) * 36u) * ncg + (uint32_t)lane;
+#pragma unroll
+                for (int w = 0; w < W; w++) {
+                    const uint32_t *q = xb + (size_t)w * 9u * ncg;
+                    PE0[w] += q[0]; PE1[w] += q[ncg]; PO0[w] += q[2 * ncg]; PO1[w] += q[3 * ncg]; AE0[w] += q[4 * ncg]; AE1[w] += q[5 * ncg]; AO0[w] += q[6 * ncg]; AO1[w] += q[7 * ncg];
+                    uni[w] |= q[8 * ncg];
+                }
+            }
+            __syncthreads();
+        }
+        if (slice) mine = false;
+    }
+    if (staged) {
+        for (uint32_t p = threadIdx.x; p < nrows; p += 256) { s_pr[p] = 0; s_un[p] = 0; s_mk[p] = 0; }      // (a row without a rank here: no cell in these samples)
+        __syncthreads();
+    }
     const uint16_t *pj = perm + j * (uint64_t)cap;
     if (mine) {
 #pragma unroll
@@ -834,15 +891,16 @@ StatsLaunch stats_launch(uint32_t cap)
 }
 }
 void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt, const uint64_t *roff, uint32_t cap,
-                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, const uint32_t *r_cut)
+                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, uint32_t min_count, unsigned long long *tally)
 {
     if (n_blocks <= 0) return;
     const StatsLaunch l = stats_launch(cap);
-    if (!l.bounded()) r_cut = nullptr;                                 // (per-rank stores fill no zeros: such a launch is never bounded)
+    if (!l.bounded()) min_count = 0;                                   // (per-rank stores fill no zeros: such a launch is never bounded)
+    // (the stage's bytes take the cut's histogram first: (cap + 1) * 4 <= stage * 6 for every cap >= 2)
     hipLaunchKernelGGL(pieces_stats_kernel, dim3((unsigned)n_blocks, l.gy), dim3(256), (size_t)l.stage * 6, st, pieces, plen, perm, nrank, ncnt, roff, cap, n_samples, present, unambig, mask, vcount,
-                       l.direct, l.stage, r_cut);
+                       l.direct, l.stage, min_count, tally);
 }
-// the rows a bounded pass may stage per block (what pieces_cut_kernel is told), 0: a launch at this capacity stores per rank and is not bounded
+// the rows a bounded pass may stage per block, 0: a launch at this capacity stores per rank and is not bounded
 uint32_t pieces_stats_bound(uint32_t cap) { const StatsLaunch l = stats_launch(cap); return l.bounded() ? l.stage : 0u; }
 // split k-mers per sample (SkaDict::ksize): the cells of its pieces that are not empty; a wave per piece
 __global__ __launch_bounds__(256) void pieces_cells_kernel(const uint8_t *pieces, const uint16_t *plen, uint32_t cap, int S, unsigned long long *out)
@@ -890,6 +948,7 @@ void launch_region_totals(const uint32_t *raw, int n_samples, int logB, unsigned
 // (IUPAC letter of the 4-bit base set; '-' where the rank lies beyond the piece), stored at its own alignment so that a wave writes whole lines.
 // ------------------------------------------------------------------------------------------------
 constexpr int PR_WAVES = 8;
+constexpr int PR_AHEAD = 3;                                              // 16-byte loads per lane that a wave keeps on the way for its next sample
 // 4 base sets (a byte each) -> their IUPAC letters: two byte permutes over "-ACMTWYH" / "GRSVKDBN" and a select on bit 3
 __device__ static inline uint32_t ap_iupac4(uint32_t m)
 {
@@ -951,23 +1010,46 @@ __global__ __launch_bounds__(64 * PR_WAVES) void pieces_rows_kernel(PiecesRowsAr
         __syncthreads();
         if (KEPT && !a.full_pieces) nrw = (s_top + 7u) / 8u;
         const uint32_t v_lo = t0 / 4u, v_hi = (t0 + cap) / 4u < ndw ? (t0 + cap) / 4u : ndw;      // this pass's dwords
-        for (int s = s_lo + wv; s < s_hi; s += PR_WAVES) {
-            const uint32_t pl = a.plen[j * (uint64_t)S + s];
-            const uint32_t plw = (pl + 7u) / 8u;
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(a.pieces + (j * (uint64_t)S + s) * (cap / 2));
-            {   // sixteen bytes per lane and step (the pieces and the wave's buffer are 16-byte aligned: cap is a multiple of 128); a dword per
-                // lane made this copy a quarter of the kernel's time (3.95 -> 3.10 ms for the kept rows of 1 000 x 5 Mbp)
-                const uint4 *src4 = reinterpret_cast<const uint4 *>(src);
-                uint4 *pc4 = reinterpret_cast<uint4 *>(pc);
-                for (uint32_t i = lane; i < (nrw + 3u) / 4u; i += 64) {
-                    uint4 x = 4u * i < plw ? src4[i] : make_uint4(0u, 0u, 0u, 0u);      // ranks handed out after this sample: no cell
-                    if (4u * i + 1u >= plw) x.y = 0u;
-                    if (4u * i + 2u >= plw) x.z = 0u;
-                    if (4u * i + 3u >= plw) x.w = 0u;
-                    pc4[i] = x;
-                }
+        // A wave's samples s_lo + wv + PR_WAVES i, i < cnt.  Their piece lengths arrive 64 at a time (a lane each) and are handed round with
+        // v_readlane; the piece of sample i + 1 is asked for -- sixteen bytes per lane and load, up to PR_AHEAD loads: 192 x 16 B holds a piece
+        // of 6 016 ranks -- before the cells of sample i are produced, and goes to the wave's buffer after sample i's last read of it.
+        const int cnt = __builtin_amdgcn_readfirstlane(s_lo + wv < s_hi ? (s_hi - s_lo - wv + PR_WAVES - 1) / PR_WAVES : 0);      // (the same in every lane)
+        const uint32_t n4 = (nrw + 3u) / 4u;                                  // 16-byte groups of a piece that the columns can name
+        const uint16_t *plj = a.plen + j * (uint64_t)S + s_lo + wv;
+        uint4 *pc4 = reinterpret_cast<uint4 *>(pc);
+        // (the pieces and the wave's buffer are 16-byte aligned: cap is a multiple of 128; a dword per lane made this copy a quarter of the
+        // kernel's time: 3.95 -> 3.10 ms for the kept rows of 1 000 x 5 Mbp)
+        // (the length masks what was loaded only when it goes to the buffer: nothing touches the registers while the loads are on their way)
+        auto masked = [&](uint4 x, uint32_t i, uint32_t plw) {
+            if (4u * i >= plw) x.x = 0u;                                        // ranks handed out after this sample: no cell
+            if (4u * i + 1u >= plw) x.y = 0u;
+            if (4u * i + 2u >= plw) x.z = 0u;
+            if (4u * i + 3u >= plw) x.w = 0u;
+            return x;
+        };
+        uint32_t plv = 0, plw = 0, plw_next = 0;
+        uint4 nx[PR_AHEAD];
+#pragma unroll
+        for (int u = 0; u < PR_AHEAD; u++) nx[u] = make_uint4(0u, 0u, 0u, 0u);
+        auto ask = [&](int i) {                                                 // sample i of the wave: its length, its piece on the way
+            if ((i & 63) == 0) plv = i + lane < cnt ? (uint32_t)plj[(size_t)(i + lane) * PR_WAVES] : 0u;
+            plw_next = ((uint32_t)__builtin_amdgcn_readlane((int)plv, i & 63) + 7u) / 8u;
+            const uint4 *src4 = reinterpret_cast<const uint4 *>(a.pieces + (j * (uint64_t)S + (uint64_t)(s_lo + wv + i * PR_WAVES)) * (cap / 2));
+#pragma unroll
+            for (int u = 0; u < PR_AHEAD; u++) { const uint32_t i4 = (uint32_t)lane + 64u * u; if (i4 < n4 && 4u * i4 < plw_next) nx[u] = src4[i4]; }
+        };
+        if (cnt > 0) ask(0);
+        for (int it = 0; it < cnt; it++) {
+            const int s = s_lo + wv + it * PR_WAVES;
+            plw = plw_next;
+#pragma unroll
+            for (int u = 0; u < PR_AHEAD; u++) { const uint32_t i4 = (uint32_t)lane + 64u * u; if (i4 < n4) pc4[i4] = masked(nx[u], i4, plw); }
+            if (n4 > 64u * PR_AHEAD) {                                          // (a longer piece: its rest straight from memory)
+                const uint4 *src4 = reinterpret_cast<const uint4 *>(a.pieces + (j * (uint64_t)S + (uint64_t)s) * (cap / 2));
+                for (uint32_t i4 = (uint32_t)lane + 64u * PR_AHEAD; i4 < n4; i4 += 64) pc4[i4] = masked(4u * i4 < plw ? src4[i4] : make_uint4(0u, 0u, 0u, 0u), i4, plw);
             }
             __builtin_amdgcn_wave_barrier();
+            if (it + 1 < cnt) ask(it + 1);
             unsigned char *dst = a.out + (uint64_t)s * a.pitch + (ocol - shift);
             for (uint32_t v = v_lo + lane; v < v_hi; v += 64) {
                 const uint2 rr = *reinterpret_cast<const uint2 *>(s_src + 4u * (v - v_lo));      // four ranks

@@ -183,10 +183,11 @@ void launch_append_wide(const AppendArgs &a, hipStream_t st);
 void launch_append_wide_probe(const AppendArgs &a, unsigned blocks, hipStream_t st);
 // row statistics from the pieces (present, unambiguous, code set, variant_count), written to the rows in the order of H
 void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt, const uint64_t *roff, uint32_t cap,
-                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, const uint32_t *r_cut = nullptr);
-// r_cut[j] = the min_count-th largest piece length of row block j (0: min_count > samples): no rank at or beyond it can reach min_count.
-// ncnt / stage (pieces_stats_bound; ncnt may be null): blocks the bounded statistics pass would not stage get 0xFFFFFFFF; tally (optional, zeroed):
-// [0] += ranks in 16-byte columns the bounded pass leaves unread, [1] += blocks with any
+                         int n_samples, int n_blocks, uint32_t *present, uint32_t *unambig, uint32_t *mask, uint32_t *vcount, hipStream_t st, uint32_t min_count = 0, unsigned long long *tally = nullptr);
+// min_count >= 1: the pass of a frequency filter -- a staged workgroup takes its block's cut (the min_count-th largest piece length, 0: min_count >
+// samples; no rank at or beyond it can reach min_count) and reads only the columns below it; tally (optional, zeroed): [0] += ranks in 16-byte
+// columns the bounded pass leaves unread, [1] += blocks with any.  launch_pieces_cut: the cut alone, r_cut[j] (a test hook's kernel);
+// ncnt / stage (pieces_stats_bound; ncnt may be null): blocks the bounded statistics pass would not stage get 0xFFFFFFFF
 void launch_pieces_cut(const uint16_t *plen, int n_samples, uint32_t cap, uint32_t min_count, const uint32_t *nrank, const uint32_t *ncnt, uint32_t stage, int n_blocks,
                        uint32_t *r_cut, unsigned long long *tally, hipStream_t st);
 uint32_t pieces_stats_bound(uint32_t cap);                               // rows per block the statistics pass stages; 0: launches at this capacity are not bounded
