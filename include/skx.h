@@ -340,6 +340,38 @@ int  skx_array_delete_samples(skx_array *a, const char *const *names, int n_name
 typedef struct { uint64_t rows_present, removed, silent, sites; } skx_subset_info;
 int  skx_array_subset_filtered(skx_array *a, const int *samples, int n_samples, const skx_filter_spec *f,
                                skx_array **out, skx_subset_info *info);
+/* `ska markers`: which split k-mers, and which middle-base alleles, tell one group of samples from everybody else -- for every group of a
+ * partition from a number of passes over the matrix that does not depend on how many groups there are.  The reference has no counterpart: its
+ * users chain delete_samples of a group (merge_ska_array.rs:231-271) and the Debug output of `ska nk --full-info` (:649-698) once per group and
+ * compare the text (SKA 1 had `ska unique`).
+ * Inputs.  The array holds S samples and U rows.  Cells are bytes; code(cell) is the 4-bit IUPAC set (A 1, C 2, T 4, G 8; '-' and the 0 byte
+ * are 0).  A partition assigns every sample to exactly one segment: segments 0..G-1 are the groups (of the file, in the order their labels first
+ * appear); samples no group lists form one further, unnamed segment, which is never reported -- its samples still count as "others".
+ * Per-row quantities for a reported group g (n = its size): in = cells of g with code != 0; out = cells of all other samples with code != 0;
+ * bases_in / bases_out = OR of the codes on each side.
+ * Thresholds, computed in doubles exactly like this: t_in = max(1, (uint64)ceil(n * P)), t_out = (uint64)floor((S - n) * Q).
+ * Kinds.  presence marker of g: in >= t_in and out <= t_out.  allele marker of g: in >= t_in, not a presence marker, and
+ * bases_in & bases_out == 0.  An ambiguous cell stands for all its bases, which is conservative.  A row can be a marker of several groups; it is
+ * a marker of one group at most once.
+ * segment_of[S]: the segment of every sample, n_groups for the unnamed one; reported[n_groups]: non-zero = this group's markers are wanted (a
+ * group that is not reported still counts as others); P = min_in, Q = max_out; kinds: SKX_MARKER_PRESENCE | SKX_MARKER_ALLELE (which of the two
+ * are returned; an allele marker is never a presence marker, whichever are asked for).  records / keys: malloc'd (skx_free), n of each, sorted by
+ * (group, row index in the array's current order); keys[i] = the record's split k-mer as skx_array_export gives keys; info (n_groups, may be
+ * NULL): the records of each kind per group.  The records are counted before their buffer is allocated: when they do not fit, SKX_ENOMEM with
+ * a message.  SKX_EINVAL with a message that begins "markers:" for P or Q outside [0, 1] or NaN, a segment index out of range, a reported group
+ * without samples, kinds == 0 or unknown bits, an array without split k-mers (skx_array_load_filtered, skx_array_subset_filtered); SKX_EUNSUP with
+ * the same beginning above 65 535 samples or segments.  `a` keeps its content (an array held as pieces or lazily is materialised first); both
+ * key widths are taken.  Device memory beside the array: 12 bytes a row, 16 a group, 68 a record while they are sorted. */
+enum { SKX_MARKER_PRESENCE = 1, SKX_MARKER_ALLELE = 2 };
+typedef struct {
+    uint64_t row;                      /* row index in the array's current order */
+    uint32_t group, n_in, n_out;       /* in, out */
+    uint8_t  kind;                     /* SKX_MARKER_PRESENCE or SKX_MARKER_ALLELE */
+    uint8_t  bases_in, bases_out, reserved;
+} skx_marker;
+typedef struct { uint64_t presence, allele; } skx_marker_info;
+int  skx_array_group_markers(skx_array *a, const int32_t *segment_of, int n_groups, const uint8_t *reported, double min_in, double max_out, int kinds,
+                             skx_marker **records, skx_key **keys, uint64_t *n, skx_marker_info *info);
 /* MergeSkaArray::weed (merge_ska_array.rs:452-487): rows whose split k-mer is (reverse: is not) in `weed` are removed;
  * `weed` = the split k-mers of the weed FASTA (RefSka::new + kmer_iter, ska_ref.rs:189-262,541), i.e. the key set of its
  * dictionary: skx_dictset_build_files (1 sample) -> skx_keyset_union. */

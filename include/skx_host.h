@@ -44,6 +44,21 @@ int skh_align_samples_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, 
  * <n>: ..." for a line without exactly two fields, an empty name or label, a label holding '/' or a NUL or equal to "." or "..", a sample
  * name listed twice; SKX_EIO when the file cannot be read. */
 int skh_read_groups(const char *path, char **buf, uint64_t *len, uint64_t *n_pairs);
+/* `ska markers <SKF_FILE> --groups FILE -o PREFIX [--min-in P] [--max-out Q] [--min-group-size N] [--kind ...] [--fasta]` (no counterpart in the
+ * reference, whose users run `ska delete` of a group, generic_modes.rs:192-210, and `ska nk --full-info`, lib.rs:808-827, once per group and
+ * compare the text): the file is loaded once (skh_load_array), the groups file is read by skh_read_groups and its names matched as
+ * skh_align_groups matches them; groups of fewer than min_group_size (>= 1) samples are not reported, their samples still count as others;
+ * one call of skx_array_group_markers (its definition of a marker; kinds as it takes them) answers every group.
+ * <PREFIX>.markers.tsv: header "Group\tUpper\tLower\tKind\tIn\tOut\tBases\tOther bases", one line per record, groups in file order, within a
+ * group in the order `ska nk --full-info` prints the rows of the same file, Upper and Lower decoded as there; Kind = presence | allele,
+ * In = in/n, Out = out/(S-n), Bases / Other bases = the IUPAC letter of the set ("-" for the empty one).
+ * <PREFIX>.markers.summary.tsv: header "Group\tSamples\tPresence\tAllele", one line per group, "-" in the two counts of a group that was too small.
+ * fasta != 0: <PREFIX>.<label>.markers.fa for every reported group with a marker, one record per marker in the TSV's order:
+ * ">{label}_{i} kind=.. in=.. out=.. bases=.." (i from 1), sequence = Upper + the first of A, C, G, T in the group's set + Lower + one N --
+ * `ska weed <skf> <that file> --reverse --min-freq 0` keeps exactly the marker rows (k bases alone give the reference's reader no split k-mer; the N adds none).
+ * Phases: markers.load / markers.pass / markers.text. */
+int skh_markers(skx_ctx *ctx, const char *skf_file, const char *groups_file, const char *out_prefix, double min_in, double max_out,
+                int min_group_size, int kinds, int fasta);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

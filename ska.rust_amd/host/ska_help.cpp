@@ -112,6 +112,15 @@ const std::vector<Cmd> &commands()
           {"graph traversal", {{"-d, --depth", "<DEPTH>", "maximum depth of recursive paths [default: 4]"}}},
           {"other", {{"-n, --indel-kmers", "<INDEL_KMERS>", "maximum number of internal indel k-mers [default: 2]"},
                      {"--threads", "<THREADS>", THREADS}}}}},
+        {"markers", "(MI355X engine) Find the split k-mers and middle-base alleles that tell each group of samples from everybody else", "ska markers [OPTIONS] --groups <FILE> -o <OUTPUT> <SKF_FILE>",
+         {{"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on"}},
+         {{"--groups", "<FILE>", "Sample name and group label per line (comma or tab separated; <PREFIX>.clusters.csv of `ska distance --clusters` is taken as it is); samples it does not list count as others"},
+          {"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.markers.tsv and <OUTPUT>.markers.summary.tsv"},
+          {"--min-in", "<P>", "Smallest fraction of a group's samples that must have the split k-mer [default: 1.0]"},
+          {"--max-out", "<Q>", "Largest fraction of the other samples that may have a presence marker's split k-mer [default: 0.0]"},
+          {"--min-group-size", "<N>", "Do not report groups of fewer than N samples (they still count as others) [default: 1]"},
+          {"--kind", "<KIND>", "Markers to report [default: both] [possible values: presence, allele, both]"},
+          {"--fasta", "", "Also write <OUTPUT>.<label>.markers.fa per group: `ska weed <SKF_FILE> <that file> --reverse --min-freq 0` keeps exactly its marker rows"}}},
     };
     return C;
 }

@@ -924,7 +924,7 @@ const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
                             "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels",
-                            "--groups", "--min-group-size", "--samples", "--samples-file", nullptr};
+                            "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
@@ -1520,6 +1520,29 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (!a.pos.empty() && a.has("-f")) { fprintf(stderr, "error: the argument '[NAMES]...' cannot be used with '-f <FILE_LIST>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("delete")); return 2; }
     }
     else if (cmd == "weed") { if (a.pos.empty()) return clap_missing("weed", "<SKF_FILE>"); if (int e = filter()) return e; if (int e = freq()) return e; }
+    else if (cmd == "markers") {
+        // the engine's own mode: one device's array and a groups file, refused as clap refuses a missing requirement, a conflict and a value that does not parse
+        if (a.pos.empty()) return clap_missing("markers", "<SKF_FILE>");
+        if (a.pos.size() > 1) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[1].c_str(), skh_usage_line("markers")); return 2; }
+        if (!a.has("--groups")) return clap_missing("markers", "--groups <FILE>");
+        if (!a.has("-o")) return clap_missing("markers", "-o <OUTPUT>");
+        if (a.has("--gpus") || multi) { fprintf(stderr, "error: the argument '--gpus <GPUS>' cannot be used with '--groups <FILE>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("markers")); return 2; }
+        for (auto o : {std::make_pair("--groups", "--groups <FILE>"), std::make_pair("-o", "-o <OUTPUT>")}) if (a.get(o.first).empty()) return clap_invalid("", o.second, "a value is required");
+        for (auto o : {std::make_pair("--min-in", "--min-in <P>"), std::make_pair("--max-out", "--max-out <Q>")}) {
+            if (!a.has(o.first)) continue;
+            const std::string v = a.get(o.first);
+            if (!lo_float(v)) return clap_invalid(v, o.second, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
+            const double f = strtod(v.c_str(), nullptr);
+            if (!(f >= 0.0 && f <= 1.0)) return clap_invalid(v, o.second, "Proportion must be between 0 and 1 (inclusive)");
+        }
+        if (a.has("--min-group-size")) {
+            const std::string v = a.get("--min-group-size");                                     // usize::from_str, then the range
+            if (v.empty()) return clap_invalid(v, "--min-group-size <N>", "cannot parse integer from empty string");
+            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--min-group-size <N>", "invalid digit found in string");
+            if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, "--min-group-size <N>", "must be one or higher");
+        }
+        if (a.has("--kind")) { const std::string v = a.get("--kind"); if (v != "presence" && v != "allele" && v != "both") return clap_possible(v, "--kind <KIND>", "presence, allele, both"); }
+    }
     else if (cmd == "lo") {                                                                                       // cli.rs:395-425
         if (a.pos.size() < 2) return clap_missing("lo", a.pos.empty() ? "<INPUT_SKF>\n  <OUTPUT>" : "<OUTPUT>");
         if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("lo")); return 2; }
@@ -1576,6 +1599,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
+            {"markers", " -o --groups --min-in --max-out --min-group-size --kind --fasta --gpus "},
             {"lo", " -r --reference -m --missing -d --depth -n --indel-kmers --threads "}};
         for (auto &kc : KNOWN)
             if (cmd == kc.cmd)
@@ -1717,6 +1741,13 @@ extern "C" int skh_main(int argc, char **argv)
         char *buf = nullptr; uint64_t len = 0;
         if (skh_load_array(ctx, in, 1, 1, &arr) != SKX_OK || skh_nk(arr, a.has("--full-info"), &buf, &len) != SKX_OK) rcode = engine_fail();
         else { rcode = emit("", buf, len); skx_free(buf); }
+    } else if (cmd == "markers") {                                                                                // the engine's own: skh_markers
+        const std::string kind = a.get("--kind", "both");
+        const int kinds = kind == "presence" ? SKX_MARKER_PRESENCE : kind == "allele" ? SKX_MARKER_ALLELE : SKX_MARKER_PRESENCE | SKX_MARKER_ALLELE;
+        const int min_size = (int)std::min<unsigned long long>(strtoull(a.get("--min-group-size", "1").c_str(), nullptr, 10), INT_MAX);
+        if (skh_markers(ctx, a.pos[0].c_str(), a.get("--groups").c_str(), a.get("-o").c_str(), strtod(a.get("--min-in", "1.0").c_str(), nullptr),
+                        strtod(a.get("--max-out", "0.0").c_str(), nullptr), min_size, kinds, a.has("--fasta")) != SKX_OK)
+            rcode = engine_fail();
     } else if (cmd == "cov") {                                                                                    // cli.rs Cov, lib.rs:828-851
         if (a.pos.size() != 2) return fail("usage: ska cov <fastq_fwd> <fastq_rev> [-k K] [--single-strand]");
         const int k = atoi(a.get("-k", "31").c_str());
@@ -1773,7 +1804,7 @@ extern "C" int skh_main(int argc, char **argv)
         if (r == SKX_EEMPTY) rcode = 1;                                                                          // extremities.rs: std::process::exit(1)
         else if (r != SKX_OK) rcode = engine_fail();
     } else {
-        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo)");
+        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers)");
     }
     const double t_done = since();
     if (dbg) fprintf(stderr, "[skx] main: %s done after %.2f s\n", cmd.c_str(), t_done);

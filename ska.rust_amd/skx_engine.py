@@ -22,6 +22,10 @@ KEY_DT = np.dtype([("lo", "<u8"), ("hi", "<u8")])
 DIST_DT = np.dtype([("distance", "<f8"), ("mismatch_prop", "<f8"), ("match_count", "<u8"), ("mismatch_count", "<u8")])
 PAIR_DT = np.dtype([("i", "<u4"), ("j", "<u4"), ("d", DIST_DT)])      # skx_dist_pair
 NJ_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("len_a", "<f8"), ("len_b", "<f8")])      # skx_nj_join
+MARKER_DT = np.dtype([("row", "<u8"), ("group", "<u4"), ("n_in", "<u4"), ("n_out", "<u4"), ("kind", "u1"), ("bases_in", "u1"), ("bases_out", "u1"),
+                      ("reserved", "u1")])                                               # skx_marker
+MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])                      # skx_marker_info
+MARKER_PRESENCE, MARKER_ALLELE = 1, 2
 
 
 class Qual(C.Structure):
@@ -129,7 +133,8 @@ skx_array_distance_select skx_array_distance_select_prefiltered skh_distance_sel
 skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv skh_cluster_cutoffs skh_distance_banded_files
 skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd
 skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv
-skx_ctx_filter_cut""".split()
+skx_ctx_filter_cut
+skx_array_group_markers skh_markers""".split()
 
 _lib = None
 
@@ -178,6 +183,8 @@ def load_library():
     lib.skh_read_groups.argtypes = [cp, pp, C.POINTER(u64), C.POINTER(u64)]
     lib.skh_align_groups.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, cp, i, cp]
     lib.skh_align_samples_fd.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, C.POINTER(cp), i, i]
+    lib.skx_array_group_markers.argtypes = [vp, vp, i, vp, d, d, i, pp, pp, C.POINTER(u64), vp]
+    lib.skh_markers.argtypes = [vp, cp, cp, cp, d, d, i, i, i]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -522,6 +529,12 @@ class Context:
         arr = (C.c_char_p * len(inputs))(*[x.encode() for x in inputs])
         _check(_lib.skh_align_groups(self.h, arr, len(inputs), int(threads), int(filter_type), int(mask_ambig), int(ignore_const_gaps), float(min_freq),
                                      int(filter_ambig_as_missing), groups_file.encode(), int(min_group_size), out_prefix.encode()))
+
+    def markers(self, skf_file, groups_file, out_prefix, min_in=1.0, max_out=0.0, min_group_size=1, kinds=MARKER_PRESENCE | MARKER_ALLELE, fasta=False):
+        """`ska markers <skf> --groups FILE -o PREFIX` (skh_markers): PREFIX.markers.tsv, PREFIX.markers.summary.tsv and, with fasta,
+        PREFIX.<label>.markers.fa per group, from one load"""
+        _check(_lib.skh_markers(self.h, os.fsencode(skf_file), os.fsencode(groups_file), os.fsencode(out_prefix), float(min_in), float(max_out),
+                                int(min_group_size), int(kinds), int(fasta)))
 
     def align_samples(self, inputs, names, fd, threads=1, min_freq=0.9, filter_ambig_as_missing=False, filter_type=FILTER_NO_CONST, mask_ambig=False,
                       ignore_const_gaps=False):
@@ -991,6 +1004,26 @@ class Array:
         h, info = C.c_void_p(), SubsetInfo()
         _check(_lib.skx_array_subset_filtered(self.h, _np_ptr(idx), len(idx), C.byref(fs), None if counts_only else C.byref(h), C.byref(info)))
         return (None if counts_only else Array(h, self.ctx)), {n: getattr(info, n) for n, _ in SubsetInfo._fields_}
+
+    def group_markers(self, segment_of, n_groups, reported=None, min_in=1.0, max_out=0.0, kinds=MARKER_PRESENCE | MARKER_ALLELE):
+        """skx_array_group_markers: the presence and allele markers of every reported group of a partition, this array left as it is.
+        segment_of[s] = the group of sample s (n_groups: listed by no group); reported[g] (default: every group)
+        -> (records as MARKER_DT sorted by (group, row), their split k-mers as KEY_DT, per-group counts as MARKER_INFO_DT)"""
+        seg = np.ascontiguousarray(segment_of, np.int32)
+        if seg.size != self.nsamples:
+            raise ValueError("one segment per sample is required")
+        rep = np.ones(max(n_groups, 1), np.uint8) if reported is None else np.ascontiguousarray(reported, np.uint8)
+        if rep.size < n_groups:
+            raise ValueError("one flag per group is required")
+        info = np.zeros(max(n_groups, 1), MARKER_INFO_DT)
+        pr, pk, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(_lib.skx_array_group_markers(self.h, _np_ptr(seg), int(n_groups), _np_ptr(rep), float(min_in), float(max_out), int(kinds),
+                                            C.byref(pr), C.byref(pk), C.byref(n), _np_ptr(info)))
+        rec = np.frombuffer(C.string_at(pr, n.value * MARKER_DT.itemsize), MARKER_DT).copy() if n.value else np.zeros(0, MARKER_DT)
+        keys = np.frombuffer(C.string_at(pk, n.value * KEY_DT.itemsize), KEY_DT).copy() if n.value else np.zeros(0, KEY_DT)
+        _lib.skx_free(pr)
+        _lib.skx_free(pk)
+        return rec, keys, info[:n_groups]
 
     def map(self, reference, fmt="aln", ambig_mask=False, repeat_mask=False, threads=0):
         """generic_modes::map: RefSka::new + map + write_aln | write_vcf -> text (generic_modes.rs:56-84)."""
