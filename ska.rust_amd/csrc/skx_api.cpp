@@ -1429,6 +1429,8 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
     }
     // the coarsest split whose blocks hold their rows with six sigma to spare (a finer one reads every region more often)
     for (logQ = min_logQ; logQ < bits && u_est / (double)(1ull << logQ) + 6.0 * std::sqrt(u_est / (double)(1ull << logQ) + 1.0) + 32.0 > (double)max_cap; logQ++) { }
+    // (tests: SKX_KNOBS=append_coarse=N starts N steps coarser, so that row blocks overflow and the retries below run -- no input reaches them)
+    if (knob("append_coarse") > 0) logQ = std::max<long>(min_logQ, logQ - knob("append_coarse"));
     for (int attempt = 0;; attempt++, logQ++) {
         if (logQ > bits || attempt > 3) return not_taken("row blocks kept overflowing (a sample that is one repeat, or far more rows than the probe saw)");
         const uint64_t nsub = 1ull << logQ;
@@ -1546,6 +1548,8 @@ extern "C" int skx_merge(skx_ctx *ctx, skx_dictset *d, const char *const *names,
     return skx_guarded([&]() -> int {
     if (!ctx || !d || !out) { set_error("bad arguments"); return SKX_EINVAL; }
     { const int ra = merge_append(ctx, d, names, out); if (ra != SKF_NOT_TAKEN) return ra; }
+    // (sorted here: the union below would otherwise offer the dictset to the append pass once more -- probe and four launches again)
+    SKX_TRY(dictset_sort(d));
     skx_keyset *ks = nullptr;
     SKX_TRY(keyset_union_dict(ctx, d, &ks, true));
     int r = skx_array_assemble(ctx, d, ks, names, out);

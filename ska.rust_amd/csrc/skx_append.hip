@@ -240,7 +240,9 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
             for (uint32_t t = home(kh); t + 3u < total_slots;) {
                 AP_COUNT(10, 1); if (ap_mbcnt(__ballot(true)) == 0u) AP_COUNT(11, 1);
                 const unsigned long long e0 = s_tab[t], e1 = s_tab[t + 1], e2 = s_tab[t + 2], e3 = s_tab[t + 3];
-                const bool m0 = (e0 ^ keyE) <= AP_RANK_MASK, m1 = (e1 ^ keyE) <= AP_RANK_MASK, m2 = (e2 ^ keyE) <= AP_RANK_MASK, m3 = (e3 ^ keyE) <= AP_RANK_MASK;
+                // (entry ^ key) is the rank field, 1 .. all ones, where the keys agree -- less one: an EMPTY slot is not taken for the key whose bits are
+                // all zero (the poly-A split k-mer, whose hash is 0; every key when rem = 0), which read as "found, no rank" and failed the launch
+                const bool m0 = (e0 ^ keyE) - 1ull < AP_RANK_MASK, m1 = (e1 ^ keyE) - 1ull < AP_RANK_MASK, m2 = (e2 ^ keyE) - 1ull < AP_RANK_MASK, m3 = (e3 ^ keyE) - 1ull < AP_RANK_MASK;
                 bool won = false;
                 uint32_t at = 0;
                 if (!(m0 | m1 | m2 | m3)) {
