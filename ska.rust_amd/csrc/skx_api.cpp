@@ -461,7 +461,7 @@ static int dictset_sort_flat(skx_ctx *ctx, skx_dictset *d)
     d->words = std::move(words); d->off = std::move(off); d->raw = std::move(rawn); d->ucnt = std::move(ucnt);
     d->sidx.release(); d->sb = 0; d->logB = 0;
     d->sample_size = sizes;
-    d->sorted = true;
+    d->sorted = true; d->sketch.release();                      // (the sketch sizes the append pass, which reads unsorted regions only)
     return SKX_OK;
 }
 
@@ -477,7 +477,7 @@ int skx::dictset_sort(skx_dictset *d)
     if (overflow) { set_error("internal: a fixed-capacity region did not fit the counting sort (%d)", overflow); return SKX_EUNSUP; }
     d->sample_size.assign(d->n, 0);
     for (int s = 0; s < d->n; s++) for (uint64_t b = 0; b < (1ull << d->logB); b++) d->sample_size[s] += ucnt[((uint64_t)s << d->logB) + b];
-    d->sorted = true;
+    d->sorted = true; d->sketch.release();
     return SKX_OK;
 }
 
@@ -613,6 +613,8 @@ static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *>
             const uint32_t region_cap = region_capacity(maxlen, logB);
             launch_fill_offsets(d->off.p, nreg, region_cap, st);
             SKX_TRY(d->words.alloc(nreg * (uint64_t)region_cap * wpk + 2048));      // (+ slack: the append pass reads whole chunks of up to 12 KB)
+            // the split sketch, zeroed with the regions' fills: what append_pass sizes its row blocks from instead of a count-only launch
+            if (sketch_ok(wide ? wh.bits : hp.bits, logB)) { SKX_TRY(d->sketch.alloc(sketch_words(logB))); SKX_TRY(d->sketch.zero(st)); a.sketch = d->sketch.p; }
             { StageTimer t(ctx, &ctx->tm.scatter); a.hist = d->raw.p; a.off = d->off.p; a.words = d->words.p; a.capacity = region_cap;
               if (wide) launch_scatter_wide(a, st); else launch_scatter(a, st); }
             int over = 0;
@@ -664,6 +666,7 @@ static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *>
         int overflow = 0;
         std::vector<uint32_t> ucnt;
         SKX_TRY(dedupe_regions(ctx, d.get(), lds_cap, maxlen, &overflow, ucnt));
+        d->sketch.release();                                                          // sorted dictionaries: no sketch
         if (overflow) {
             if (logB >= std::min(key_bits_used, MAX_LOGB)) return build_reads();       // repeat content beyond every region size
             logB++;
@@ -1389,9 +1392,12 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
     if (min_logQ > bits) return not_taken("no row-block split with room for a rank in a table entry");
     // (regions of any size: a wave streams a region in chunks of 1 024 words -- the samples above ~5 Mbp of round 6 keep their bucket count and
     // grow their regions)
+    // ranks a block of `mean` expected rows needs: six sigma of its binomial size and of the estimate's own error together (independent: the
+    // variances add; est_relvar = the relative variance of |U| as the sketch gives it, 0 for a count), + 32
+    double est_relvar = 0.0;
+    auto ranks_need = [&](double mean) -> double { return mean + 6.0 * std::sqrt(mean + 1.0 + est_relvar * mean * mean) + 32.0; };
     auto ranks_for = [&](double mean) -> uint32_t {
-        const double c = mean + 6.0 * std::sqrt(mean + 1.0) + 32.0;
-        return (uint32_t)std::min<double>(max_cap, std::ceil(c / 128.0) * 128.0);
+        return (uint32_t)std::min<double>(max_cap, std::ceil(ranks_need(mean) / 128.0) * 128.0);
     };
     auto slots_for = [&](uint32_t cap) -> uint32_t {                  // a power of two (the home slot is a shift), a third more than the ranks at least
         uint32_t n = 256u;
@@ -1404,11 +1410,47 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
     AppendArgs aa{};
     aa.words = d->words.p; aa.off = d->off.p; aa.raw = d->raw.p; aa.n_samples = S; aa.logB = logB; aa.bits = bits; aa.overflow = d_flag.p; aa.probe = d_probe.p;
     StageTimer t(ctx, &ctx->tm.key_union);
-    // |U| from a thin slice of the hash space: the first row blocks of a 2^logP split, rows counted only
+    // |U| from a slice of the hash space.  A dictset the single-pass scatter kernel filled brings a sketch of that slice (skx_device.h: a bitmap
+    // per sketch region, the zero bits of which give the region's distinct keys by linear counting), read out by one small kernel; the rows of a
+    // block are binomial around |U| / 2^logQ wherever they fall (H's top bits are uniform), so the estimate that sizes the split is the SUM over
+    // the sketch regions scaled to all regions -- what the count-only launch measures -- and the estimator's own error joins the block's binomial
+    // spread in the six sigma below (ranks_need: two independent errors, so their variances add; added to |U| on top of the block's six sigma
+    // the same 0.2 % moved 1 000 x 5 Mbp to twice the row blocks and the step from 33.2 to 39.9 ms: its 5 521 rows a block are 0.3 % under the
+    // 5 537 at which the split doubles.  For the same reason not the LARGEST sketch region: the largest of four lies 0.7 % above their mean,
+    // which is the binomial spread counted a second time).  An underestimate ends where the launch's ended: the blocks overflow and the loop
+    // below comes back one step finer.  No sketch, a sketch more than SKETCH_MAX_FILL full or SKX_KNOBS=probe_launch: the first row blocks of a
+    // 2^logP split, rows counted only
     double u_est = (double)raw_max;
     const double target = wide ? 2600.0 : 5400.0;    // mean rows of a probe block (the final split: the coarsest whose blocks fit their ranks)
     int logQ = min_logQ;
-    if (S > 1) {
+    char sized[160] = "one sample";
+    bool by_sketch = false;
+    if (S > 1 && d->sketch.p && !knob("probe_launch")) {
+        const int nsk = sketch_regions(logB);
+        DevBuf<uint32_t> d_zeros; SKX_TRY(d_zeros.alloc(nsk));
+        { KernelTimer kt(ctx, &ctx->tm.append_probe); launch_sketch_count(d->sketch.p, logB, d_zeros.p, st); }
+        std::vector<uint32_t> zeros(nsk);
+        SKX_HIP(hipMemcpyAsync(zeros.data(), d_zeros.p, (size_t)nsk * 4, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipStreamSynchronize(st));
+        SKX_HIP(hipGetLastError());
+        const double M = (double)(1u << SKETCH_M);
+        double rows = 0, var = 0, fill = 0;
+        for (uint32_t z : zeros) {
+            fill = std::max(fill, 1.0 - (double)z / M);
+            if (z == 0) continue;                                      // (a full bitmap: fill = 1, no estimate)
+            const double t = -std::log((double)z / M);
+            rows += M * t; var += M * (std::exp(t) - t - 1.0);
+        }
+        if (fill > SKETCH_MAX_FILL) snprintf(sized, sizeof sized, "the probe launch: the sketch is %.3f full", fill);
+        else {
+            by_sketch = true;
+            const double scale = (double)(1u << sketch_step_log(logB));
+            u_est = std::max((double)raw_max * 0.5, rows * scale);
+            est_relvar = rows > 0 ? var / (rows * rows) : 0.0;
+            snprintf(sized, sizeof sized, "the sketch: %.1f rows in %d sketch regions, fill %.3f", rows, nsk, fill);
+        }
+    } else if (S > 1) snprintf(sized, sizeof sized, "the probe launch: %s", d->sketch.p ? "SKX_KNOBS=probe_launch" : "no sketch");
+    if (S > 1 && !by_sketch) {
         int logP = std::min(bits, std::max(min_logQ, ilog2_ceil((uint64_t)((double)raw_max * 3.0 / target) + 1)));
         for (int attempt = 0;; attempt++) {
             const unsigned blocks = (unsigned)std::min<uint64_t>(64, 1ull << logP);
@@ -1428,7 +1470,7 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
         }
     }
     // the coarsest split whose blocks hold their rows with six sigma to spare (a finer one reads every region more often)
-    for (logQ = min_logQ; logQ < bits && u_est / (double)(1ull << logQ) + 6.0 * std::sqrt(u_est / (double)(1ull << logQ) + 1.0) + 32.0 > (double)max_cap; logQ++) { }
+    for (logQ = min_logQ; logQ < bits && ranks_need(u_est / (double)(1ull << logQ)) > (double)max_cap; logQ++) { }
     // (tests: SKX_KNOBS=append_coarse=N starts N steps coarser, so that row blocks overflow and the retries below run -- no input reaches them)
     if (knob("append_coarse") > 0) logQ = std::max<long>(min_logQ, logQ - knob("append_coarse"));
     for (int attempt = 0;; attempt++, logQ++) {
@@ -1470,7 +1512,7 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
         SKX_HIP(hipMemcpyAsync(&ov, d_flag.p, 4, hipMemcpyDeviceToHost, st));
         SKX_HIP(hipStreamSynchronize(st));
         SKX_HIP(hipGetLastError());
-        if (getenv("SKX_DEBUG")) fprintf(stderr, "[skx] append%s: logQ=%d (x%llu per region) cap=%u slots=%u rows~%.0f -> %s\n", wide ? " (128-bit keys)" : "", logQ, (unsigned long long)amp, cap, nslots, u_est, ov ? "overflow" : "ok");
+        if (getenv("SKX_DEBUG")) fprintf(stderr, "[skx] append%s: logQ=%d (x%llu per region) cap=%u slots=%u rows~%.0f -> %s [sized by %s]\n", wide ? " (128-bit keys)" : "", logQ, (unsigned long long)amp, cap, nslots, u_est, ov ? "overflow" : "ok", sized);
         if (ov & 4) return not_taken("the table's bytes are not at LDS address 0");
         if (ov) continue;
         SKX_TRY(keyset_finish(ks.get()));

@@ -87,7 +87,47 @@ struct ExtractArgs {
     uint64_t *words;              // dict storage (pass 2)
     uint32_t capacity;            // words per region (pass 2): ranks beyond it are dropped and *overflow is set
     int *overflow;
+    uint32_t *sketch = nullptr;   // scatter form, optional: the split sketch [SKETCH_COPIES][sketch_regions(logB)][SKETCH_WORDS], zeroed (below)
 };
+
+// ---- the split sketch: how many distinct split k-mers a region holds, learnt while the extraction kernel has the words in hand -------
+// A fixed set of *sketch regions* (sketch_step_log: every 256th bucket where a sample has 2^10 buckets and more, every 64th where it has 64 x 4,
+// every bucket otherwise) gets a bitmap of M = 2^SKETCH_M bits: a word sets the bit named by the SKETCH_M
+// hash bits directly below its bucket bits (128-bit keys) or by sketch_index64 (64-bit keys).  Distinct keys are then balls thrown into M
+// bins whatever the samples have in common (a repeated key sets its bit again), and Z zero bits give n^ = -M ln(Z / M) (linear counting) with
+//     Var(n^) ~= M (e^t - t - 1),  t = n / M        (Whang, Vander-Zanden, Taylor 1990)
+// Why the 64-bit keys do not take the bits below the bucket bits too: their H has two Feistel rounds, and its upper half L' = L ^ f(R) passes
+// the upper arm's own bits through.  Two split k-mers with the same lower arm whose upper arms differ in a base next to the middle one -- every
+// SNP makes such a pair -- differ in the lowest bits of L' alone and would set the same bit: the count came out 1.4 % low for three related
+// samples of 2 kbp (2 091 for 2 120 rows; tests/test_gpu_split_sketch.py works it on the CPU).  The lower half R' = R ^ f(L') differs all over for
+// such a pair, so the index is a multiplicative hash of H's low 32 bits cut to the bits below the bucket bits.  The three rounds of the 128-bit
+// H mix the upper half twice.
+// SKETCH_M = 18: 22 000 rows a region (the 5 Mbp shape: t = 0.084) have a standard error of 31 rows, 0.14 %, and its four sketch regions
+// together 0.07 %; at the fill beyond which the sketch is not used (SKETCH_MAX_FILL: t = ln 2, 181 704 rows) it is 284 rows, 0.16 %.
+// Why a 256th of the hash space and not the 64th the count-only launch reads: the ORs are not free.  Each is an L2 request of its own (the
+// bits of a bucket's dozen words a tile share no line), and the extraction kernel is bound by its requests: 192 a tile (every 64th bucket)
+// cost it 1.0 ms of 11.8 per 1 000 x 5 Mbp -- more than the 0.75 ms launch they replace -- whoever issues them and however small the bitmaps
+// (2^16 bits, 512 threads: the same; plain byte stores: 2.3 ms), 48 a tile 0.35-0.45 ms (profiles/split_sketch_variants_2026-10-19.log).  The
+// price is the slice's own sampling error: 88 000 rows of 22.6 M are sqrt(88 000) = 0.34 % (one sigma) from a 256th of the total, where the
+// launch's 64th is 0.17 % -- neither is in the margin (the block's six sigma + 32 ranks is), and what an underestimate costs is the retry.
+// The extraction kernel's workgroups set their bits in the copy of their own XCD (blockIdx & 7: atomics of different XCDs on one line meet in
+// no common cache before the kernel ends); sketch_count_kernel counts the zero bits of the OR of the copies.
+constexpr int SKETCH_M = 18, SKETCH_COPIES = 8;
+constexpr uint32_t SKETCH_WORDS = 1u << (SKETCH_M - 5);                // dwords of one bitmap (32 KB)
+// more than half of a bitmap's bits set: "too many rows to tell".  Not for the estimator's sake (above) -- M ln 2 rows are more than the 32
+// row blocks a region may have can hold (32 x 5 537), so every split the sketch is there to size lies below, and what lies above keeps the
+// count-only launch with its finer splits and its exit to the sorted path
+constexpr double SKETCH_MAX_FILL = 0.5;
+__host__ __device__ inline int sketch_step_log(int logB) { return logB >= 10 ? 8 : logB >= 8 ? 6 : 0; }   // sketch region r = bucket r << step
+__host__ __device__ inline int sketch_regions(int logB) { return 1 << (logB - sketch_step_log(logB)); }
+// 64-bit keys: h = the low 32 bits of H, shift = sketch_shift64: the product's bits [nb - SKETCH_M, nb) depend on the low nb bits of h alone,
+// nb = min(32, hash bits below the bucket bits)
+__host__ __device__ inline int sketch_shift64(int bits, int logB) { return (bits - logB < 32 ? bits - logB : 32) - SKETCH_M; }
+__host__ __device__ inline uint32_t sketch_index64(uint32_t h, int shift) { return ((h * 0x9E3779B1u) >> shift) & ((1u << SKETCH_M) - 1u); }
+inline bool sketch_ok(int bits, int logB) { return bits - logB >= SKETCH_M; }                          // (shorter hashes: no sketch)
+inline size_t sketch_words(int logB) { return (size_t)SKETCH_COPIES * (size_t)sketch_regions(logB) * SKETCH_WORDS; }
+// zeros[r] = zero bits of sketch region r over the OR of the copies
+void launch_sketch_count(const uint32_t *sketch, int logB, uint32_t *zeros, hipStream_t st);
 
 void launch_hist(const ExtractArgs &a, hipStream_t st);
 void launch_scatter(const ExtractArgs &a, hipStream_t st);

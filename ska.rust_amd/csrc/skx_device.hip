@@ -149,6 +149,60 @@ extern "C" void skx_debug_phase_prof(unsigned long long *out, int reset)
 #else
 #define DD_PROF(i) do { } while (0)
 #endif
+// The split sketch (skx_device.h), filled once a staging round's words stand in bucket order: staged indices [lo, hi) of the tile are in
+// s_stage[0 .. hi - lo), and the words of bucket b are the indices s_hist[b] .. s_hist[b + 1] (s_hist[B] = the tile's word count).  The first
+// 512 threads are dealt to the sketch buckets, 2^(9 - log2 of their number) each (128 at 2^10 buckets: four sketch buckets of a dozen words
+// a tile), so a thread has one word at most but for a tile that is one repeat.  sketch_range, BEFORE the round's copy-out, reads the thread's
+// range from s_hist; sketch_set, behind the copy-out's stores, reads the word and issues one OR without a returned value into the bitmap copy
+// of this XCD -- no wave ends its round on two dependent LDS reads that way (worth under 0.1 ms per 1 000 x 5 Mbp; what the ORs cost is their
+// number, whoever issues them: profiles/split_sketch_variants_2026-10-19.log).  The bit: sketch_index64 (skx_device.h); 128-bit words:
+// the SKETCH_M hash bits below the bucket bits, `shift` from the word's bit 0.
+struct SketchRange { uint32_t i, end; };
+__device__ static inline SketchRange sketch_range(const uint32_t *s_hist, uint32_t lo, uint32_t hi, int logB, int tid)
+{
+    const int step = sketch_step_log(logB), tl = 9 - (logB - step);
+    if (tid >= 512) return {0u, 0u};
+    const uint32_t b = ((uint32_t)tid >> tl) << step;
+    uint32_t i0 = s_hist[b], i1 = s_hist[b + 1];
+    i0 = i0 > lo ? i0 : lo; i1 = i1 < hi ? i1 : hi;
+    return {i0 + ((uint32_t)tid & ((1u << tl) - 1u)), i1};
+}
+template <typename W>
+__device__ static inline void sketch_set(const W *s_stage, SketchRange g, uint32_t lo, int logB, int shift, uint32_t *sketch, int tid)
+{
+    if (g.i >= g.end) return;
+    const int nskl = logB - sketch_step_log(logB), tl = 9 - nskl;
+    uint32_t *bm = sketch + ((size_t)(blockIdx.x & 7u) << (nskl + SKETCH_M - 5)) + (size_t)((uint32_t)tid >> tl) * SKETCH_WORDS;
+    for (uint32_t i = g.i; i < g.end; i += 1u << tl) {
+        uint32_t x;
+        if constexpr (sizeof(W) == 8) x = sketch_index64((uint32_t)(s_stage[i - lo] >> 4), shift);
+        else x = (uint32_t)(s_stage[i - lo] >> shift) & ((1u << SKETCH_M) - 1u);
+        atomicOr(&bm[x >> 5], 1u << (x & 31u));
+    }
+}
+// zero bits per sketch region over the OR of the copies: a workgroup per region, 32 KB from each copy
+__global__ __launch_bounds__(256) void sketch_count_kernel(const uint32_t *sketch, int nsk, uint32_t *zeros)
+{
+    __shared__ uint32_t s_sum[4];
+    const uint32_t r = blockIdx.x;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    uint32_t z = 0;
+    for (uint32_t i = threadIdx.x; i < SKETCH_WORDS / 4; i += 256) {
+        u32x4 v = {0u, 0u, 0u, 0u};
+        for (int c = 0; c < SKETCH_COPIES; c++) v |= reinterpret_cast<const u32x4 *>(sketch + ((size_t)c * nsk + r) * SKETCH_WORDS)[i];
+        z += 128u - (uint32_t)(__builtin_popcount(v.x) + __builtin_popcount(v.y) + __builtin_popcount(v.z) + __builtin_popcount(v.w));
+    }
+    for (int d = 32; d > 0; d >>= 1) z += __shfl_down(z, d, 64);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = z;
+    __syncthreads();
+    if (threadIdx.x == 0) zeros[r] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+void launch_sketch_count(const uint32_t *sketch, int logB, uint32_t *zeros, hipStream_t st)
+{
+    const int nsk = sketch_regions(logB);
+    hipLaunchKernelGGL(sketch_count_kernel, dim3((unsigned)nsk), dim3(256), 0, st, sketch, nsk, zeros);
+}
+
 template <bool SCATTER, int TILE, bool HI, int PPT, bool SPLIT, int RMAX>
 __global__ __launch_bounds__(TILE / PPT, SPLIT ? 6 : 1) void extract_kernel(ExtractArgs a)
 {
@@ -385,11 +439,14 @@ __global__ __launch_bounds__(TILE / PPT, SPLIT ? 6 : 1) void extract_kernel(Extr
     typedef uint64_t __attribute__((address_space(1))) *gout_t;
     gout_t out = (gout_t)(uintptr_t)(a.words + span0);
     const uint32_t end0 = total < HALF ? total : HALF;
+    SketchRange skr = {0u, 0u};
+    if (a.sketch) skr = sketch_range(s_hist, 0u, end0, a.logB, tid);
     for (uint32_t i = tid; i < end0; i += NT) {
         const uint64_t w = s_stage[i];
         const uint32_t b = HI ? (uint32_t)(w >> 32) >> bsh_hi : (uint32_t)((w >> 4) >> bshift);
         out[s_base[b] + i] = w;
     }
+    if (a.sketch) sketch_set(s_stage, skr, 0u, a.logB, sketch_shift64(hp.bits, a.logB), a.sketch, tid);
     EXT_PROF(5);
     if (SPLIT && total > HALF) {
         __syncthreads();
@@ -398,11 +455,13 @@ __global__ __launch_bounds__(TILE / PPT, SPLIT ? 6 : 1) void extract_kernel(Extr
         for (int j = 0; j < PPT; j++) if (sidx_[j] - HALF < HALF) s_stage[sidx_[j] - HALF] = wv[j];
         __syncthreads();
         EXT_PROF(7);
+        if (a.sketch) skr = sketch_range(s_hist, HALF, total, a.logB, tid);
         for (uint32_t i = HALF + tid; i < total; i += NT) {
             const uint64_t w = s_stage[i - HALF];
             const uint32_t b = HI ? (uint32_t)(w >> 32) >> bsh_hi : (uint32_t)((w >> 4) >> bshift);
             out[s_base[b] + i] = w;
         }
+        if (a.sketch) sketch_set(s_stage, skr, HALF, a.logB, sketch_shift64(hp.bits, a.logB), a.sketch, tid);
     }
     EXT_PROF(8);
     if (dropped) *a.overflow = 1;

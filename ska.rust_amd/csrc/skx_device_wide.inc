@@ -288,11 +288,14 @@ __global__ __launch_bounds__(WNT, SKX_WIDE_WPS) void extract_wide_kernel(Extract
         }
         __syncthreads();
         const uint32_t n = total - lo < STAGE ? total - lo : STAGE;
+        SketchRange skr = {0u, 0u};                          // the split sketch, as in extract_kernel
+        if (a.sketch) skr = sketch_range(s_hist, lo, lo + n, a.logB, tid);
         for (uint32_t i = tid; i < n; i += WNT) {
             const u128 w = s_stage[i];
             const uint32_t b = wide_bucket(w, bshift);
             words[s_base[b] + lo + i] = w;
         }
+        if (a.sketch) sketch_set(s_stage, skr, lo, a.logB, bshift + 4 - SKETCH_M, a.sketch, tid);      // (index bits: the hash bits below the bucket bits)
         if (lo + STAGE < total) __syncthreads();
         WIDE_PROF(3 + lo / STAGE);
     }

@@ -123,6 +123,9 @@ struct skx_dictset {
     bool sorted = true;
     uint32_t region_cap = 0; uint64_t maxlen = 0;        // what the later sort needs: words per region, the longest record stream
     std::vector<uint64_t> raw_total;     // windows per sample (raw form): 0 = the sample has no valid sequence
+    // the split sketch (skx_device.h) of a dictset the single-pass scatter kernel filled: [8 copies][sketch_regions(logB)][2^18 bits]; none
+    // (p == nullptr) for every other dictset -- sorted forms, read sets, the exact two-pass layout, hashes shorter than logB + 18 bits
+    skx::DevBuf<uint32_t> sketch;
     skx::DictView view() const { return skx::DictView{words.p, off.p, ucnt.p, n, logB, wide() ? wh.bits : hp.bits, sidx.p, sb}; }
 };
 
