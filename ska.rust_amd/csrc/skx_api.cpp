@@ -1,5 +1,6 @@
 // skx_api.cpp -- the C ABI (include/skx.h): host orchestration of the gfx950 kernels for build -> merge -> filter and the .skf
-// life-cycle operations (cov / map / .skf files: skx_api_io.cpp; sequence files onto the device: skx_build_files.cpp; distance: skx_distance.cpp).
+// life-cycle operations (dictset construction: skx_dictset.cpp; cov / map / .skf files: skx_api_io.cpp; sequence files onto the device:
+// skx_build_files.cpp; distance: skx_distance.cpp).
 // No CPU fallback exists: without a usable HIP device every compute entry point fails with SKX_ENODEV.
 #include "skx_internal.h"
 #include "../../include/skx_host.h"
@@ -296,425 +297,7 @@ struct KernelTimer {       // StageTimer's bracket around one kernel inside a st
         float ms = 0; if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *slot += ms;
     }
 };
-int ilog2_ceil(uint64_t x) { int l = 0; while ((1ull << l) < x) l++; return l; }
-constexpr uint32_t LDS_TABLE_MAX = 18000;     // slots (+ pad) of 8 B must stay below 160 KiB
-constexpr uint32_t LDS_SORT_MAX = 6144;       // words per region of the counting sort (24 per thread in registers)
-constexpr uint32_t LDS_SORT_MAX_WIDE = 4096;  // 128-bit path (16 per thread)
 }  // namespace
-
-// ------------------------------------------------------------------------------------------ dictset
-extern "C" void skx_dictset_free(skx_dictset *d) { delete d; }
-extern "C" int skx_dictset_nsamples(const skx_dictset *d) { return d->n; }
-extern "C" int skx_dictset_key_bits(const skx_dictset *d) { return d->key_bits; }
-
-// The passing windows' packed words of every sample (reads_sample_words) -> (sample, bucket) regions like an assembly's -> the same dedupe
-// kernel: sorted, folded, sub-indexed regions, so union / assemble treat reads and assemblies alike.  SKF_NOT_TAKEN: regions the LDS
-// sort cannot hold (the sort-based form takes the batch).
-int skx::reads_words_to_dictset(skx_ctx *ctx, std::vector<DevBuf<uint64_t>> &wl, std::vector<DevBuf<uint64_t>> &wh2, const std::vector<uint64_t> &cnt,
-                                int k, int rc, skx_dictset **out)
-{
-    const int n = (int)wl.size();
-    hipStream_t st = ctx->stream;
-    const bool wide_r = k > 31;
-    const int wpk_r = wide_r ? 2 : 1, kbits = 2 * (k - 1);
-    uint64_t maxn = 0;
-    for (auto c : cnt) maxn = std::max(maxn, c);
-    const uint64_t per = wide_r ? 2500 : 3500, lds_max = wide_r ? LDS_SORT_MAX_WIDE : LDS_SORT_MAX;
-    int logB = std::min({ilog2_ceil((maxn + per - 1) / per), kbits, MAX_LOGB});
-    if (logB < 0) logB = 0;
-    std::unique_ptr<skx_dictset> d(new skx_dictset());
-    d->ctx = ctx; d->n = n; d->k = k; d->rc = rc; d->logB = logB; d->hp = make_hash_params(std::min(k, 31)); d->wh = make_wide_hash(k);
-    d->key_bits = wide_r ? 128 : 64;
-    const uint64_t nreg = (uint64_t)n << logB;
-    SKX_TRY(d->raw.alloc(nreg)); SKX_TRY(d->ucnt.alloc(nreg)); SKX_TRY(d->off.alloc(nreg + 1)); SKX_TRY(d->sidx.alloc(nreg * skx::SUBIDX));
-    d->sb = std::min(4, kbits - logB);
-    SKX_TRY(d->raw.zero(st));
-    for (int s = 0; s < n; s++) launch_words_regions(true, wl[s].p, wide_r ? wh2[s].p : nullptr, cnt[s], kbits, logB, (uint64_t)s << logB, d->raw.p, nullptr, nullptr, nullptr, st);
-    DevBuf<uint32_t> d_max, cursor; SKX_TRY(d_max.alloc(1)); SKX_TRY(cursor.alloc(nreg)); SKX_TRY(cursor.zero(st));
-    launch_scan_u32(d->raw.p, d->off.p, nreg, d_max.p, st);
-    uint64_t total = 0; uint32_t max_raw = 0;
-    SKX_HIP(hipMemcpyAsync(&total, d->off.p + nreg, 8, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipMemcpyAsync(&max_raw, d_max.p, 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    if (max_raw > lds_max) { if (getenv("SKX_DEBUG")) fprintf(stderr, "[skx] reads: region of %u words, batch left to the sort-based form\n", max_raw); return SKF_NOT_TAKEN; }   // e.g. min_count 2 on deep reads: every repeat occurrence is a word
-    SKX_TRY(d->words.alloc(std::max<uint64_t>(total, 1) * wpk_r));
-    for (int s = 0; s < n; s++) {
-        launch_words_regions(false, wl[s].p, wide_r ? wh2[s].p : nullptr, cnt[s], kbits, logB, (uint64_t)s << logB, nullptr, d->off.p, cursor.p, d->words.p, st);
-        wl[s].release(); wh2[s].release();
-    }
-    const uint32_t cap = std::max<uint32_t>(512, (uint32_t)std::min<uint64_t>(((uint64_t)max_raw + 255) / 256 * 256, lds_max));
-    DevBuf<int> d_flag2; SKX_TRY(d_flag2.alloc(1)); SKX_TRY(d_flag2.zero(st));
-    SKX_HIP(hipMemsetAsync(d->sidx.p, 0xFF, nreg * skx::SUBIDX * sizeof(uint16_t), st));
-    { StageTimer t(ctx, &ctx->tm.dedupe);
-      if (wide_r) launch_dedupe_wide((u128 *)d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, cap, kbits - logB, d_flag2.p, d->sidx.p, d->sb, st);
-      else launch_dedupe_mb(d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, cap, d->hp.bits - logB, d_flag2.p, d->sidx.p, d->sb, st); }
-    int overflow = 0;
-    std::vector<uint32_t> ucnt(nreg);
-    SKX_HIP(hipMemcpyAsync(&overflow, d_flag2.p, 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipMemcpyAsync(ucnt.data(), d->ucnt.p, nreg * 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    SKX_HIP(hipGetLastError());
-    if (overflow) { if (getenv("SKX_DEBUG")) fprintf(stderr, "[skx] reads: dedupe overflow, batch left to the sort-based form\n"); return SKF_NOT_TAKEN; }
-    d->sample_size.assign(n, 0);
-    for (int s = 0; s < n; s++) for (uint64_t b = 0; b < (1ull << logB); b++) d->sample_size[s] += ucnt[((uint64_t)s << logB) + b];
-    *out = d.release();
-    return SKX_OK;
-
-}
-
-// the regions of a dictset sorted and folded in place (a sample's SkaDict per bucket: dedupe_mb_kernel / dedupe_wide_kernel, the table
-// form for repeat-rich regions); *overflow != 0: a region does not fit, the caller builds again with more buckets
-static int dictset_sort_flat(skx_ctx *ctx, skx_dictset *d);
-static int dedupe_regions(skx_ctx *ctx, skx_dictset *d, uint32_t lds_cap, uint64_t maxlen, int *overflow_out, std::vector<uint32_t> &ucnt)
-{
-    hipStream_t st = ctx->stream;
-    const bool wide = d->wide();
-    const int logB = d->logB;
-    const uint64_t nreg = (uint64_t)d->n << logB;
-    const HashParams hp = d->hp;
-    const int key_bits_used = 2 * (d->k - 1);
-    DevBuf<int> d_flag; SKX_TRY(d_flag.alloc(1));
-    {
-    // LDS capacity (words) of the per-region counting sort: 12 B per word, <= 160 KiB
-    uint32_t cap = std::max<uint32_t>(512, (uint32_t)std::min<uint64_t>(((uint64_t)lds_cap + 255) / 256 * 256, wide ? LDS_SORT_MAX_WIDE : LDS_SORT_MAX));
-    // windows per region are Poisson around len / B: all but ~5 in 10 000 regions stay below mean + 3.3 sigma, which may need a
-    // smaller launch shape than the regions' capacity does (launch_dedupe_mb)
-    const double mean_r = (double)(maxlen >> logB) + 1.0;
-    const uint32_t typical = wide ? 0u : (uint32_t)(mean_r + 3.3 * std::sqrt(mean_r) + 1.0);
-    DevBuf<uint32_t> d_big;
-    if (typical) SKX_TRY(d_big.alloc(nreg + 1));
-    SKX_TRY(d_flag.zero(st));
-    SKX_HIP(hipMemsetAsync(d->sidx.p, 0xFF, nreg * skx::SUBIDX * sizeof(uint16_t), st));     // 0xFFFF = sub-range without words
-    { StageTimer t(ctx, &ctx->tm.dedupe);
-      if (wide) launch_dedupe_wide((u128 *)d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, cap, key_bits_used - logB, d_flag.p, d->sidx.p, d->sb, st);
-      else launch_dedupe_mb(d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, cap, hp.bits - logB, d_flag.p, d->sidx.p, d->sb, st, typical, d_big.p, 0); }
-    int overflow = 0;
-    SKX_HIP(hipMemcpyAsync(&overflow, d_flag.p, 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    for (uint32_t from = dedupe_spill_grid(); !wide && (overflow & 4); from += dedupe_spill_grid()) {     // more listed regions than one grid of the second stage
-        int keep = overflow & ~4;
-        SKX_HIP(hipMemcpyAsync(d_flag.p, &keep, 4, hipMemcpyHostToDevice, st));
-        { StageTimer t(ctx, &ctx->tm.dedupe); launch_dedupe_mb(d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, cap, hp.bits - logB, d_flag.p, d->sidx.p, d->sb, st, typical, d_big.p, from); }
-        SKX_HIP(hipMemcpyAsync(&overflow, d_flag.p, 4, hipMemcpyDeviceToHost, st));
-        SKX_HIP(hipStreamSynchronize(st));
-    }
-    if (getenv("SKX_DEBUG") && typical) {
-        uint32_t listed = 0;
-        SKX_HIP(hipMemcpy(&listed, d_big.p, 4, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[skx] dedupe: typical region %u words, capacity %u; %u of %llu regions above the typical launch shape\n", typical, cap, listed, (unsigned long long)nreg);
-    }
-    if (!wide && overflow == 2) {
-        // regions beyond the counting sort's capacity (repeat-rich buckets): table-based dedupe, only distinct keys must fit
-        SKX_TRY(d_flag.zero(st));
-        { StageTimer t(ctx, &ctx->tm.dedupe); launch_dedupe(d->words.p, d->off.p, d->raw.p, d->ucnt.p, nreg, LDS_TABLE_MAX, hp.bits - logB, d_flag.p, cap, d->sidx.p, d->sb, st); }
-        SKX_HIP(hipMemcpyAsync(&overflow, d_flag.p, 4, hipMemcpyDeviceToHost, st));
-    }
-    ucnt.resize(nreg);
-    SKX_HIP(hipMemcpyAsync(ucnt.data(), d->ucnt.p, nreg * 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    SKX_HIP(hipGetLastError());
-    *overflow_out = overflow;
-    return SKX_OK;
-    }
-}
-
-// Samples whose regions are beyond the per-region LDS sort (assemblies above ~5 Mbp keep 2^10 regions that grow with them, so that the
-// extraction kernel's (tile, bucket) chunks stay whole lines: round 6): every sample's words as ONE sorted, folded list -- the form the
-// sort-based read-set path leaves (logB = 0), which every consumer of sorted dictionaries takes.  Radix sort + fold (skx_prims, skx_reads.hip).
-static int dictset_sort_flat(skx_ctx *ctx, skx_dictset *d)
-{
-    hipStream_t st = ctx->stream;
-    const bool wide = d->wide();
-    const int wpk = wide ? 2 : 1, n = d->n;
-    const uint64_t B = 1ull << d->logB, nreg = (uint64_t)n << d->logB;
-    std::vector<uint32_t> raw(nreg);
-    SKX_HIP(hipMemcpyAsync(raw.data(), d->raw.p, nreg * 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    std::vector<DevBuf<uint64_t>> lists(n);
-    std::vector<uint64_t> sizes(n, 0), offs(n + 1, 0), dst(B);
-    DevBuf<uint64_t> d_dst, lo, hi;
-    SKX_TRY(d_dst.alloc(B));
-    for (int s = 0; s < n; s++) {
-        uint64_t m = 0;
-        for (uint64_t b = 0; b < B; b++) { dst[b] = m; m += raw[(uint64_t)s * B + b]; }
-        if (m == 0) continue;
-        if (lo.n < m) { SKX_TRY(lo.alloc(m + m / 8)); if (wide) SKX_TRY(hi.alloc(m + m / 8)); }
-        SKX_HIP(hipMemcpyAsync(d_dst.p, dst.data(), B * 8, hipMemcpyHostToDevice, st));
-        launch_gather_regions(d->words.p, d->off.p, d->raw.p, d_dst.p, (uint64_t)s * B, B, wpk, lo.p, wide ? hi.p : nullptr, st);
-        SKX_TRY(sort_fold_words(ctx, lo.p, wide ? hi.p : nullptr, m, lists[s], &sizes[s]));      // (returns with the stream idle: dst may be refilled)
-        if (sizes[s] > 0xFFFFFFFFull) { set_error("sample too large"); return SKX_EUNSUP; }
-    }
-    for (int s = 0; s < n; s++) offs[s + 1] = offs[s] + sizes[s];
-    lo.release(); hi.release();
-    DevBuf<uint64_t> words, off; DevBuf<uint32_t> rawn, ucnt;
-    SKX_TRY(words.alloc(offs[n] * wpk)); SKX_TRY(off.alloc(n + 1)); SKX_TRY(rawn.alloc(n)); SKX_TRY(ucnt.alloc(n));
-    std::vector<uint32_t> uc(n);
-    for (int s = 0; s < n; s++) {
-        uc[s] = (uint32_t)sizes[s];
-        if (sizes[s]) SKX_HIP(hipMemcpyAsync(words.p + offs[s] * wpk, lists[s].p, sizes[s] * 8 * wpk, hipMemcpyDeviceToDevice, st));
-    }
-    SKX_HIP(hipMemcpyAsync(off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    SKX_HIP(hipMemcpyAsync(ucnt.p, uc.data(), n * 4, hipMemcpyHostToDevice, st));
-    SKX_HIP(hipMemcpyAsync(rawn.p, uc.data(), n * 4, hipMemcpyHostToDevice, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    SKX_HIP(hipGetLastError());
-    d->words = std::move(words); d->off = std::move(off); d->raw = std::move(rawn); d->ucnt = std::move(ucnt);
-    d->sidx.release(); d->sb = 0; d->logB = 0;
-    d->sample_size = sizes;
-    d->sorted = true; d->sketch.release();                      // (the sketch sizes the append pass, which reads unsorted regions only)
-    return SKX_OK;
-}
-
-int skx::dictset_sort(skx_dictset *d)
-{
-    if (d->sorted) return SKX_OK;
-    skx_ctx *ctx = d->ctx;
-    SKX_HIP(hipSetDevice(ctx->device));
-    if (d->region_cap > (d->wide() ? LDS_SORT_MAX_WIDE : LDS_SORT_MAX)) return dictset_sort_flat(ctx, d);
-    int overflow = 0;
-    std::vector<uint32_t> ucnt;
-    SKX_TRY(dedupe_regions(ctx, d, d->region_cap, d->maxlen, &overflow, ucnt));
-    if (overflow) { set_error("internal: a fixed-capacity region did not fit the counting sort (%d)", overflow); return SKX_EUNSUP; }
-    d->sample_size.assign(d->n, 0);
-    for (int s = 0; s < d->n; s++) for (uint64_t b = 0; b < (1ull << d->logB); b++) d->sample_size[s] += ucnt[((uint64_t)s << d->logB) + b];
-    d->sorted = true; d->sketch.release();
-    return SKX_OK;
-}
-
-// The region layout of an assembly batch from its longest sample: how many buckets a sample's words are split into, and the fixed capacity of a region.
-uint32_t skx::region_capacity(uint64_t maxlen, int logB)
-{
-    // hashed buckets are Poisson around len/B: 20 % + 256 words of head-room covers ordinary repeat content
-    const uint64_t mean = (maxlen >> logB) + 1;
-    return (uint32_t)std::min<uint64_t>(((mean + mean / 5 + 256) + 63) / 64 * 64, 0x7FFFFFFFull);
-}
-RegionLayout skx::region_layout(uint64_t maxlen, int k)
-{
-    const bool wide = k > 31;
-    // windows per bucket (upper bound): the 64-bit dedupe sorts up to 6 144 words per region in LDS and the regions get 20 % + 256
-    // words of head-room, so 4 900 is the largest mean that fits -- and the largest buckets give the scatter its widest chunks
-    // (128-bit keys: 3 200, so that a region's fixed capacity -- 20 % + 256 above the mean -- stays within the 4 096 words of the wide counting sort
-    // and the samples can stay as extracted for the append pass whatever their length)
-    uint64_t per_region = wide ? 3200 : 4900;
-    if (knob("per_region") > 0) per_region = (uint64_t)knob("per_region");       // (measurements: 9800 = 2^9 regions for 5 Mbp samples, 2450 = 2^11)
-    // Longer samples (round 6): the bucket count stops growing at the 5 Mbp shape (2^10 regions; 2^11 for 128-bit keys) and the regions grow
-    // instead -- the extraction kernel's (tile, bucket) chunks stay whole lines (with regions capped at 4 900 words a 20 Mbp sample took 13 ps per
-    // base against 2.5, a 40 Mbp one 43, and beyond that the assembly kernels were left altogether), the append pass reads regions of any
-    // size unsorted (2^(logQ - logB) row blocks per region: up to 32 readers a region), and who asks for sorted dictionaries of such samples
-    // gets the flat sorted form (dictset_sort_flat).  Beyond 32 row blocks per region the buckets grow again (to 2^13: ~1.3 Gbp).
-    const int need = std::max(0, ilog2_ceil((maxlen + per_region - 1) / per_region));
-    const int base_logB = knob("per_region") > 0 ? std::min(need, MAX_LOGB) : (wide ? 11 : 10);
-    const bool grow_regions = !knob("small_regions");
-    if ((grow_regions ? need - 5 : need) > MAX_LOGB) return {-1, 0};
-    const int logB = std::max(0, std::min({grow_regions && need > base_logB ? std::max(base_logB, need - 5) : need, 2 * (k - 1), MAX_LOGB}));
-    return {logB, region_capacity(maxlen, logB)};
-}
-
-static int dictset_build_device(skx_ctx *ctx, const std::vector<const uint8_t *> &seqs, const std::vector<const uint8_t *> &quals,
-                                const std::vector<uint64_t> &lens, int k, int rc, const skx_qual *q, skx_dictset **out)
-{
-    const int n = (int)seqs.size();
-    hipStream_t st = ctx->stream;
-    bool any_qual = false;
-    for (auto p : quals) any_qual |= p != nullptr;
-    // reads: per-sample quality gates + KmerFilter (skx_reads.hip); the dictset is then one sorted region per sample.  The same
-    // sort-based path takes assemblies too large for the bucketed one (more than 2^MAX_LOGB regions' worth of windows: a 40 Mbp
-    // sample and up, to 4 Gbp), with the filters switched off.
-    auto build_sorted = [&]() -> int {
-        const bool wide_r = k > 31;
-        const int wpk_r = wide_r ? 2 : 1;
-        std::vector<DevBuf<uint64_t>> lists(n);
-        std::vector<uint64_t> sizes(n, 0), offs(n + 1, 0);
-        for (int s = 0; s < n; s++) {
-            skx_qual qs = q ? *q : skx_qual{5, 20, SKX_QUAL_STRICT};
-            if (!quals[s]) { qs.min_count = 0; qs.qual_filter = SKX_QUAL_NOFILTER; }        // FASTA sample in a mixed batch: no filtering
-            SKX_TRY(reads_sample_dict(ctx, seqs[s], quals[s], lens[s], k, rc, qs, lists[s], &sizes[s]));
-            if (sizes[s] > 0xFFFFFFFFull) { set_error("sample too large"); return SKX_EUNSUP; }
-            offs[s + 1] = offs[s] + sizes[s];
-        }
-        std::unique_ptr<skx_dictset> d(new skx_dictset());
-        d->ctx = ctx; d->n = n; d->k = k; d->rc = rc; d->logB = 0; d->hp = make_hash_params(std::min(k, 31)); d->wh = make_wide_hash(k);
-        d->key_bits = wide_r ? 128 : 64;
-        SKX_TRY(d->words.alloc(offs[n] * wpk_r)); SKX_TRY(d->off.alloc(n + 1)); SKX_TRY(d->raw.alloc(n)); SKX_TRY(d->ucnt.alloc(n));
-        std::vector<uint32_t> uc(n);
-        for (int s = 0; s < n; s++) {
-            uc[s] = (uint32_t)sizes[s];
-            if (sizes[s]) SKX_HIP(hipMemcpyAsync(d->words.p + offs[s] * wpk_r, lists[s].p, sizes[s] * 8 * wpk_r, hipMemcpyDeviceToDevice, st));
-        }
-        SKX_HIP(hipMemcpyAsync(d->off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-        SKX_HIP(hipMemcpyAsync(d->ucnt.p, uc.data(), n * 4, hipMemcpyHostToDevice, st));
-        SKX_HIP(hipMemcpyAsync(d->raw.p, uc.data(), n * 4, hipMemcpyHostToDevice, st));
-        SKX_HIP(hipStreamSynchronize(st));
-        d->sample_size = sizes;
-        *out = d.release();
-        return SKX_OK;
-    };
-    // The same samples through the engine's own kernels (skx_reads2.hip): the windows that pass the gates and the count filter
-    // come back as packed words, which go into (sample, bucket) regions like an assembly's and through the same dedupe kernel
-    // -- sorted, folded, sub-indexed regions, so union / assemble treat reads and assemblies alike.  A sample the partition
-    // kernels do not take (or regions the LDS sort cannot hold) sends the batch to the sort-based form above.
-    auto build_bucketed_reads = [&]() -> int {
-        std::vector<DevBuf<uint64_t>> wl(n), wh2(n);
-        std::vector<uint64_t> cnt(n, 0);
-        uint64_t maxn = 0;
-        for (int s = 0; s < n; s++) {
-            skx_qual qs = q ? *q : skx_qual{5, 20, SKX_QUAL_STRICT};
-            if (!quals[s]) { qs.min_count = 0; qs.qual_filter = SKX_QUAL_NOFILTER; }        // FASTA sample in a mixed batch: no filtering
-            const int r = reads_sample_words(ctx, seqs[s], quals[s], lens[s], k, rc, qs, wl[s], wh2[s], &cnt[s]);
-            if (r != SKX_OK) return r;                                                       // SKF_NOT_TAKEN included
-            maxn = std::max(maxn, cnt[s]);
-        }
-        return reads_words_to_dictset(ctx, wl, wh2, cnt, k, rc, out);
-    };
-    auto build_reads = [&]() -> int {
-        if (!knob("reads_sort")) {
-            const int r = build_bucketed_reads();
-            if (r != SKF_NOT_TAKEN) return r;
-        }
-        return build_sorted();
-    };
-    const bool wide = k > 31;                                   // lib.rs:592: u64 for k <= 31, u128 above
-    uint64_t maxlen = 0;
-    for (auto l : lens) maxlen = std::max(maxlen, l);
-    HashParams hp = make_hash_params(std::min(k, 31));
-    WideHash wh = make_wide_hash(k);
-    const int key_bits_used = 2 * (k - 1);
-    if (any_qual) return build_reads();
-    int logB = region_layout(maxlen, k).logB;
-    if (logB < 0) return build_reads();
-
-    DevBuf<const uint8_t *> d_seqs, d_quals;
-    DevBuf<uint64_t> d_lens;
-    SKX_TRY(d_seqs.alloc(n)); SKX_TRY(d_lens.alloc(n));
-    SKX_HIP(hipMemcpyAsync(d_seqs.p, seqs.data(), n * sizeof(void *), hipMemcpyHostToDevice, st));
-    SKX_HIP(hipMemcpyAsync(d_lens.p, lens.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (any_qual) { SKX_TRY(d_quals.alloc(n)); SKX_HIP(hipMemcpyAsync(d_quals.p, quals.data(), n * sizeof(void *), hipMemcpyHostToDevice, st)); }
-    DevBuf<int> d_flag;
-    SKX_TRY(d_flag.alloc(1));
-
-    bool exact = false;        // single pass with fixed-capacity regions first; exact two-pass layout if a region overflows
-    for (;;) {
-        std::unique_ptr<skx_dictset> d(new skx_dictset());
-        d->ctx = ctx; d->n = n; d->k = k; d->rc = rc; d->logB = logB; d->hp = hp; d->wh = wh; d->key_bits = wide ? 128 : 64;
-        const int wpk = wide ? 2 : 1;
-        const int tile_bases = wide ? extract_tile_bases_wide() : extract_tile_bases(logB);
-        const uint64_t nreg = (uint64_t)n << logB;
-        SKX_TRY(d->raw.alloc(nreg)); SKX_TRY(d->ucnt.alloc(nreg)); SKX_TRY(d->off.alloc(nreg + 1));
-        SKX_TRY(d->sidx.alloc(nreg * skx::SUBIDX)); d->sb = std::min(4, (wide ? key_bits_used : hp.bits) - logB);
-        SKX_TRY(d->raw.zero(st)); SKX_TRY(d_flag.zero(st));
-
-        ExtractArgs a{};
-        a.seqs = d_seqs.p; a.quals = any_qual ? d_quals.p : nullptr; a.lens = d_lens.p; a.n_samples = n;
-        a.tiles_max = (int)((maxlen + tile_bases - 1) / tile_bases);
-        a.k = k; a.rc = rc; a.min_qual = q ? q->min_qual : 0; a.qual_filter = q ? q->qual_filter : 0;
-        a.logB = logB; a.hp = hp; a.wh = wh; a.overflow = d_flag.p;
-        uint32_t lds_cap;
-        if (!exact) {
-            const uint32_t region_cap = region_capacity(maxlen, logB);
-            launch_fill_offsets(d->off.p, nreg, region_cap, st);
-            SKX_TRY(d->words.alloc(nreg * (uint64_t)region_cap * wpk + 2048));      // (+ slack: the append pass reads whole chunks of up to 12 KB)
-            // the split sketch, zeroed with the regions' fills: what append_pass sizes its row blocks from instead of a count-only launch
-            if (sketch_ok(wide ? wh.bits : hp.bits, logB)) { SKX_TRY(d->sketch.alloc(sketch_words(logB))); SKX_TRY(d->sketch.zero(st)); a.sketch = d->sketch.p; }
-            { StageTimer t(ctx, &ctx->tm.scatter); a.hist = d->raw.p; a.off = d->off.p; a.words = d->words.p; a.capacity = region_cap;
-              if (wide) launch_scatter_wide(a, st); else launch_scatter(a, st); }
-            int over = 0;
-            SKX_HIP(hipMemcpyAsync(&over, d_flag.p, 4, hipMemcpyDeviceToHost, st));
-            SKX_HIP(hipStreamSynchronize(st));
-            if (over) { exact = true; continue; }
-            lds_cap = region_cap;
-        } else {
-            DevBuf<uint32_t> d_cursor, d_max;
-            SKX_TRY(d_cursor.alloc(nreg)); SKX_TRY(d_max.alloc(1)); SKX_TRY(d_cursor.zero(st));
-            { StageTimer t(ctx, &ctx->tm.hist); a.hist = d->raw.p; if (wide) launch_hist_wide(a, st); else launch_hist(a, st); }
-            launch_scan_u32(d->raw.p, d->off.p, nreg, d_max.p, st);
-            uint64_t total = 0; uint32_t max_raw = 0;
-            SKX_HIP(hipMemcpyAsync(&total, d->off.p + nreg, 8, hipMemcpyDeviceToHost, st));
-            SKX_HIP(hipMemcpyAsync(&max_raw, d_max.p, 4, hipMemcpyDeviceToHost, st));
-            SKX_HIP(hipStreamSynchronize(st));
-            SKX_TRY(d->words.alloc(total * wpk));
-            { StageTimer t(ctx, &ctx->tm.scatter); a.hist = d_cursor.p; a.off = d->off.p; a.words = d->words.p; a.capacity = 0xFFFFFFFFu;
-              if (wide) launch_scatter_wide(a, st); else launch_scatter(a, st); }
-            lds_cap = max_raw;
-        }
-        // Assemblies whose regions kept their fixed capacity stay as the extraction kernel left them (both key widths): MergeSkaDict::append
-        // (skx_append.hip) reads them unsorted, and the sorted, folded form (a sample's SkaDict) is made when something asks for it
-        // (skx::dictset_sort: skx_dictset_size / _export, the key-set union of a sharded job).  A fixed-capacity region always fits
-        // the counting sort (region_cap <= LDS_SORT_MAX), so that later sort cannot come back for a finer split.
-        d->maxlen = maxlen; d->region_cap = lds_cap;
-        const bool big_regions = lds_cap > (wide ? LDS_SORT_MAX_WIDE : LDS_SORT_MAX);
-        if (!exact && !any_qual && (big_regions || (!knob("sorted_dicts") && !(wide && knob("sorted_wide"))))) {
-            DevBuf<unsigned long long> d_tot; SKX_TRY(d_tot.alloc(n));
-            launch_region_totals(d->raw.p, n, logB, d_tot.p, st);
-            d->raw_total.resize(n);
-            SKX_HIP(hipMemcpyAsync(d->raw_total.data(), d_tot.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-            SKX_HIP(hipStreamSynchronize(st));
-            SKX_HIP(hipGetLastError());
-            d->sorted = false;
-            // (regions beyond the per-region sort stay as extracted whatever the knobs say -- that is what keeps the extraction's chunks whole --
-            // and the knobs that ask for sorted dictionaries get them from the flat sort)
-            if (big_regions && (knob("sorted_dicts") || (wide && knob("sorted_wide")))) SKX_TRY(dictset_sort(d.get()));
-            *out = d.release();
-            return SKX_OK;
-        }
-        if (big_regions) {
-            // an exact layout (a region overflowed its fixed capacity: repeat content) of regions the LDS sort cannot hold: the flat sort
-            d->sorted = false;
-            SKX_TRY(dictset_sort(d.get()));
-            *out = d.release();
-            return SKX_OK;
-        }
-        int overflow = 0;
-        std::vector<uint32_t> ucnt;
-        SKX_TRY(dedupe_regions(ctx, d.get(), lds_cap, maxlen, &overflow, ucnt));
-        d->sketch.release();                                                          // sorted dictionaries: no sketch
-        if (overflow) {
-            if (logB >= std::min(key_bits_used, MAX_LOGB)) return build_reads();       // repeat content beyond every region size
-            logB++;
-            continue;
-        }
-        d->sample_size.assign(n, 0);
-        for (int s = 0; s < n; s++) for (uint64_t b = 0; b < (1ull << logB); b++) d->sample_size[s] += ucnt[((uint64_t)s << logB) + b];
-        *out = d.release();
-        return SKX_OK;
-    }
-}
-
-extern "C" int skx_dictset_build(skx_ctx *ctx, const skx_stream *samples, int n, int on_device, int k, int rc, const skx_qual *q, skx_dictset **out)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !samples || n <= 0 || !out) { set_error("bad arguments"); return SKX_EINVAL; }
-    SKX_TRY(check_k(k));
-    SKX_HIP(hipSetDevice(ctx->device));
-    std::vector<const uint8_t *> seqs(n), quals(n, nullptr);
-    std::vector<uint64_t> lens(n);
-    std::vector<DevBuf<uint8_t>> own;
-    if (on_device) {
-        for (int i = 0; i < n; i++) {
-            if (((uintptr_t)samples[i].seq & 15) || ((uintptr_t)samples[i].qual & 15)) { set_error("device record streams must be 16-byte aligned"); return SKX_EINVAL; }
-            seqs[i] = samples[i].seq; quals[i] = samples[i].qual; lens[i] = samples[i].len;
-        }
-    } else {
-        own.resize(2 * (size_t)n);
-        for (int i = 0; i < n; i++) {
-            lens[i] = samples[i].len;
-            SKX_TRY(own[2 * i].alloc(samples[i].len + 16));
-            SKX_HIP(hipMemcpyAsync(own[2 * i].p, samples[i].seq, samples[i].len, hipMemcpyHostToDevice, ctx->stream));
-            seqs[i] = own[2 * i].p;
-            if (samples[i].qual) {
-                SKX_TRY(own[2 * i + 1].alloc(samples[i].len + 16));
-                SKX_HIP(hipMemcpyAsync(own[2 * i + 1].p, samples[i].qual, samples[i].len, hipMemcpyHostToDevice, ctx->stream));
-                quals[i] = own[2 * i + 1].p;
-            }
-        }
-    }
-    skx_dictset *d = nullptr;
-    SKX_TRY(dictset_build_device(ctx, seqs, quals, lens, k, rc, q, &d));
-    for (int s = 0; s < n; s++)
-        if ((d->sorted ? d->sample_size[s] : d->raw_total[s]) == 0) { set_error("sample %d has no valid sequence", s); delete d; return SKX_EEMPTY; }
-    *out = d;
-    return SKX_OK;
-    });
-}
 
 // Test hook (not part of the drop-in boundary): FASTQ text through the device framing (skx_fastq.hip), the planes expanded to the two record
 // streams the read-set kernels would see -- sequence A C T G N '\n', quality ' ' (passes) / '!' (fails) / '\n'.  seq / qual: room for len / 2 + 64.
@@ -820,57 +403,6 @@ extern "C" int skx_read_records(const char *file1, const char *file2, double pro
     memcpy(s, h.seq.data(), n);
     if (q) memcpy(q, h.qual.data(), n);
     *seq = s; *qual = q; *len = n;
-    return SKX_OK;
-    });
-}
-
-extern "C" int skx_dictset_size(skx_dictset *d, int sample, uint64_t *n)
-{
-    return skx_guarded([&]() -> int {
-    if (!d || sample < 0 || sample >= d->n) { set_error("bad sample index"); return SKX_EINVAL; }
-    SKX_TRY(dictset_sort(d));
-    *n = d->sample_size[sample];
-    return SKX_OK;
-    });
-}
-
-extern "C" int skx_dictset_export(skx_dictset *d, int sample, skx_key *keys, uint8_t *bases, uint64_t cap)
-{
-    return skx_guarded([&]() -> int {
-    if (!d || sample < 0 || sample >= d->n) { set_error("bad sample index"); return SKX_EINVAL; }
-    skx_ctx *ctx = d->ctx; hipStream_t st = ctx->stream;
-    SKX_HIP(hipSetDevice(ctx->device));
-    SKX_TRY(dictset_sort(d));
-    const uint64_t B = 1ull << d->logB, sz = d->sample_size[sample];
-    if (cap < sz) { set_error("buffer too small"); return SKX_EINVAL; }
-    std::vector<uint64_t> off(B + 1); std::vector<uint32_t> uc(B);
-    SKX_HIP(hipMemcpyAsync(off.data(), d->off.p + ((uint64_t)sample << d->logB), (B + 1) * 8, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipMemcpyAsync(uc.data(), d->ucnt.p + ((uint64_t)sample << d->logB), B * 4, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    std::vector<skx_key> hk(sz); std::vector<uint8_t> hb(sz);
-    static const char M2I[17] = "-ACMTWYHGRSVKDBN";
-    const int wpk = d->wide() ? 2 : 1;
-    {
-        std::vector<uint64_t> raw((size_t)sz * wpk);
-        uint64_t w = 0;
-        for (uint64_t b = 0; b < B; b++) {
-            if (uc[b]) SKX_HIP(hipMemcpyAsync(raw.data() + w * wpk, d->words.p + off[b] * wpk, (size_t)uc[b] * 8 * wpk, hipMemcpyDeviceToHost, st));
-            w += uc[b];
-        }
-        SKX_HIP(hipStreamSynchronize(st));
-        for (uint64_t i = 0; i < sz; i++) {
-            if (d->wide()) {
-                const u128 word = ((u128)raw[2 * i + 1] << 64) | raw[2 * i];
-                const u128 key = hunmix_w(word >> 4, d->wh);
-                hk[i].lo = (uint64_t)key; hk[i].hi = (uint64_t)(key >> 64); hb[i] = (uint8_t)M2I[(unsigned)word & 15u];
-            } else {
-                hk[i].lo = hunmix(raw[i] >> 4, d->hp); hk[i].hi = 0; hb[i] = (uint8_t)M2I[raw[i] & 15u];
-            }
-        }
-    }
-    std::vector<uint64_t> idx(sz); std::iota(idx.begin(), idx.end(), 0);
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b2) { return hk[a].hi != hk[b2].hi ? hk[a].hi < hk[b2].hi : hk[a].lo < hk[b2].lo; });
-    for (uint64_t i = 0; i < sz; i++) { if (keys) keys[i] = hk[idx[i]]; if (bases) bases[i] = hb[idx[i]]; }
     return SKX_OK;
     });
 }
@@ -1481,7 +1013,7 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
         const uint64_t amp = 1ull << (logQ - logB);
         // every region is read by `amp` workgroups that keep a share each: 8 at most where the regions are the 5 Mbp shape's (beyond that the
         // samples are unrelated and the sorted path reads less), 32 where the regions have grown with the samples (one XCD's workgroups: 256 / 8)
-        const uint64_t amp_max = region_cap > (wide ? LDS_SORT_MAX_WIDE : LDS_SORT_MAX) ? 32 : 8;
+        const uint64_t amp_max = region_cap > lds_sort_max(wide) ? 32 : 8;
         if (amp > amp_max && (double)raw_sum * (double)amp > 4e8) return not_taken("too many row blocks per region: every region would be read too often");
         if (!pass_ok(logQ, nslots, cap)) return not_taken("no row-block split that fits the LDS");
         std::unique_ptr<skx_keyset> ks(new skx_keyset());

@@ -138,10 +138,7 @@ void launch_fill_offsets(uint64_t *off, uint64_t n, uint32_t capacity, hipStream
 void launch_scan_u32(const uint32_t *in, uint64_t *out, uint64_t n, uint32_t *max_out, hipStream_t st);
 
 constexpr int SUBIDX = 16;     // sub-ranges indexed per (sample, bucket) region
-// in-place sort + dedupe (OR of masks) of every (sample,bucket) region through an order-preserving LDS table
-void launch_dedupe(uint64_t *words, const uint64_t *off, const uint32_t *raw, uint32_t *ucnt, uint64_t n_regions,
-                   uint32_t table_slots, int rem_bits, int *overflow, uint32_t min_n, uint16_t *sidx, int sb, hipStream_t st);
-
+// in-place sort + dedupe (OR of masks) of every (sample,bucket) region: a counting sort in LDS, cap >= every raw[region] (else *overflow bit 2)
 // typical / big_list / big_from: the two-shape launch (skx_device.hip); *overflow bit 4 = relaunch with big_from += dedupe_spill_grid()
 uint32_t dedupe_spill_grid();      // workgroups of one second-stage launch (16 384; SKX_DEDUPE_SPILL_GRID overrides, for tests)
 void launch_dedupe_mb(uint64_t *words, const uint64_t *off, const uint32_t *raw, uint32_t *ucnt, uint64_t n_regions,

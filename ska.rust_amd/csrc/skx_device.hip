@@ -759,53 +759,6 @@ typedef const uint64_t __attribute__((address_space(1))) *gwords_t;
 __device__ static inline gwords_t as_global(const uint64_t *p) { return (gwords_t)(uintptr_t)p; }
 
 // K3: per (sample,bucket) region: dedupe (OR of base masks) + sort, in place
-// K3 (fallback for regions larger than the counting sort's LDS capacity, i.e. heavy repeat content: tandem repeats,
-// homopolymers): duplicates collapse on insertion, so only the number of DISTINCT keys has to fit.
-__global__ __launch_bounds__(256) void dedupe_kernel(uint64_t *words, const uint64_t *off, const uint32_t *raw, uint32_t *ucnt,
-                                                     uint32_t nslots, int rem_bits, int *overflow, uint32_t min_n, uint16_t *sidx, int sb)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned long long s_tab[];
-    __shared__ uint32_t s_tmp[17];
-    __shared__ uint32_t s_sub[SUBIDX];
-    __shared__ int s_fail;
-    const uint64_t region = blockIdx.x;
-    const uint32_t n = raw[region];
-    if (n <= min_n) return;                                  // handled by the counting-sort kernel
-    if (n == 0) { if (threadIdx.x == 0) ucnt[region] = 0; if (threadIdx.x < SUBIDX) sidx[region * SUBIDX + threadIdx.x] = 0; return; }
-    if (threadIdx.x < SUBIDX) s_sub[threadIdx.x] = 0xFFFFFFFFu;
-    const uint32_t total_slots = nslots + TABLE_PAD;
-    for (uint32_t i = threadIdx.x; i < total_slots; i += blockDim.x) s_tab[i] = 0ull;
-    if (threadIdx.x == 0) s_fail = 0;
-    __syncthreads();
-    uint64_t *reg = words + off[region];
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint64_t w = reg[i];
-        if (!table_insert(s_tab, total_slots, home_slot(w, rem_bits, nslots), w)) s_fail = 1;
-    }
-    __syncthreads();
-    if (s_fail) { if (threadIdx.x == 0) { *overflow = 1; ucnt[region] = 0; } if (threadIdx.x < SUBIDX) sidx[region * SUBIDX + threadIdx.x] = 0; return; }
-    const uint64_t lmask = rem_bits >= 60 ? ~0ull : ((1ull << rem_bits) - 1);
-    uint32_t total = table_emit_sorted(s_tab, total_slots, s_tmp, [&](uint32_t idx, uint64_t w) {
-        reg[idx] = w;
-        atomicMin(&s_sub[sb ? (uint32_t)(((w >> 4) & lmask) >> (rem_bits - sb)) : 0u], idx);
-    });
-    if (threadIdx.x == 0) ucnt[region] = total;
-    __syncthreads();
-    if (threadIdx.x < SUBIDX) {                              // first word of sub-range s = first set entry at or above s
-        uint32_t v = total;
-        for (int s2 = SUBIDX - 1; s2 >= (int)threadIdx.x; s2--) if (s_sub[s2] != 0xFFFFFFFFu) v = s_sub[s2];
-        sidx[region * SUBIDX + threadIdx.x] = (uint16_t)v;
-    }
-}
-void launch_dedupe(uint64_t *words, const uint64_t *off, const uint32_t *raw, uint32_t *ucnt, uint64_t n_regions,
-                   uint32_t table_slots, int rem_bits, int *overflow, uint32_t min_n, uint16_t *sidx, int sb, hipStream_t st)
-{
-    if (!n_regions) return;
-    size_t lds = (size_t)(table_slots + TABLE_PAD) * 8;
-    (void)hipFuncSetAttribute((const void *)dedupe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(dedupe_kernel, dim3((unsigned)n_regions), dim3(256), lds, st, words, off, raw, ucnt, table_slots, rem_bits, overflow, min_n, sidx, sb);
-}
-
 // (Leaving a region grouped by micro-bucket but unordered inside -- all its consumers need, and 5 % cheaper here: 20.05 -> 19.05 ms -- was
 // measured and dropped: union and assemble then run at less than half their rate (8.4 -> 19.9 ms, 14.9 -> 28.4 ms), because with sorted
 // slices neighbouring lanes look up neighbouring table slots / rows in LDS; profiles/r03j_ab_grouped_full.log.)
@@ -833,7 +786,7 @@ __global__ __launch_bounds__(NT) void dedupe_mb_kernel(uint64_t *words, const ui
     const uint32_t n = raw[region];
     if (n == 0) { if (threadIdx.x == 0) ucnt[region] = 0; return; }
     if (big_mode == 1 && n > (uint32_t)NT * ITEMS) return;
-    if (n > cap || n > (uint32_t)NT * ITEMS) { if (threadIdx.x == 0) atomicOr(overflow, 2); return; }      // left to dedupe_kernel
+    if (n > cap || n > (uint32_t)NT * ITEMS) { if (threadIdx.x == 0) atomicOr(overflow, 2); return; }      // (the host sends no such region: an internal error there)
     uint64_t *s_elem = reinterpret_cast<uint64_t *>(s_mem);                 // [cap]
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + (size_t)cap * 8 + 32) + 1;   // (four sentinel words first) [-1] = 0 | [M] counts -> cursors (= bucket ends) -> leader counts
     int logM = 31 - __clz(n);                                                // ~1..2 words per micro-bucket

@@ -333,7 +333,7 @@ int skf_read_stream(const char *path, SkfMeta &m, std::vector<skx_key> &keys, st
                     const DevDecode *dev = nullptr);
 }  // namespace skx
 
-// helpers shared by the ABI translation units (skx_api.cpp, skx_build_files.cpp, skx_api_io.cpp, skx_distance.cpp)
+// helpers shared by the ABI translation units (skx_api.cpp, skx_dictset.cpp, skx_build_files.cpp, skx_api_io.cpp, skx_distance.cpp)
 namespace skx {
 // the one or two paths of a sample, and what a look at a file tells (skx_build_files.cpp): each caller decides for itself what it makes of it
 struct SampleFiles { const char *f[2]; int n; const char *const *begin() const { return f; } const char *const *end() const { return f + n; } };
@@ -345,7 +345,11 @@ struct FileProbe {
     bool gzip() const { return n_head == 2 && head[0] == 0x1f && head[1] == 0x8b; }
 };
 FileProbe probe_file(const char *path, bool gz_trailer = false);
-// how an assembly batch's (sample, bucket) regions are laid out (skx_api.cpp): 2^logB regions a sample (-1: not bucketed, the sort-based form takes
+inline int ilog2_ceil(uint64_t x) { int l = 0; while ((1ull << l) < x) l++; return l; }
+// words per region of the per-region counting sort in LDS: 6 144 (24 per thread in registers), 4 096 for 128-bit keys (16 per thread); regions
+// beyond it are read unsorted by the append pass and sorted as one flat list per sample (skx_dictset.cpp)
+constexpr uint32_t lds_sort_max(bool wide) { return wide ? 4096u : 6144u; }
+// how an assembly batch's (sample, bucket) regions are laid out (skx_dictset.cpp): 2^logB regions a sample (-1: not bucketed, the sort-based form takes
 // the batch) of `cap` words each
 struct RegionLayout { int logB; uint32_t cap; };
 uint32_t region_capacity(uint64_t longest_sample, int logB);

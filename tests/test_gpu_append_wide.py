@@ -93,13 +93,13 @@ def test_wide_repeat_that_overflows_a_region_takes_the_sorted_path(E, k):
 
 @pytest.mark.parametrize("k", [41])
 def test_wide_append_equals_the_sorted_path(E, k, monkeypatch):
-    """The same samples through the pass and through per-sample sort + union + assemble (SKX_KNOBS=sorted_wide): one array."""
+    """The same samples through the pass and through per-sample sort + union + assemble (SKX_KNOBS=sorted_dicts): one array."""
     rng = np.random.default_rng(3)
     samples = related(rng, 50_000, 9, 30)
     ga, oa = build_both(E, samples, k, True)
     assert E.default_context().merge_path() == "append128"
     m1 = as_map(*ga.export())
-    set_knob(monkeypatch, "sorted_wide", 1)
+    set_knob(monkeypatch, "sorted_dicts", 1)
     gb, _ = build_both(E, samples, k, True)
     assert E.default_context().merge_path().startswith("sorted:")
     assert as_map(*gb.export()) == m1 == as_map(*oa.export())

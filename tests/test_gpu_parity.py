@@ -408,7 +408,10 @@ def test_repeat_rich_tiny_wide_sample(E):
 
 def test_repeat_rich_sample(E):
     """Tandem repeats / homopolymers put tens of thousands of identical split k-mers into one hash bucket: the region
-    overflows the fixed-capacity layout (-> exact histogram pass) and the counting sort (-> table dedupe)."""
+    overflows the fixed-capacity layout (-> exact histogram pass) and, at 20 000 words, the per-region counting sort too
+    (-> the flat sort of whole samples).  The last input keeps the repeat within the counting sort: one sample of 5 600 bases
+    has two regions of capacity 3 648, and the ~4 970 poly-A windows in one of them overflow that but not the 6 144 words the
+    sort holds (-> exact layout, sorted per region)."""
     rng = np.random.default_rng(9)
     rnd = bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=150_000).tolist())
     recs = [rnd[:60_000] + b"AT" * 12_000 + rnd[60_000:90_000], b"A" * 20_000 + rnd[90_000:], b"GATTACA" * 5_000, b"ACGT" * 9_000]
@@ -417,6 +420,7 @@ def test_repeat_rich_sample(E):
         ga = ds.merge(["rep", "rnd"])
         oa = ora.Array.from_dicts([oracle_dict(recs, k, rc), oracle_dict([rnd], k, rc)], ["rep", "rnd"])
         assert as_map(*ga.export()) == as_map(*oa.export())
+    check_dicts(E, [[b"A" * 5000 + rnd[:600]]], 31, True)
 
 
 def test_unrelated_samples_fine_split(E):
