@@ -1,5 +1,5 @@
 // skx_api_io.cpp -- the C ABI entry points that move text and files: `ska cov` histogram, `ska map`, .skf save / load.
-// (skx_api.cpp holds the build -> merge -> filter path, skx_distance.cpp the distance, skx_build_files.cpp the reading of sequence files.)
+// (skx_api.cpp holds the build batching and the filter, skx_merge.cpp the merge between them, skx_distance.cpp the distance, skx_build_files.cpp the reading of sequence files.)
 #include "skx_internal.h"
 #include "../../include/skx_host.h"
 #include <algorithm>

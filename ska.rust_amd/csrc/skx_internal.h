@@ -92,15 +92,18 @@ struct skx_ctx {
 
 namespace skx {
 struct StageTimer {        // HIP-event bracket around one stage on the ctx stream
-    skx_ctx *c; double *slot;
-    StageTimer(skx_ctx *c_, double *s) : c(c_), slot(s) { if (c->timing) (void)hipEventRecord(c->ev[0], c->stream); }
+    skx_ctx *c; double *slot; hipEvent_t *ev;
+    StageTimer(skx_ctx *c_, double *s, int first_event = 0) : c(c_), slot(s), ev(c_->ev + first_event) { if (c->timing) (void)hipEventRecord(ev[0], c->stream); }
     ~StageTimer()
     {
         if (!c->timing) return;
-        (void)hipEventRecord(c->ev[1], c->stream);
-        (void)hipEventSynchronize(c->ev[1]);
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) *slot += ms;
+        (void)hipEventRecord(ev[1], c->stream);
+        (void)hipEventSynchronize(ev[1]);
+        float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *slot += ms;
     }
+};
+struct KernelTimer : StageTimer {      // the same bracket around one kernel inside a stage (its own pair of events)
+    KernelTimer(skx_ctx *c_, double *s) : StageTimer(c_, s, 2) {}
 };
 uint64_t next_object_id();
 }
@@ -333,7 +336,7 @@ int skf_read_stream(const char *path, SkfMeta &m, std::vector<skx_key> &keys, st
                     const DevDecode *dev = nullptr);
 }  // namespace skx
 
-// helpers shared by the ABI translation units (skx_api.cpp, skx_dictset.cpp, skx_build_files.cpp, skx_api_io.cpp, skx_distance.cpp)
+// helpers shared by the ABI translation units (skx_api.cpp, skx_dictset.cpp, skx_merge.cpp, skx_build_files.cpp, skx_api_io.cpp, skx_distance.cpp)
 namespace skx {
 // the one or two paths of a sample, and what a look at a file tells (skx_build_files.cpp): each caller decides for itself what it makes of it
 struct SampleFiles { const char *f[2]; int n; const char *const *begin() const { return f; } const char *const *end() const { return f + n; } };
@@ -451,6 +454,14 @@ int array_lazy_stats(skx_array *a);                                  // a lazily
                                                                      // passes first, directly or through array_materialize
 // rows [r0, r0 + nr) of a lazily held array as a sample-major window: cell (s, r) at win + s * wpitch + (r - r0)
 int array_lazy_window(skx_array *a, uint64_t r0, uint64_t nr, DevBuf<uint8_t> &buf, const uint8_t **win, uint64_t *wpitch);
+// rows of a lazily held array into the caller's buffer (skx_merge.cpp): all of them, the row blocks [j_base, j_base + n_blocks) from column
+// col_base on, or -- with keep / kpos -- the rows a filter keeps at their new places
+int array_lazy_rows(skx_array *a, uint8_t *out, uint64_t pitch, uint32_t j_base = 0, uint32_t n_blocks = 0, uint64_t col_base = 0, const uint8_t *keep = nullptr,
+                    const uint64_t *kpos = nullptr, int mask_ambig = 0, bool full_pieces = false);
+// the statistics of an array over its pieces: every rank (min_count 0), or a frequency filter's bounded pass (skx_merge.cpp)
+int pieces_stats_pass(skx_array *a, uint64_t min_count, DevBuf<unsigned long long> *tally = nullptr);
+// one batch of skx_build_and_merge: takes the dictset, returns the batch's array (append pass, else rows + a lazily held array, else the eager merge)
+int merge_batch(skx_ctx *ctx, skx_dictset *d, const char *const *names, skx_array **out);
 inline uint64_t pitch_for(uint64_t cols) { return ((cols + 255) / 256) * 256 + 256; }
 inline bool key_less(const skx_key &x, const skx_key &y) { return x.hi != y.hi ? x.hi < y.hi : x.lo < y.lo; }
 inline bool key_eq(const skx_key &x, const skx_key &y) { return x.hi == y.hi && x.lo == y.lo; }

@@ -2,6 +2,7 @@
 array into its .skf window by window, `ska align *.fa` filters it before any cell is written; every other operation assembles
 the matrix first.  All of them must give what the eagerly assembled array (SKX_KNOBS=eager_array) and the oracle give."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -151,6 +152,139 @@ def test_assemble_lazy_equals_assemble(E, tmp_path, k):
     ds5.assemble_lazy(rows5, names).save(p)
     for x, y in zip(_sorted(ora.Array.load(p)), _sorted(eager)):
         assert np.array_equal(x, y)
+
+
+def _related_records(k, n=3, length=3_000, snps=12):
+    rng = np.random.default_rng(100 + k)
+    anc = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=length)]
+    recs = []
+    for _ in range(n):
+        s = anc.copy()
+        s[rng.integers(0, length, size=snps)] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=snps)]
+        recs.append(s.tobytes() + b"\n")
+    return recs
+
+
+def _same_export(got, want):
+    for x, y in zip(got.export(), want.export()):                   # keys, cells and counts in the engine's own row order: byte for byte
+        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("k", [21, 41])
+def test_assemble_over_flat_rows_reslabs_them(E, k):
+    """skx_array_assemble over a flat key list (KeySet.from_device: logN < 0) slabs the rows again at the dictionaries' granularity and
+    gives the array skx_merge gives; with one key taken out of the list it says which rows are missing instead."""
+    recs, names = _related_records(k), ["a", "b", "c"]
+    want = E.DictSet.build(recs, k, True).merge(names)
+    ds = E.DictSet.build(recs, k, True)
+    merged_rows = ds.union_keys()
+    p, n, wpk = merged_rows.device()
+    assert n == want.nrows and wpk == (2 if k > 31 else 1)
+    _same_export(ds.assemble(E.KeySet.from_device(p, n, k), names), want)
+    with pytest.raises(E.EngineError, match="row keyset does not contain every split k-mer of the samples"):
+        ds.assemble(E.KeySet.from_device(p + 8 * wpk, n - 1, k), names)
+    _same_export(ds.assemble_lazy(E.KeySet.from_device(p, n, k), names), want)      # no lazy form over flat rows: assembled at once
+
+
+def _unrelated_records(n, length, seed):
+    rng = np.random.default_rng(seed)
+    return [np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=length)].tobytes() + b"\n" for _ in range(n)]
+
+
+def test_assemble_over_an_append_pass_rows_uses_its_pieces(E, tmp_path):
+    """union_keys(notes=True) over assemblies (64-bit keys) is the append pass: its rows carry the samples' cells as pieces, and
+    skx_array_assemble / _lazy make the array over them -- over the pass's own row blocks, and over the global rows of a sharded job (here of
+    one rank) when those are slabbed at least as finely as the blocks."""
+    k, names = 21, [f"p{i}" for i in range(4)]
+    recs = _related_records(k, n=4, length=30_000, snps=40)
+    ctx = E.default_context()
+    want = E.DictSet.build(recs, k, True).merge(names)
+    for lazy in (False, True):
+        ds = E.DictSet.build(recs, k, True)
+        own = ds.union_keys(notes=True)
+        assert ctx.merge_path() == "append64"
+        got = ds.assemble_lazy(own, names) if lazy else ds.assemble(own, names)
+        assert got.pieces_info()[1] > 0                             # still over the pieces
+        _same_export(got, want)
+    ds = E.DictSet.build(recs, k, True)
+    own = ds.union_keys(notes=True)
+    comm = E.Comm.local(0, 1, str(tmp_path), ctx=ctx)
+    got = ds.assemble(comm.keyset_allgather(own), names)
+    assert got.pieces_info()[1] > 0
+    comm.reduce_stats(got, len(names))
+    _same_export(got, want)
+    comm.free()
+
+
+def test_union_with_notes_where_the_append_pass_is_not_taken(E, monkeypatch):
+    """128-bit keys: a sharded job's exchange composes 64-bit rows only, so union_keys(notes=True) sorts the dictionaries and takes the
+    notes of the union kernel.  64-bit keys whose row blocks keep overflowing (started nine splits too coarse): the same way out."""
+    for k, recs, why in ((41, _related_records(41), "sorted: the key-table exchange of a sharded job composes 64-bit rows only"),
+                         (21, _unrelated_records(16, 30_000, 9), "sorted: row blocks kept overflowing")):
+        names = [f"n{i}" for i in range(len(recs))]
+        want = E.DictSet.build(recs, k, True).merge(names)
+        if k == 21:
+            set_knob(monkeypatch, "append_coarse", "9")
+        ds = E.DictSet.build(recs, k, True)
+        rows = ds.union_keys(notes=True)
+        del_knob(monkeypatch, "append_coarse")
+        assert E.default_context().merge_path().startswith(why)
+        got = ds.assemble(rows, names)
+        assert got.pieces_info()[1] == 0
+        _same_export(got, want)
+
+
+def test_notes_of_the_union_travel_to_a_sharded_jobs_rows(E, tmp_path, monkeypatch):
+    """Sorted dictionaries (SKX_KNOBS=sorted_dicts): union_keys(notes=True) takes the union kernel's notes, the key-table exchange (one
+    rank) carries them over to the global rows, and skx_array_assemble fills the rank's columns from them."""
+    k, names = 21, [f"q{i}" for i in range(4)]
+    recs = _related_records(k, n=4, length=30_000, snps=40)
+    want = E.DictSet.build(recs, k, True).merge(names)
+    set_knob(monkeypatch, "sorted_dicts", "1")
+    ds = E.DictSet.build(recs, k, True)
+    own = ds.union_keys(notes=True)
+    comm = E.Comm.local(0, 1, str(tmp_path), ctx=E.default_context())
+    got = ds.assemble(comm.keyset_allgather(own), names)
+    assert got.pieces_info()[1] == 0                                # no append pass over sorted dictionaries: filled from the notes
+    comm.reduce_stats(got, len(names))
+    _same_export(got, want)
+    comm.free()
+
+
+@pytest.mark.parametrize("eager", [False, True])
+def test_build_batch_whose_dictionaries_are_sorted(E, tmp_path, monkeypatch, eager):
+    """skx_build_and_merge on a batch the append pass does not take (SKX_KNOBS=sorted_dicts): rows and a lazily held array over the
+    dictionaries, or -- eager_array -- the matrix at once; the array of the append pass either way."""
+    inputs = _files(tmp_path, n=4, length=20_000, seed=81)
+    want = E.Array.build(inputs, k=31, threads=2)
+    assert want.pieces_info()[1] > 0
+    set_knob(monkeypatch, "sorted_dicts", "1")
+    if eager:
+        set_knob(monkeypatch, "eager_array", "1")
+    got = E.Array.build(inputs, k=31, threads=2)
+    assert E.default_context().merge_path().startswith("sorted: ") and got.pieces_info()[1] == 0
+    _same_export(got, want)
+
+
+def test_assemble_over_rows_coarser_than_the_buckets_reslabs_them(E, capfd, monkeypatch):
+    """Three copies of a 2 kbp unit: 6 000 windows give 2^1 buckets, fewer than 2 500 distinct split k-mers one slab (logN = 0) when the
+    row set goes through KeySet.merge -- coarser than the buckets, so skx_array_assemble slabs the rows again (0 <= logN < logB)."""
+    from test_gpu_split_sketch import log_buckets
+    k = 21
+    rng = np.random.default_rng(77)
+    unit = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=2_000)].tobytes()
+    recs, names = [unit * 3 + b"\n"], ["r"]
+    assert log_buckets(len(recs[0]), k) == 1
+    want = E.DictSet.build(recs, k, True).merge(names)
+    assert want.nrows < 2_500
+    monkeypatch.setenv("SKX_DEBUG", "1")
+    ds = E.DictSet.build(recs, k, True)
+    capfd.readouterr()
+    rows = E.KeySet.merge([ds.union_keys()])
+    got = ds.assemble(rows, names)
+    slabs = [int(x) for x in re.findall(r"\[skx\] keyset: logN=(-?\d+)", capfd.readouterr().err)]
+    assert slabs == [1, 0, 1]                                       # the union over 2^1 buckets, the merged rows, the rows slabbed again
+    _same_export(got, want)
 
 
 @pytest.mark.parametrize("filt", [True, False])
