@@ -372,6 +372,29 @@ typedef struct {
 typedef struct { uint64_t presence, allele; } skx_marker_info;
 int  skx_array_group_markers(skx_array *a, const int32_t *segment_of, int n_groups, const uint8_t *reported, double min_in, double max_out, int kinds,
                              skx_marker **records, skx_key **keys, uint64_t *n, skx_marker_info *info);
+/* `ska distance --sites`: which rows make up the distance of a pair, and which base each of the two samples carries there.  The reference has no
+ * counterpart: its users run `ska delete` down to the pair (merge_ska_array.rs:231-271), `ska align` and `ska nk --full-info` and compare columns.
+ * Definition.  The array holds S samples and U rows, in its current order.  Cells are bytes; code(cell) is the 4-bit IUPAC set as above
+ * (skx_array_group_markers); a cell is unambiguous when popcount(code) == 1.  A row is swept when it passes the two filters of
+ * generic_modes::distance for min_freq -- the rows the distance entry points build their planes over: the threshold ceil(S * min_freq) when
+ * min_freq * S >= 1, then NoConst.
+ *     sites(i, j) = { r swept : M[i][r] and M[j][r] unambiguous and M[i][r] != M[j][r] },  r ascending        (i < j)
+ * |sites(i, j)| is the `distance` skx_array_distance_filtered gives the pair with filt_ambig, exactly; without filt_ambig distances are fractional
+ * sums over base-set overlaps and sites are not defined.  (The NoConst stage never removes a site row: two different unambiguous bases make the
+ * row non-constant.  Only the frequency threshold can.)
+ * ij = n_pairs x (i, j) with i < j < S, in any order; a pair given twice gets two runs of records.  records: malloc'd (skx_free), n of them,
+ * sorted by (pair, row) -- the order of ij, then ascending rows; pair = the index into ij, row = the index in the array's current order, the bases
+ * as ASCII.  keys may be NULL; otherwise keys[n] (malloc'd) = the record's split k-mer as skx_array_group_markers returns keys; both key widths
+ * are taken.  counts (n_pairs entries, the caller's memory) may be NULL; otherwise counts[p] = |sites| of pair p.
+ * The records are counted exactly before anything is allocated for them: max_records > 0 and a larger total is SKX_ENOMEM with a message naming
+ * both numbers, and so are records that do not fit the device or the host; counts is filled even then, so that a caller can size a second call.
+ * SKX_EINVAL with a message that begins "pair sites:" for i >= j, an index outside the array, NaN or min_freq outside [0, 1], keys != NULL on an
+ * array without split k-mers (skx_array_load_filtered, skx_array_subset_filtered).  n_pairs == 0 or U == 0: SKX_OK with *n = 0.  `a` keeps its
+ * content (an array held as pieces or lazily is materialised first).  Device memory beside the array: a byte a row, 8 bytes per pair and 4 096
+ * rows, 16 bytes a record (32 with keys). */
+typedef struct { uint64_t row; uint32_t pair; uint8_t base_i, base_j, reserved[2]; } skx_pair_site;
+int  skx_array_pair_sites(skx_array *a, double min_freq, const uint32_t *ij, uint64_t n_pairs, uint64_t max_records,
+                          skx_pair_site **records, skx_key **keys, uint64_t *counts, uint64_t *n);
 /* MergeSkaArray::weed (merge_ska_array.rs:452-487): rows whose split k-mer is (reverse: is not) in `weed` are removed;
  * `weed` = the split k-mers of the weed FASTA (RefSka::new + kmer_iter, ska_ref.rs:189-262,541), i.e. the key set of its
  * dictionary: skx_dictset_build_files (1 sample) -> skx_keyset_union. */

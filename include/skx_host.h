@@ -81,6 +81,20 @@ int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, double min_freq,
 /* `ska distance <skf> --mst`: the header and the lines of skh_distance_skf_tsv's table that form its minimum spanning forest under `spec`
  * (skx_array_distance_mst), in the table's order and text.  The same one-pass filtered load; the full table is never formed. */
 int skh_distance_mst_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, char **buf, uint64_t *len);
+/* `ska distance <skf> (--max-snps N | --max-mismatches P | --closest K | --mst ...) --sites PREFIX [--sites-max N]`: the table's selected lines as
+ * skh_distance_select_tsv (spec) or skh_distance_mst_tsv (mst) give them -- exactly one of the two is not NULL -- and in <prefix>.sites.tsv the rows
+ * that make up each line's Distance (skx_array_pair_sites; filter-ambiguous distances only).  The file is loaded with its split k-mers
+ * (skh_load_array), the pairs come from skx_array_distance_select / skx_array_distance_mst with min_freq and the sites from skx_array_pair_sites
+ * with the same min_freq and max_records (0: no limit).
+ * <prefix>.sites.tsv: header "Sample1\tSample2\tUpper\tLower\tBase1\tBase2", one line per record, the pairs in the order of the table's lines,
+ * rows ascending within a pair; Upper / Lower as <prefix>.markers.tsv spells them (skh_key_arms).
+ * *buf is the table whenever the selection itself succeeded: when the sites are refused (SKX_ENOMEM above max_records, with the ABI's message)
+ * the call returns the error and still hands the table back, and no sites file is written.
+ * Phases: distance.pair_sweep / distance.table_text / distance.sites_count / distance.sites_write / distance.sites_text. */
+int skh_distance_sites(skx_ctx *ctx, const char *skf_file, double min_freq, const skx_select_spec *spec, const skx_mst_spec *mst, const char *prefix,
+                       uint64_t max_records, char **buf, uint64_t *len);
+/* the two arms of a split k-mer of length k as `ska nk --full-info` spells them: upper and lower receive (k - 1) / 2 letters and a NUL each */
+void skh_key_arms(const skx_key *key, int k, char *upper, char *lower);
 /* the clusters of a forest at a ladder of SNP thresholds (host only): for each of the n_levels levels L, in the order given, the connected
  * components of the forest's lines whose distance as the table prints it ("%.2f") is <= L -- the single-linkage clusters of `--clusters
  * --cluster-snps L` when the forest is the whole table's -- numbered 1, 2, ... in ascending order of their lowest sample.  csv: the header

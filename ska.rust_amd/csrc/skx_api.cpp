@@ -549,7 +549,8 @@ extern "C" int skx_array_from_host(skx_ctx *ctx, int k, int rc, const char *cons
         SKX_HIP(hipStreamSynchronize(st));
     }
     int bad = 0;
-    SKX_HIP(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
+    SKX_HIP(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));     // on the stream: without rows nothing above has waited for the flag's memset
+    SKX_HIP(hipStreamSynchronize(st));
     SKX_HIP(hipGetLastError());
     if (bad) { set_error("variants contain a byte outside -ACGTMRWSYKVHDBN (not supported on the device path)"); return SKX_EUNSUP; }
     *out = a.release();

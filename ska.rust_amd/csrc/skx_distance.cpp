@@ -159,21 +159,26 @@ static int build_planes(skx_array *a, const uint8_t *keep, int filt_ambig, const
     SKX_TRY(sp.p.alloc((filt_ambig ? 4 : 8) * (uint64_t)S));
     return sp.p.zero(st);
 }
+// the two filters of generic_modes::distance per row, in one pass over the row statistics (skx_internal.h): what entry_planes and skx_array_pair_sites read
+void skx::distance_filter_flags(skx_array *a, double min_freq, uint8_t *keep, hipStream_t st)
+{
+    const uint64_t S_total = a->total_samples ? a->total_samples : (uint64_t)a->names.size();
+    const uint64_t thr = min_freq * (double)S_total >= 1.0 ? (uint64_t)std::ceil((double)S_total * min_freq) : 0;       // generic_modes.rs:149-159
+    FilterArgs fa{a->vcount.p, a->present.p, a->unambig.p, a->mask.p, a->n_rows, (uint32_t)S_total, thr, 0, SKX_FILTER_NO_CONST, 0, keep, 1};
+    launch_filter_flags(fa, st);
+}
 // the planes of an entry point.  prefiltered: the array has been filtered already (skx_array_distance, the *_prefiltered entry points) -- every
 // row is swept and *prefiltered is the constant; nullptr: the two filters of generic_modes::distance (generic_modes.rs:136-189) decide per row
 // and the planes are built over the rows that stay, without touching the array; constant = rows the NoConst stage removes
 static int entry_planes(skx_array *a, const double *prefiltered, double min_freq, int filt_ambig, const int *order, SweepPlanes &sp, double &constant, uint64_t &kept)
 {
     hipStream_t st = a->ctx->stream;
-    const int S = (int)a->names.size(); const uint64_t U = a->n_rows;
+    const uint64_t U = a->n_rows;
     if (prefiltered) { constant = *prefiltered; return build_planes(a, nullptr, filt_ambig, order, sp, kept); }
-    const uint64_t S_total = a->total_samples ? a->total_samples : (uint64_t)S;
-    const uint64_t thr = min_freq * (double)S_total >= 1.0 ? (uint64_t)std::ceil((double)S_total * min_freq) : 0;       // generic_modes.rs:149-159
     DevBuf<uint8_t> keep; DevBuf<unsigned long long> d_c; unsigned long long n_const = 0;
     if (U) {
         SKX_TRY(keep.alloc(U)); SKX_TRY(d_c.alloc(1)); SKX_TRY(d_c.zero(st));
-        FilterArgs fa{a->vcount.p, a->present.p, a->unambig.p, a->mask.p, U, (uint32_t)S_total, thr, 0, SKX_FILTER_NO_CONST, 0, keep.p, 1};
-        launch_filter_flags(fa, st);
+        distance_filter_flags(a, min_freq, keep.p, st);
         launch_count_u8(keep.p, U, 3, d_c.p, st);
         SKX_HIP(hipMemcpyAsync(&n_const, d_c.p, 8, hipMemcpyDeviceToHost, st));      // arrives with the builder's row count: it synchronises for that
     }

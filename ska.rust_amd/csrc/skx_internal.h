@@ -444,6 +444,9 @@ int nj_run_device(skx_ctx *ctx, DevBuf<double> &D, uint64_t pitch, uint32_t S, s
 // bit planes of the rows flagged 1 in keep (4 planes with filt, else 8): every word written; rows = how many
 // (order: launch_build_planes_keep's, device memory or nullptr)
 int planes_of_kept_rows(skx_array *a, const uint8_t *keep, int filt, DevBuf<uint64_t> &planes, uint64_t &wpr, uint64_t &rows, const int *order = nullptr);
+// the two filters of generic_modes::distance (generic_modes.rs:136-189) for min_freq, per row of a materialised array (n_rows > 0): keep[r] = 1 the
+// row is swept, 0 the frequency threshold removes it, 3 the NoConst stage does (what the distance entry points build their planes over)
+void distance_filter_flags(skx_array *a, double min_freq, uint8_t *keep, hipStream_t st);
 int cpu_budget();                                                    // CPUs the process may keep busy (hardware threads, or the control group's quota)
 int check_k(int k);                                                  // "Invalid k-mer length" (ska_dict.rs:342-344)
 bool mappable_output_fd(int fd, off_t *pos);                         // regular file, read-write, not O_APPEND: can be written through a mapping

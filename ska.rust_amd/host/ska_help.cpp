@@ -71,6 +71,8 @@ const std::vector<Cmd> &commands()
           {"--cluster-snps", "<N>", "(MI355X engine) Largest SNP distance that links two samples (with --clusters) [default: 10]"},
           {"--cluster-mismatches", "<P>", "(MI355X engine) Largest mismatch proportion that links two samples (with --clusters) [default: 1.0]"},
           {"--no-table", "", "(MI355X engine) With --tree / --clusters: write those files only, from a banded sweep that never forms the table (no <PREFIX>.graph.dot; see --max-snps for the lines themselves)"},
+          {"--sites", "<PREFIX>", "(MI355X engine) With --max-snps / --max-mismatches / --closest / --mst: list the split k-mers behind each printed line's Distance, and the base either sample has there, in <PREFIX>.sites.tsv"},
+          {"--sites-max", "<N>", "(MI355X engine) With --sites: refuse to list more than N sites [default: 134217728]"},
           {"--query", "<NAMES>", "(MI355X engine) Print only the table's lines that name one of these samples (comma separated)"},
           {"--query-file", "<FILE>", "(MI355X engine) The same, sample names from a file (one per line)"},
           {"--query-skf", "<FILE>", "(MI355X engine) Merge this .skf into <SKF_FILE> in memory and print the lines that name one of its samples"},

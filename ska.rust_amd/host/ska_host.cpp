@@ -414,6 +414,68 @@ extern "C" int skh_distance_mst_tsv(skx_ctx *ctx, const char *skf_file, double m
     });
 }
 
+// `ska distance ... --sites PREFIX`: the selected lines from the array loaded with its split k-mers, then the rows behind each line's Distance
+extern "C" int skh_distance_sites(skx_ctx *ctx, const char *skf_file, double min_freq, const skx_select_spec *spec, const skx_mst_spec *mst, const char *prefix,
+                                  uint64_t max_records, char **buf, uint64_t *len)
+{
+    return skx_guarded([&]() -> int {
+    if (!ctx || !skf_file || !prefix || !buf || !len || !spec == !mst) { skx_set_error("skh_distance_sites: bad arguments"); return SKX_EINVAL; }
+    *buf = nullptr; *len = 0;
+    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
+    skx_array *a = nullptr; int r;
+    { const char *in[1] = {skf_file}; if ((r = skh_load_array(ctx, in, 1, 1, &a)) != SKX_OK) return r; }
+    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
+    skx_array_info_t info; skx_array_info(a, &info);
+    std::vector<const char *> names(info.n_samples);
+    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
+    skx_dist_pair *pairs = nullptr; uint64_t n_pairs = 0;
+    {
+        Phase pd("distance.pair_sweep");
+        int64_t constant = 0; uint64_t rows = 0;
+        r = spec ? skx_array_distance_select(a, min_freq, 1, spec, &pairs, &n_pairs, &constant, &rows, nullptr)
+                 : skx_array_distance_mst(a, min_freq, 1, mst, &pairs, &n_pairs, &constant, &rows, nullptr);
+        if (r != SKX_OK) return r;
+    }
+    struct FreePairs { skx_dist_pair *p; ~FreePairs() { skx_free(p); } } free_pairs{pairs};
+    if ((r = distance_select_text(names, pairs, n_pairs, buf, len)) != SKX_OK) return r;
+    std::vector<uint32_t> ij(2 * n_pairs);
+    for (uint64_t p = 0; p < n_pairs; p++) { ij[2 * p] = pairs[p].i; ij[2 * p + 1] = pairs[p].j; }
+    skx_pair_site *rec = nullptr; skx_key *keys = nullptr; uint64_t n = 0;
+    // (the phases distance.sites_count and distance.sites_write are recorded by the call itself: both happen inside it)
+    if ((r = skx_array_pair_sites(a, min_freq, ij.data(), n_pairs, max_records, &rec, &keys, nullptr, &n)) != SKX_OK) return r;
+    struct FreeRec { skx_pair_site *r; skx_key *k; ~FreeRec() { skx_free(r); skx_free(k); } } free_rec{rec, keys};
+    char msg[160];
+    snprintf(msg, sizeof msg, "Sites: %llu records of %llu lines", (unsigned long long)n, (unsigned long long)n_pairs);
+    skh_log(2, "ska::generic_modes", msg);
+    Phase pt("distance.sites_text");
+    // a record's line, formatted in slices by a few threads as the table's lines are
+    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n / 4096, std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+    std::vector<std::string> part(T);
+    auto work = [&](uint64_t t) {
+        std::string &o = part[t];
+        char up[32], lo[32];
+        for (uint64_t x = n * t / T; x < n * (t + 1) / T; x++) {
+            const skx_dist_pair &p = pairs[rec[x].pair];
+            skh_key_arms(&keys[x], info.k, up, lo);
+            o += names[p.i]; o += '\t'; o += names[p.j]; o += '\t'; o += up; o += '\t'; o += lo; o += '\t';
+            o += (char)rec[x].base_i; o += '\t'; o += (char)rec[x].base_j; o += '\n';
+        }
+    };
+    std::vector<std::thread> th;
+    for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    // (the slices go to the file one after the other: the text, gigabytes for a large selection, is never held twice)
+    const std::string path = std::string(prefix) + ".sites.tsv";
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { skx_set_error("cannot create %s", path.c_str()); return SKX_EIO; }
+    bool ok = fputs("Sample1\tSample2\tUpper\tLower\tBase1\tBase2\n", f) >= 0;
+    for (auto &x : part) ok = ok && fwrite(x.data(), 1, x.size(), f) == x.size();
+    if (fclose(f) != 0 || !ok) { skx_set_error("cannot write %s", path.c_str()); return SKX_EIO; }
+    return SKX_OK;
+    });
+}
+
 // `ska distance --no-table`: the extras' files from the banded sweep (x names at least one).  What reaches the host is S labels and S - 1 joins
 extern "C" int skh_distance_banded_files(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *x)
 {
@@ -923,7 +985,7 @@ struct Args {
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
-                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels",
+                            "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels", "--sites", "--sites-max",
                             "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
@@ -1400,6 +1462,31 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
             if (names.empty()) return clap_invalid(a.get("--samples", a.get("--samples-file")), a.has("--samples") ? "--samples <NAMES>" : "--samples-file <FILE>", "no sample names given");
         }
     }
+    if (cmd == "distance" && (a.has("--sites") || a.has("--sites-max"))) {
+        // the sites are those of the selected lines of one device's filter-ambiguous table: refused as clap refuses arguments that conflict, a
+        // missing requirement and a value that does not parse
+        const std::pair<const char *, const char *> others[] = {{"--allow-ambiguous", "--allow-ambiguous"}, {"--no-table", "--no-table"}, {"--query", "--query <NAMES>"},
+                                                                {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}, {"--gpus", "--gpus <GPUS>"},
+                                                                {"--mst-clusters", "--mst-clusters <PREFIX>"}};      // (the ladder is cut from the prefiltered load's forest)
+        if (a.has("--sites"))
+            for (auto &o : others)
+                if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
+                    fprintf(stderr, "error: the argument '--sites <PREFIX>' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
+                    return 2;
+                }
+        if (!a.has("--sites")) return clap_missing("distance", "--sites <PREFIX>");
+        if (!has_select(a) && !a.has("--mst")) return clap_missing("distance", "<--max-snps <N>|--max-mismatches <P>|--closest <K>|--mst>");
+        if (a.get("--sites").empty()) return clap_invalid("", "--sites <PREFIX>", "a value is required");
+        if (a.has("--sites-max")) {                                                              // u64::from_str, then the range
+            const std::string v = a.get("--sites-max");
+            if (v.empty()) return clap_invalid(v, "--sites-max <N>", "cannot parse integer from empty string");
+            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--sites-max <N>", "invalid digit found in string");
+            errno = 0;
+            const unsigned long long m = strtoull(v.c_str(), nullptr, 10);
+            if (errno == ERANGE) return clap_invalid(v, "--sites-max <N>", "number too large to fit in target type");
+            if (m < 1) return clap_invalid(v, "--sites-max <N>", "must be one or higher");
+        }
+    }
     if (cmd == "distance" && a.has("--no-table")) {
         // the tree and the clusters from the banded sweep, on one device, and nothing else: refused as clap refuses arguments that conflict and
         // a required group that is missing
@@ -1595,7 +1682,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"build", " -o -k -f --proportion-reads --single-strand --min-count --min-qual --qual-filter --threads --gpus --merge "},
             {"align", " -o -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites --threads --gpus --groups --min-group-size --samples --samples-file "},
             {"map", " -o -f --format --ambig-mask --repeat-mask --threads "},
-            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table --mst --mst-clusters --levels "},
+            {"distance", " -o -m --min-freq --allow-ambiguous --threads --gpus --tree --clusters --cluster-snps --cluster-mismatches --query --query-file --query-skf --max-snps --max-mismatches --closest --no-table --mst --mst-clusters --levels --sites --sites-max "},
             {"merge", " -o "}, {"delete", " -s --skf-file -o -f "},
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
@@ -1712,6 +1799,14 @@ extern "C" int skh_main(int argc, char **argv)
         }
         else if (a.has("--no-table")) {
             if (skh_distance_banded_files(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get()) != SKX_OK) rcode = engine_fail();
+        }
+        else if (a.has("--sites")) {                                                              // (validate_cli: one of the selecting options is there)
+            const skx_select_spec sp = select_spec(a);
+            const skx_mst_spec ms{sp.max_snps, sp.max_mismatches, 0};
+            const unsigned long long cap = a.has("--sites-max") ? strtoull(a.get("--sites-max").c_str(), nullptr, 10) : 1ull << 27;
+            const int r = skh_distance_sites(ctx, a.pos[0].c_str(), mf, a.has("--mst") ? nullptr : &sp, a.has("--mst") ? &ms : nullptr, a.get("--sites").c_str(), cap, &buf, &len);
+            if (buf) { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }                    // the table's lines stand even when the sites are refused
+            if (r != SKX_OK) rcode = engine_fail();
         }
         else if (a.has("--mst")) {
             const skx_select_spec ss = select_spec(a);

@@ -48,6 +48,16 @@ const char IUPAC[] = "-ACMTWYHGRSVKDBN";       // the letter of a 4-bit base set
 
 }  // namespace
 
+extern "C" void skh_key_arms(const skx_key *key, int k, char *upper, char *lower)
+{
+    static const char L[] = "ACTG";
+    const int half = (k - 1) / 2;
+    unsigned __int128 w = ((unsigned __int128)key->hi << 64) | key->lo;
+    for (int b = 0; b < half; b++) { lower[half - 1 - b] = L[(int)(w & 3)]; w >>= 2; }
+    for (int b = 0; b < half; b++) { upper[half - 1 - b] = L[(int)(w & 3)]; w >>= 2; }
+    upper[half] = lower[half] = 0;
+}
+
 extern "C" int skh_markers(skx_ctx *ctx, const char *skf_file, const char *groups_file, const char *out_prefix, double min_in, double max_out,
                            int min_group_size, int kinds, int fasta)
 {
@@ -93,7 +103,6 @@ extern "C" int skh_markers(skx_ctx *ctx, const char *skf_file, const char *group
     struct FreeRec { skx_marker *r; skx_key *k; ~FreeRec() { skx_free(r); skx_free(k); } } free_rec{rec, keys};
 
     Phase pt("markers.text");
-    const int half = (info.k - 1) / 2;
     static const char L[] = "ACTG";
     std::string tsv = "Group\tUpper\tLower\tKind\tIn\tOut\tBases\tOther bases\n", summary = "Group\tSamples\tPresence\tAllele\n";
     char line[256];
@@ -111,10 +120,8 @@ extern "C" int skh_markers(skx_ctx *ctx, const char *skf_file, const char *group
         std::string fa;
         uint64_t i = 0;
         for (uint64_t j : idx) {
-            unsigned __int128 key = ((unsigned __int128)keys[j].hi << 64) | keys[j].lo;
-            std::string up(half, 'A'), lo(half, 'A');
-            for (int b = 0; b < half; b++) { lo[half - 1 - b] = L[(int)(key & 3)]; key >>= 2; }
-            for (int b = 0; b < half; b++) { up[half - 1 - b] = L[(int)(key & 3)]; key >>= 2; }
+            char up[32], lo[32];
+            skh_key_arms(&keys[j], info.k, up, lo);
             const char *kind = rec[j].kind == SKX_MARKER_PRESENCE ? "presence" : "allele";
             const char bases = IUPAC[rec[j].bases_in & 15], other = IUPAC[rec[j].bases_out & 15];
             snprintf(line, sizeof line, "\t%s\t%u/%llu\t%u/%llu\t%c\t%c\n", kind, rec[j].n_in, (unsigned long long)size[g], rec[j].n_out,

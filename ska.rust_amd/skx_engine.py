@@ -26,6 +26,7 @@ MARKER_DT = np.dtype([("row", "<u8"), ("group", "<u4"), ("n_in", "<u4"), ("n_out
                       ("reserved", "u1")])                                               # skx_marker
 MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])                      # skx_marker_info
 MARKER_PRESENCE, MARKER_ALLELE = 1, 2
+PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
 
 
 class Qual(C.Structure):
@@ -134,7 +135,8 @@ skx_array_distance_banded skx_array_distance_banded_prefiltered skh_clusters_csv
 skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd
 skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv
 skx_ctx_filter_cut
-skx_array_group_markers skh_markers""".split()
+skx_array_group_markers skh_markers skh_key_arms
+skx_array_pair_sites skh_distance_sites""".split()
 
 _lib = None
 
@@ -185,6 +187,10 @@ def load_library():
     lib.skh_align_samples_fd.argtypes = [vp, C.POINTER(cp), i, i, i, i, i, d, i, C.POINTER(cp), i, i]
     lib.skx_array_group_markers.argtypes = [vp, vp, i, vp, d, d, i, pp, pp, C.POINTER(u64), vp]
     lib.skh_markers.argtypes = [vp, cp, cp, cp, d, d, i, i, i]
+    lib.skh_key_arms.argtypes = [vp, i, cp, cp]
+    lib.skh_key_arms.restype = None
+    lib.skx_array_pair_sites.argtypes = [vp, d, vp, u64, u64, pp, pp, vp, C.POINTER(u64)]
+    lib.skh_distance_sites.argtypes = [vp, cp, d, C.POINTER(SelectSpec), C.POINTER(MstSpec), cp, u64, pp, C.POINTER(u64)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -516,6 +522,21 @@ class Context:
         p, n = C.c_void_p(), C.c_uint64()
         _check(_lib.skh_distance_mst_tsv(self.h, skf_file.encode(), float(min_freq), int(filt_ambig), C.byref(spec), C.byref(p), C.byref(n)))
         return _take(p, n)
+
+    def distance_sites(self, skf_file, prefix, min_freq=0.0, max_snps=None, max_mismatches=None, closest=0, mst=False, max_records=0):
+        """`ska distance <skf> (--max-snps N | --max-mismatches P | --closest K | --mst) --sites PREFIX` (skh_distance_sites) -> the header and
+        the selected lines; PREFIX.sites.tsv lists the rows behind each line's Distance.  Above max_records (0: no limit) the call raises and
+        the error carries the table as its `table` attribute"""
+        sel, forest = SelectSpec.of(max_snps, max_mismatches, closest), MstSpec.of(max_snps, max_mismatches)
+        p, n = C.c_void_p(), C.c_uint64()
+        rc = _lib.skh_distance_sites(self.h, os.fsencode(skf_file), float(min_freq), None if mst else C.byref(sel), C.byref(forest) if mst else None,
+                                     os.fsencode(prefix), int(max_records), C.byref(p), C.byref(n))
+        table = _take(p, n) if p.value else None
+        if rc != OK:
+            err = EngineError(rc, _lib.skx_last_error().decode())
+            err.table = table
+            raise err
+        return table
 
     def distance_banded_files(self, skf_file, min_freq=0.0, filt_ambig=True, tree=None, clusters=None, cluster_snps=10.0, cluster_mismatches=1.0):
         """`ska distance <skf> --no-table [--tree FILE] [--clusters PREFIX ...]` (skh_distance_banded_files): the files, no table"""
@@ -1024,6 +1045,27 @@ class Array:
         _lib.skx_free(pr)
         _lib.skx_free(pk)
         return rec, keys, info[:n_groups]
+
+    def pair_sites(self, ij, min_freq=0.0, max_records=0, keys=True):
+        """skx_array_pair_sites: the rows that make up the filter-ambiguous distance of each pair of ij ([n_pairs, 2], i < j), this array left as
+        it is -> (records as PAIR_SITE_DT sorted by (pair, row), their split k-mers as KEY_DT or None, the sites per pair).  Above max_records
+        (0: no limit) the call raises ENOMEM and the error carries the counts as its `counts` attribute"""
+        ij = np.ascontiguousarray(ij, np.uint32).reshape(-1, 2)
+        counts = np.zeros(max(len(ij), 1), np.uint64)
+        pr, pk, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        rc = _lib.skx_array_pair_sites(self.h, float(min_freq), _np_ptr(ij), len(ij), int(max_records), C.byref(pr), C.byref(pk) if keys else None,
+                                       _np_ptr(counts), C.byref(n))
+        if rc != OK:
+            err = EngineError(rc, _lib.skx_last_error().decode())
+            err.counts, err.records = counts[:len(ij)], pr.value
+            raise err
+        rec = np.frombuffer(C.string_at(pr, n.value * PAIR_SITE_DT.itemsize), PAIR_SITE_DT).copy() if n.value else np.zeros(0, PAIR_SITE_DT)
+        k = None
+        if keys:
+            k = np.frombuffer(C.string_at(pk, n.value * KEY_DT.itemsize), KEY_DT).copy() if n.value else np.zeros(0, KEY_DT)
+            _lib.skx_free(pk)
+        _lib.skx_free(pr)
+        return rec, k, counts[:len(ij)]
 
     def map(self, reference, fmt="aln", ambig_mask=False, repeat_mask=False, threads=0):
         """generic_modes::map: RefSka::new + map + write_aln | write_vcf -> text (generic_modes.rs:56-84)."""
