@@ -1,11 +1,9 @@
 // ska_groups.cpp -- `ska align --groups / --samples`: one alignment per group of samples from a single load (host side above the C ABI).
 // The reference has no such mode: its users run `ska delete` + `ska align` per group (generic_modes.rs:192-210, 22-50); the files written here
 // are those, byte for byte.  skh_read_groups touches no device.
-#include "../../include/skx_host.h"
+#include "ska_host_util.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,28 +12,8 @@
 #include <unistd.h>
 #include <vector>
 
+using namespace skh;
 namespace {
-
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-void set_error(const char *fmt, ...)
-{
-    char tmp[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(tmp, sizeof tmp, fmt, ap); va_end(ap);
-    skx_set_last_error(tmp);
-}
-template <typename F>
-int guarded(F &&f) noexcept
-{
-    try { return f(); }
-    catch (const std::bad_alloc &) { skx_set_last_error("out of host memory"); return SKX_ENOMEM; }
-    catch (...) { skx_set_last_error("internal error"); return SKX_EINVAL; }
-}
-struct Phase {       // wall-clock phase recorded through the ABI (skx_phase_add)
-    const char *name; std::chrono::steady_clock::time_point t0;
-    explicit Phase(const char *n) : name(n), t0(std::chrono::steady_clock::now()) {}
-    void stop() { if (name) { skx_phase_add(name, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); name = nullptr; } }
-    ~Phase() { stop(); }
-};
 
 struct Group { std::string label; std::vector<std::string> names; };
 

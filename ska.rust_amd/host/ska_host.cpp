@@ -2,49 +2,22 @@
 // (generic_modes.rs: align / apply_filters / distance / save_skf; io_utils.rs: read_input_fastas /
 // get_input_list / load_array / set_ostream; cli.rs + lib.rs:557-727,808-827 for build | align | distance | nk).
 // Written in C++ because the image has no Rust toolchain; it only talks to the engine through include/skx.h.
-#include "../../include/skx_host.h"
-#include <algorithm>
+#include "ska_host_util.h"
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <chrono>
 #include <fstream>
 #include <sstream>
-#include <atomic>
-#include <thread>
 #include <ctime>
-#include <string>
 #include <fcntl.h>
 #include <signal.h>
 #include <spawn.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
-#include <vector>
 
+using namespace skh;
 namespace {
 
-void put(std::string &s, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-void put(std::string &s, const char *fmt, ...)
-{
-    char tmp[256];
-    va_list ap; va_start(ap, fmt); int n = vsnprintf(tmp, sizeof tmp, fmt, ap); va_end(ap);
-    if (n < (int)sizeof tmp) { s.append(tmp, (size_t)n); return; }
-    std::vector<char> big((size_t)n + 1);
-    va_start(ap, fmt); vsnprintf(big.data(), big.size(), fmt, ap); va_end(ap);
-    s.append(big.data(), (size_t)n);
-}
-int to_buf(const std::string &s, char **buf, uint64_t *len)
-{
-    char *p = (char *)malloc(s.size() + 1);
-    if (!p) return SKX_ENOMEM;
-    memcpy(p, s.data(), s.size()); p[s.size()] = 0;
-    *buf = p; *len = s.size();
-    return SKX_OK;
-}
 bool ends_with_ci(const std::string &s, const char *suf)
 {
     size_t m = strlen(suf);
@@ -63,26 +36,6 @@ void rust_debug(std::string &o, const std::string &s)
         else o += (char)c;
     }
     o += '"';
-}
-void skx_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-void skx_set_error(const char *fmt, ...)
-{
-    char tmp[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(tmp, sizeof tmp, fmt, ap); va_end(ap);
-    skx_set_last_error(tmp);
-}
-struct Phase {       // wall-clock phase recorded through the ABI (skx_phase_add)
-    const char *name; std::chrono::steady_clock::time_point t0;
-    explicit Phase(const char *n) : name(n), t0(std::chrono::steady_clock::now()) {}
-    void stop() { if (name) { skx_phase_add(name, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); name = nullptr; } }
-    ~Phase() { stop(); }
-};
-template <typename F>
-int skx_guarded(F &&f) noexcept
-{
-    try { return f(); }
-    catch (const std::bad_alloc &) { return SKX_ENOMEM; }
-    catch (...) { return SKX_EINVAL; }
 }
 }  // namespace
 
@@ -105,7 +58,7 @@ extern "C" char *skh_sample_name(const char *path)
 extern "C" int skh_apply_filters(skx_array *a, double min_freq, int filter_ambig_as_missing, int filter_type, int ambig_mask,
                                  int ignore_const_gaps, int32_t *removed)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array_info_t info; skx_array_info(a, &info);
     const uint64_t threshold = (uint64_t)std::ceil((double)info.total_samples * min_freq);   // generic_modes.rs:121 (nsamples() over all slabs)
     return skx_array_filter(a, threshold, filter_ambig_as_missing, filter_type, ambig_mask, ignore_const_gaps, /*update_kmers=*/0, removed);
@@ -115,7 +68,7 @@ extern "C" int skh_apply_filters(skx_array *a, double min_freq, int filter_ambig
 extern "C" int skh_align(skx_array *a, int filter_type, int mask_ambig, int ignore_const_gaps, double min_freq, int filter_ambig_as_missing,
                          char **buf, uint64_t *len)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     int32_t removed = 0;
     int r = skh_apply_filters(a, min_freq, filter_ambig_as_missing, filter_type, mask_ambig, ignore_const_gaps, &removed);
     if (r != SKX_OK) return r;
@@ -126,7 +79,7 @@ extern "C" int skh_align(skx_array *a, int filter_type, int mask_ambig, int igno
 // the same, written straight to a file descriptor (the alignment of a large array is never held on the host)
 extern "C" int skh_align_fd(skx_array *a, int filter_type, int mask_ambig, int ignore_const_gaps, double min_freq, int filter_ambig_as_missing, int fd)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     int32_t removed = 0;
     Phase pf("align.filter");
     int r = skh_apply_filters(a, min_freq, filter_ambig_as_missing, filter_type, mask_ambig, ignore_const_gaps, &removed);
@@ -137,392 +90,10 @@ extern "C" int skh_align_fd(skx_array *a, int filter_type, int mask_ambig, int i
     });
 }
 
-static int distance_text(skx_array *a, const std::vector<skx_dist> &d, char **buf, uint64_t *len);
-static int distance_text_names(const std::vector<const char *> &names, const skx_dist *d, char **buf, uint64_t *len);
-static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, skx_array **merged, std::vector<uint64_t> *n_each = nullptr);
-extern "C" int skh_distance_tsv(skx_array *a, double min_freq, int filt_ambig, char **buf, uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    skx_array_info_t info; skx_array_info(a, &info);
-    const uint64_t S = info.n_samples;
-    std::vector<skx_dist> d(S * (S - 1) / 2 + 1);
-    int64_t constant = 0; uint64_t rows = 0; int r;
-    // the two filters of generic_modes.rs:149-168 are applied while the bit planes are built; the array itself stays as it is
-    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance_filtered(a, min_freq, filt_ambig, d.data(), &constant, &rows)) != SKX_OK) return r; }
-    return distance_text(a, d, buf, len);
-    });
-}
-
-static int distance_text(skx_array *a, const std::vector<skx_dist> &d, char **buf, uint64_t *len)
-{
-    skx_array_info_t info; skx_array_info(a, &info);
-    std::vector<const char *> names(info.n_samples);
-    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
-    return distance_text_names(names, d.data(), buf, len);
-}
-static const char DIST_HEADER[] = "Sample1\tSample2\tDistance\tMismatches (proportion)\tMatch count\tMismatch count\n";
-static void put_dist_line(std::string &o, const char *n1, const char *n2, const skx_dist &d)
-{
-    put(o, "%s\t%s\t%.2f\t%.5f\t%llu\t%llu\n", n1, n2, d.distance, d.mismatch_prop, (unsigned long long)d.match_count, (unsigned long long)d.mismatch_count);
-}
-static int distance_text_names(const std::vector<const char *> &names, const skx_dist *d, char **buf, uint64_t *len)
-{
-    const uint64_t S = names.size();
-    Phase pt("distance.table_text");
-    // the rows of one first sample are formatted by one thread (a table of 1 000 samples is half a million printf calls, 20 MB)
-    const int T = (int)std::min<uint64_t>(std::max<uint64_t>(1, S / 16), std::min(32u, std::max(1u, std::thread::hardware_concurrency())));
-    std::vector<std::string> part(S);
-    std::atomic<uint64_t> next{0};
-    auto work = [&]() {
-        for (uint64_t i; (i = next.fetch_add(1)) < S;) {
-            size_t n = (size_t)(i * (2 * S - i - 1) / 2);               // pairs before row i
-            std::string &o = part[i];
-            for (uint64_t j = i + 1; j < S; j++, n++) put_dist_line(o, names[i], names[j], d[n]);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < T; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    std::string out = DIST_HEADER;
-    size_t total = out.size();
-    for (auto &x : part) total += x.size();
-    out.reserve(total);
-    for (auto &x : part) out += x;
-    return to_buf(out, buf, len);
-}
-static int write_text_file(const std::string &path, const char *buf, uint64_t len)
-{
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) { skx_set_error("cannot create %s", path.c_str()); return SKX_EIO; }
-    const bool ok = fwrite(buf, 1, len, f) == len;
-    if (fclose(f) != 0 || !ok) { skx_set_error("cannot write %s", path.c_str()); return SKX_EIO; }
-    return SKX_OK;
-}
-// `ska distance --tree / --clusters`: the tree and the clusters of the table the command has just computed (x may be NULL)
-static int distance_extras(skx_ctx *ctx, const std::vector<const char *> &names, const skx_dist *d, const skh_dist_extras *x)
-{
-    if (!x) return SKX_OK;
-    const int S = (int)names.size();
-    int r = SKX_OK;
-    if (x->tree) {
-        std::vector<skx_nj_join> joins((size_t)std::max(S - 1, 1));
-        { Phase pn("distance.nj"); if ((r = skx_dist_nj(ctx, d, S, joins.data())) != SKX_OK) return r; }
-        Phase pt("distance.tree_text");
-        char *buf = nullptr; uint64_t len = 0;
-        if ((r = skh_nj_newick(names.data(), joins.data(), S, &buf, &len)) != SKX_OK) return r;
-        r = write_text_file(x->tree, buf, len);
-        skx_free(buf);
-        if (r != SKX_OK) return r;
-    }
-    if (x->clusters) {
-        Phase pc("distance.clusters");
-        char *csv = nullptr, *dot = nullptr; uint64_t nc = 0, nd = 0;
-        if ((r = skh_distance_clusters(names.data(), d, S, x->cluster_snps, x->cluster_mismatches, &csv, &nc, &dot, &nd)) != SKX_OK) return r;
-        r = write_text_file(std::string(x->clusters) + ".clusters.csv", csv, nc);
-        if (r == SKX_OK) r = write_text_file(std::string(x->clusters) + ".graph.dot", dot, nd);
-        skx_free(csv); skx_free(dot);
-    }
-    return r;
-}
-static int distance_table(skx_array *a, double constant, int filt_ambig, const skh_dist_extras *x, char **buf, uint64_t *len)
-{
-    skx_array_info_t info; skx_array_info(a, &info);
-    const uint64_t S = info.n_samples;
-    std::vector<skx_dist> d(S * (S - 1) / 2 + 1);
-    int r;
-    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance(a, constant, filt_ambig, d.data())) != SKX_OK) return r; }
-    if (x) {
-        std::vector<const char *> names(S);
-        for (uint64_t i = 0; i < S; i++) names[i] = skx_array_name(a, i);
-        if ((r = distance_extras(skx_array_ctx(a), names, d.data(), x)) != SKX_OK) return r;
-    }
-    return distance_text(a, d, buf, len);
-}
-
-extern "C" int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len)
-{
-    return skh_distance_skf_tsv_extras(ctx, skf_file, min_freq, filt_ambig, nullptr, buf, len);
-}
-extern "C" int skh_distance_skf_tsv_extras(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *extras, char **buf,
-                                           uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
-    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
-    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
-    if (r != SKX_OK) return r;
-    r = distance_table(a, (double)constant, filt_ambig, extras, buf, len);
-    skx_array_free(a);
-    return r;
-    });
-}
-
-// the lines of distance_text_names' table that name a query, in its order (ascending first sample, then ascending second); d as
-// skx_array_distance_query lays it out: d[q * S + j] = the pair (query[q], j)
-static int distance_query_text(const std::vector<const char *> &names, const std::vector<int> &query, const skx_dist *d, char **buf, uint64_t *len)
-{
-    const uint64_t S = names.size();
-    Phase pt("distance.table_text");
-    std::vector<int> row_of(S, -1), sorted(query);
-    for (size_t q = 0; q < query.size(); q++) row_of[query[q]] = (int)q;
-    std::sort(sorted.begin(), sorted.end());
-    const int T = (int)std::min<uint64_t>(std::max<uint64_t>(1, S / 16), std::min(32u, std::max(1u, std::thread::hardware_concurrency())));
-    std::vector<std::string> part(S);
-    std::atomic<uint64_t> next{0};
-    auto work = [&]() {
-        for (uint64_t i; (i = next.fetch_add(1)) < S;) {
-            std::string &o = part[i];
-            if (row_of[i] >= 0) for (uint64_t j = i + 1; j < S; j++) put_dist_line(o, names[i], names[j], d[(uint64_t)row_of[i] * S + j]);
-            else for (auto it = std::upper_bound(sorted.begin(), sorted.end(), (int)i); it != sorted.end(); ++it)
-                put_dist_line(o, names[i], names[*it], d[(uint64_t)row_of[*it] * S + i]);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < T; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    std::string out = DIST_HEADER;
-    size_t total = out.size();
-    for (auto &x : part) total += x.size();
-    out.reserve(total);
-    for (auto &x : part) out += x;
-    return to_buf(out, buf, len);
-}
-extern "C" int skh_distance_query_tsv(skx_ctx *ctx, const char *skf_file, const char *query_skf, const char *const *names, int n_names, double min_freq,
-                                      int filt_ambig, char **buf, uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !skf_file || !buf || !len || n_names < 0 || (n_names && !names)) { skx_set_error("skh_distance_query_tsv: bad arguments"); return SKX_EINVAL; }
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_array *a = nullptr; int64_t removed = 0, constant = 0; int r;
-    std::vector<uint64_t> n_each;
-    if (query_skf) {                                                                   // `ska merge skf_file query_skf`, kept in memory
-        const char *files[2] = {skf_file, query_skf};
-        if ((r = merge_files(ctx, files, 2, &a, &n_each)) != SKX_OK) return r;
-    } else {
-        skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
-        if ((r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant)) != SKX_OK) return r;
-    }
-    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
-    skx_array_info_t info; skx_array_info(a, &info);
-    const uint64_t S = info.n_samples;
-    std::vector<const char *> all(S);
-    for (uint64_t i = 0; i < S; i++) all[i] = skx_array_name(a, i);
-    // the query set: the names (each its first match, as skx_array_delete_samples looks them up) and every sample the second file brought
-    std::vector<char> is_q(S, 0);
-    for (int n = 0; n < n_names; n++) {
-        uint64_t i = 0;
-        while (i < S && strcmp(all[i], names[n]) != 0) i++;
-        if (i == S) { skx_set_error("Could not find sample(s): {\"%s\"}", names[n]); return SKX_EINVAL; }                     // merge_ska_array.rs:252-254
-        is_q[i] = 1;
-    }
-    if (query_skf) for (uint64_t i = std::min<uint64_t>(n_each[0], S); i < S; i++) is_q[i] = 1;               // (the first file's samples come first)
-    std::vector<int> query;
-    for (uint64_t i = 0; i < S; i++) if (is_q[i]) query.push_back((int)i);
-    if (query.empty()) { skx_set_error("No query samples given"); return SKX_EINVAL; }
-    std::vector<skx_dist> d(query.size() * S);
-    {
-        Phase pd("distance.pair_sweep");
-        if (query_skf) { uint64_t rows = 0; r = skx_array_distance_query_filtered(a, min_freq, filt_ambig, query.data(), (int)query.size(), d.data(), &constant, &rows); }
-        else r = skx_array_distance_query(a, (double)constant, filt_ambig, query.data(), (int)query.size(), d.data());
-        if (r != SKX_OK) return r;
-    }
-    return distance_query_text(all, query, d.data(), buf, len);
-    });
-}
-
-// the header and one line per selected pair (ascending (i, j): the table's order), formatted in slices by a few threads
-static int distance_select_text(const std::vector<const char *> &names, const skx_dist_pair *p, uint64_t n, char **buf, uint64_t *len)
-{
-    Phase pt("distance.table_text");
-    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n / 4096, std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
-    std::vector<std::string> part(T);
-    auto work = [&](uint64_t t) { for (uint64_t x = n * t / T; x < n * (t + 1) / T; x++) put_dist_line(part[t], names[p[x].i], names[p[x].j], p[x].d); };
-    std::vector<std::thread> th;
-    for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &t : th) t.join();
-    std::string out = DIST_HEADER;
-    size_t total = out.size();
-    for (auto &x : part) total += x.size();
-    out.reserve(total);
-    for (auto &x : part) out += x;
-    return to_buf(out, buf, len);
-}
-extern "C" int skh_distance_select_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_select_spec *spec, char **buf, uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !skf_file || !spec || !buf || !len) { skx_set_error("skh_distance_select_tsv: bad arguments"); return SKX_EINVAL; }
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
-    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
-    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
-    if (r != SKX_OK) return r;
-    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
-    skx_array_info_t info; skx_array_info(a, &info);
-    std::vector<const char *> names(info.n_samples);
-    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
-    skx_dist_pair *pairs = nullptr; uint64_t n = 0;
-    skx_select_info si{0, 0, 0, 0};
-    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance_select_prefiltered(a, constant, filt_ambig, spec, &pairs, &n, &si)) != SKX_OK) return r; }
-    char msg[200];
-    snprintf(msg, sizeof msg, "Selected %llu lines of %llu candidate pairs: %llu bands of %llu samples, count buffer of %llu bytes", (unsigned long long)n,
-             (unsigned long long)si.candidates, (unsigned long long)si.bands, (unsigned long long)si.band_rows, (unsigned long long)si.count_buffer_bytes);
-    skh_log(2, "ska::generic_modes", msg);
-    r = distance_select_text(names, pairs, n, buf, len);
-    skx_free(pairs);
-    return r;
-    });
-}
-
-// `ska distance --mst`: the forest's lines as text, and with levels (n_levels > 0) the ladder's CSV from the same forest
-static int distance_mst_run(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, const double *levels, int n_levels, char **buf,
-                            uint64_t *len, char **csv, uint64_t *csv_len)
-{
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
-    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
-    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
-    if (r != SKX_OK) return r;
-    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
-    skx_array_info_t info; skx_array_info(a, &info);
-    std::vector<const char *> names(info.n_samples);
-    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
-    skx_dist_pair *pairs = nullptr; uint64_t n = 0;
-    skx_mst_info mi{0, 0, 0, 0, 0, 0, 0};
-    { Phase pd("distance.pair_sweep"); if ((r = skx_array_distance_mst_prefiltered(a, constant, filt_ambig, spec, &pairs, &n, &mi)) != SKX_OK) return r; }
-    char msg[260];
-    snprintf(msg, sizeof msg, "Spanning forest of %llu lines in %llu trees from %llu candidate pairs: %llu bands of %llu samples, count buffer of %llu bytes, at most %llu rounds a band",
-             (unsigned long long)mi.edges, (unsigned long long)mi.components, (unsigned long long)mi.candidates, (unsigned long long)mi.bands, (unsigned long long)mi.band_rows,
-             (unsigned long long)mi.count_buffer_bytes, (unsigned long long)mi.rounds);
-    skh_log(2, "ska::generic_modes", msg);
-    r = distance_select_text(names, pairs, n, buf, len);
-    if (r == SKX_OK && n_levels > 0 && info.n_samples) {
-        r = skh_mst_levels_csv(names.data(), pairs, n, (int)info.n_samples, levels, n_levels, csv, csv_len);
-        if (r != SKX_OK) { skx_free(*buf); *buf = nullptr; }
-    }
-    skx_free(pairs);
-    return r;
-}
-extern "C" int skh_distance_mst_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skx_mst_spec *spec, char **buf, uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !skf_file || !spec || !buf || !len) { skx_set_error("skh_distance_mst_tsv: bad arguments"); return SKX_EINVAL; }
-    return distance_mst_run(ctx, skf_file, min_freq, filt_ambig, spec, nullptr, 0, buf, len, nullptr, nullptr);
-    });
-}
-
-// `ska distance ... --sites PREFIX`: the selected lines from the array loaded with its split k-mers, then the rows behind each line's Distance
-extern "C" int skh_distance_sites(skx_ctx *ctx, const char *skf_file, double min_freq, const skx_select_spec *spec, const skx_mst_spec *mst, const char *prefix,
-                                  uint64_t max_records, char **buf, uint64_t *len)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !skf_file || !prefix || !buf || !len || !spec == !mst) { skx_set_error("skh_distance_sites: bad arguments"); return SKX_EINVAL; }
-    *buf = nullptr; *len = 0;
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_array *a = nullptr; int r;
-    { const char *in[1] = {skf_file}; if ((r = skh_load_array(ctx, in, 1, 1, &a)) != SKX_OK) return r; }
-    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
-    skx_array_info_t info; skx_array_info(a, &info);
-    std::vector<const char *> names(info.n_samples);
-    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
-    skx_dist_pair *pairs = nullptr; uint64_t n_pairs = 0;
-    {
-        Phase pd("distance.pair_sweep");
-        int64_t constant = 0; uint64_t rows = 0;
-        r = spec ? skx_array_distance_select(a, min_freq, 1, spec, &pairs, &n_pairs, &constant, &rows, nullptr)
-                 : skx_array_distance_mst(a, min_freq, 1, mst, &pairs, &n_pairs, &constant, &rows, nullptr);
-        if (r != SKX_OK) return r;
-    }
-    struct FreePairs { skx_dist_pair *p; ~FreePairs() { skx_free(p); } } free_pairs{pairs};
-    if ((r = distance_select_text(names, pairs, n_pairs, buf, len)) != SKX_OK) return r;
-    std::vector<uint32_t> ij(2 * n_pairs);
-    for (uint64_t p = 0; p < n_pairs; p++) { ij[2 * p] = pairs[p].i; ij[2 * p + 1] = pairs[p].j; }
-    skx_pair_site *rec = nullptr; skx_key *keys = nullptr; uint64_t n = 0;
-    // (the phases distance.sites_count and distance.sites_write are recorded by the call itself: both happen inside it)
-    if ((r = skx_array_pair_sites(a, min_freq, ij.data(), n_pairs, max_records, &rec, &keys, nullptr, &n)) != SKX_OK) return r;
-    struct FreeRec { skx_pair_site *r; skx_key *k; ~FreeRec() { skx_free(r); skx_free(k); } } free_rec{rec, keys};
-    char msg[160];
-    snprintf(msg, sizeof msg, "Sites: %llu records of %llu lines", (unsigned long long)n, (unsigned long long)n_pairs);
-    skh_log(2, "ska::generic_modes", msg);
-    Phase pt("distance.sites_text");
-    // a record's line, formatted in slices by a few threads as the table's lines are
-    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n / 4096, std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
-    std::vector<std::string> part(T);
-    auto work = [&](uint64_t t) {
-        std::string &o = part[t];
-        char up[32], lo[32];
-        for (uint64_t x = n * t / T; x < n * (t + 1) / T; x++) {
-            const skx_dist_pair &p = pairs[rec[x].pair];
-            skh_key_arms(&keys[x], info.k, up, lo);
-            o += names[p.i]; o += '\t'; o += names[p.j]; o += '\t'; o += up; o += '\t'; o += lo; o += '\t';
-            o += (char)rec[x].base_i; o += '\t'; o += (char)rec[x].base_j; o += '\n';
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &t : th) t.join();
-    // (the slices go to the file one after the other: the text, gigabytes for a large selection, is never held twice)
-    const std::string path = std::string(prefix) + ".sites.tsv";
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) { skx_set_error("cannot create %s", path.c_str()); return SKX_EIO; }
-    bool ok = fputs("Sample1\tSample2\tUpper\tLower\tBase1\tBase2\n", f) >= 0;
-    for (auto &x : part) ok = ok && fwrite(x.data(), 1, x.size(), f) == x.size();
-    if (fclose(f) != 0 || !ok) { skx_set_error("cannot write %s", path.c_str()); return SKX_EIO; }
-    return SKX_OK;
-    });
-}
-
-// `ska distance --no-table`: the extras' files from the banded sweep (x names at least one).  What reaches the host is S labels and S - 1 joins
-extern "C" int skh_distance_banded_files(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, const skh_dist_extras *x)
-{
-    return skx_guarded([&]() -> int {
-    if (!ctx || !skf_file || !x || (!x->tree && !x->clusters)) { skx_set_error("skh_distance_banded_files: bad arguments"); return SKX_EINVAL; }
-    skh_log(2, "ska::generic_modes", "Calculating distances");                                            // generic_modes.rs:170
-    skx_filter_spec fs{min_freq, 0, SKX_FILTER_NO_CONST, 0, 0, 1};
-    skx_array *a = nullptr; int64_t removed = 0, constant = 0;
-    int r = skx_array_load_filtered(ctx, skf_file, &fs, &a, &removed, &constant);
-    if (r != SKX_OK) return r;
-    struct Free { skx_array *a; ~Free() { skx_array_free(a); } } free_a{a};
-    skx_array_info_t info; skx_array_info(a, &info);
-    const int S = (int)info.n_samples;
-    std::vector<const char *> names(info.n_samples);
-    for (uint64_t i = 0; i < info.n_samples; i++) names[i] = skx_array_name(a, i);
-    std::vector<uint32_t> labels((size_t)std::max(S, 1)); std::vector<skx_nj_join> joins((size_t)std::max(S - 1, 1));
-    const skx_banded_spec spec{x->cluster_snps, x->cluster_mismatches, 0};
-    skx_banded_info bi{0, 0, 0, 0, 0};
-    // (the phases distance.pair_sweep and distance.nj are recorded by the call itself: both happen inside it)
-    if ((r = skx_array_distance_banded_prefiltered(a, constant, filt_ambig, &spec, x->clusters ? labels.data() : nullptr, x->tree ? joins.data() : nullptr, &bi)) != SKX_OK) return r;
-    char msg[200];
-    snprintf(msg, sizeof msg, "No table: %llu bands of %llu samples, count buffer of %llu bytes; %llu pairs within the cluster thresholds, %llu clusters",
-             (unsigned long long)bi.bands, (unsigned long long)bi.band_rows, (unsigned long long)bi.count_buffer_bytes, (unsigned long long)bi.edges, (unsigned long long)bi.clusters);
-    skh_log(2, "ska::generic_modes", msg);
-    if (x->tree) {
-        Phase pt("distance.tree_text");
-        char *buf = nullptr; uint64_t len = 0;
-        if ((r = skh_nj_newick(names.data(), joins.data(), S, &buf, &len)) != SKX_OK) return r;
-        r = write_text_file(x->tree, buf, len);
-        skx_free(buf);
-        if (r != SKX_OK) return r;
-    }
-    if (x->clusters) {
-        Phase pc("distance.clusters");
-        char *csv = nullptr; uint64_t nc = 0;
-        if ((r = skh_clusters_csv(names.data(), labels.data(), S, &csv, &nc)) != SKX_OK) return r;
-        r = write_text_file(std::string(x->clusters) + ".clusters.csv", csv, nc);
-        skx_free(csv);
-    }
-    return r;
-    });
-}
-
 extern "C" int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, int filter_type, int mask_ambig, int ignore_const_gaps,
                                    double min_freq, int filter_ambig_as_missing, int fd)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array *a = nullptr; int r;
     if (n_inputs == 1) {
         skx_filter_spec fs{min_freq, filter_ambig_as_missing, filter_type, mask_ambig, ignore_const_gaps, 0};
@@ -557,7 +128,7 @@ extern "C" int skh_align_inputs_fd(skx_ctx *ctx, const char *const *inputs, int 
 
 extern "C" int skh_nk(skx_array *a, int full_info, char **buf, uint64_t *len)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array_info_t info; skx_array_info(a, &info);
     std::string o;
     put(o, "ska_version=%s\nk=%d\nk_bits=%d\nrc=%s\nk-mers=%llu\nsamples=%llu\n", skx_array_version(a), info.k, info.k_bits,
@@ -593,7 +164,7 @@ extern "C" int skh_nk(skx_array *a, int full_info, char **buf, uint64_t *len)
 
 extern "C" int skh_save_skf(skx_array *a, const char *out_prefix)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     std::string p(out_prefix);
     if (p.size() < 4 || p.compare(p.size() - 4, 4, ".skf") != 0) p += ".skf";           // generic_modes.rs:272-276
     return skx_array_save(a, p.c_str());
@@ -602,7 +173,7 @@ extern "C" int skh_save_skf(skx_array *a, const char *out_prefix)
 
 extern "C" int skh_load_array(skx_ctx *ctx, const char *const *inputs, int n_inputs, int threads, skx_array **out)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     if (n_inputs == 1) {                                                                // io_utils.rs:65-75, lib.rs:635-661
         int r = skx_array_load(ctx, inputs[0], 64, out);
         if (r != SKX_EFORMAT) return r;                                                 // only "does not fit u64" falls through to u128; a missing
@@ -620,9 +191,9 @@ extern "C" int skh_load_array(skx_ctx *ctx, const char *const *inputs, int n_inp
 
 // the files of `ska merge` loaded and merged in memory (skh_merge saves the result, `ska distance --query-skf` sweeps it)
 // n_each (optional): the samples each file brought, in file order -- the merged array holds them in that order
-static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, skx_array **merged, std::vector<uint64_t> *n_each)
+int skh::merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, skx_array **merged, std::vector<uint64_t> *n_each)
 {
-    if (n_files < 2) { skx_set_error("Need at least two files to merge"); return SKX_EINVAL; }                    // lib.rs:729-731
+    if (n_files < 2) { set_error("Need at least two files to merge"); return SKX_EINVAL; }                    // lib.rs:729-731
     std::vector<skx_array *> arrs(n_files, nullptr);
     auto cleanup = [&]() { for (auto p : arrs) if (p) skx_array_free(p); };
     const auto t_m0 = std::chrono::steady_clock::now();
@@ -658,14 +229,14 @@ static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, 
         bits = 64;
         if (skx_array_load(ctx, skf_files[0], 64, &arrs[0]) != SKX_OK) {
             bits = 128;
-            if (skx_array_load(ctx, skf_files[0], 128, &arrs[0]) != SKX_OK) { skx_set_error("Could not read input file: %s", skf_files[0]); return SKX_EIO; }
+            if (skx_array_load(ctx, skf_files[0], 128, &arrs[0]) != SKX_OK) { set_error("Could not read input file: %s", skf_files[0]); return SKX_EIO; }
         }
         std::fill(rc.begin(), rc.end(), SKX_OK);
         load_team(1, rc);
     }
     for (int i = 1; i < n_files; i++)
         if (rc[i] != SKX_OK) {                                                                                // generic_modes.rs:99-100
-            cleanup(); skx_set_error("Failed to load input file (inconsistent k-mer lengths?): %s", skf_files[i]); return SKX_EINVAL;
+            cleanup(); set_error("Failed to load input file (inconsistent k-mer lengths?): %s", skf_files[i]); return SKX_EINVAL;
         }
     skx_phase_add("merge.other_files_wall", since(t_m1));
     if (n_each) for (auto p : arrs) { skx_array_info_t info; skx_array_info(p, &info); n_each->push_back(info.n_samples); }
@@ -682,7 +253,7 @@ static int merge_files(skx_ctx *ctx, const char *const *skf_files, int n_files, 
 }
 extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files, const char *out_prefix)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array *m = nullptr;
     int r = merge_files(ctx, skf_files, n_files, &m);
     if (r != SKX_OK) return r;
@@ -694,7 +265,7 @@ extern "C" int skh_merge(skx_ctx *ctx, const char *const *skf_files, int n_files
 
 extern "C" int skh_delete(skx_array *a, const char *const *names, int n_names, const char *out_file)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     int r = skx_array_delete_samples(a, names, n_names);
     if (r != SKX_OK) return r;
     return skh_save_skf(a, out_file);                                                                             // generic_modes.rs:200-209 (same suffix rule)
@@ -704,7 +275,7 @@ extern "C" int skh_delete(skx_array *a, const char *const *names, int n_names, c
 extern "C" int skh_weed(skx_array *a, const char *weed_file, int reverse, double min_freq, int filter_ambig_as_missing, int filter_type,
                         int ambig_mask, int ignore_const_gaps, const char *out_file)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array_info_t info; skx_array_info(a, &info);
     if (weed_file) {
         // RefSka::new(k, file, rc, ..) (generic_modes.rs:222-235): FASTA only; its split k-mers = the keys of the file's dictionary
@@ -767,7 +338,7 @@ std::string lower_exp(double v)
 
 extern "C" int skh_cov_fit(const double *counts, uint64_t n, double *w0_out, double *c_out, uint64_t *cutoff)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     // argmin BFGS (inverse-Hessian form) + BacktrackingLineSearch(ArmijoCondition(1e-4), contraction 0.9) from (0.8, 20), H0 = I,
     // tolerance_cost 1e-6, max_iters 20 (coverage.rs:176-196)
     double x[2] = {0.8, 20.0}, H[2][2] = {{1.0, 0.0}, {0.0, 1.0}}, g[2];
@@ -798,7 +369,7 @@ extern "C" int skh_cov_fit(const double *counts, uint64_t n, double *w0_out, dou
         for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) r[a][b] = m[a][0] * t2[0][b] + m[a][1] * t2[1][b] + rho * s[a] * s[b];
         memcpy(H, r, sizeof r);
     }
-    if (!converged) { skx_set_error("Couldn't fit coverage model: Optimiser did not converge: Maximum number of iterations reached"); return SKX_EINVAL; }   // :216-220
+    if (!converged) { set_error("Couldn't fit coverage model: Optimiser did not converge: Maximum number of iterations reached"); return SKX_EINVAL; }   // :216-220
     uint64_t cut = 1;                                                                                            // find_cutoff, :349-363
     while (cut < n) { if (cov_a(x[0], (double)cut) - cov_b(x[0], x[1], (double)cut) < 0.0) break; cut++; }
     *w0_out = x[0]; *c_out = x[1]; *cutoff = cut;
@@ -808,7 +379,7 @@ extern "C" int skh_cov_fit(const double *counts, uint64_t n, double *w0_out, dou
 
 extern "C" int skh_cov(skx_ctx *ctx, const char *fastq_fwd, const char *fastq_rev, int k, int rc, char **text, uint64_t *len, uint64_t *cutoff)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     std::vector<uint32_t> hist(1000);
     int r = skx_cov_histogram(ctx, fastq_fwd, fastq_rev, k, rc, hist.data());
     if (r != SKX_OK) return r;
@@ -836,13 +407,13 @@ namespace {
 // the common head of the three sharded modes: this rank's dictionaries -> key-table all-gather -> the rank's columns over the global rows
 int sharded_array(skx_ctx *ctx, skx_comm *comm, const skh_job *job, uint64_t *lo_out, uint64_t *hi_out, skx_array **out)
 {
-    if (!ctx || !comm || !job || job->n_samples <= 0) { skx_set_error("bad arguments"); return SKX_EINVAL; }
+    if (!ctx || !comm || !job || job->n_samples <= 0) { set_error("bad arguments"); return SKX_EINVAL; }
     const int rank = skx_comm_rank(comm), world = skx_comm_world(comm);
     uint64_t lo = 0, hi = 0;
     // (a rank that cannot start -- no share of the samples -- goes through the status agreement below like one whose build failed: its
     // peers must not be left waiting in the all-reduce)
     int r = skx_shard_range((uint64_t)job->n_samples, rank, world, &lo, &hi);
-    if (r == SKX_OK && hi <= lo) { skx_set_error("rank %d: no samples (fewer samples than ranks)", rank); r = SKX_EINVAL; }
+    if (r == SKX_OK && hi <= lo) { set_error("rank %d: no samples (fewer samples than ranks)", rank); r = SKX_EINVAL; }
     skx_dictset *ds = nullptr; skx_keyset *ks = nullptr, *rows = nullptr;
     if (r == SKX_OK) {
         Phase p("sharded.dictionaries");
@@ -876,11 +447,11 @@ std::string part_name(const char *prefix, int rank, int world) { return std::str
 
 extern "C" int skh_build_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array *arr = nullptr; uint64_t lo, hi;
     int r = sharded_array(ctx, comm, job, &lo, &hi, &arr);
     if (r != SKX_OK) return r;
-    if (!job->output) { skx_array_free(arr); skx_set_error("-o <output> is required"); return SKX_EINVAL; }
+    if (!job->output) { skx_array_free(arr); set_error("-o <output> is required"); return SKX_EINVAL; }
     const int rank = skx_comm_rank(comm), world = skx_comm_world(comm);
     r = skx_array_save(arr, part_name(job->output, rank, world).c_str());      // local counts: each part is a self-consistent MergeSkaArray
     skx_array_free(arr);
@@ -894,7 +465,7 @@ extern "C" int skh_build_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *jo
         if (job->merge_parts) {
             if (world == 1) {                                                    // one part is the array itself
                 std::string o(job->output); if (o.size() < 4 || o.compare(o.size() - 4, 4, ".skf") != 0) o += ".skf";
-                if (rename(parts[0].c_str(), o.c_str()) != 0) { skx_set_error("cannot rename %s", parts[0].c_str()); r = SKX_EIO; }
+                if (rename(parts[0].c_str(), o.c_str()) != 0) { set_error("cannot rename %s", parts[0].c_str()); r = SKX_EIO; }
             } else if ((r = skh_merge(ctx, cp.data(), world, job->output)) == SKX_OK)
                 for (auto &x : parts) unlink(x.c_str());
         } else {
@@ -909,7 +480,7 @@ extern "C" int skh_build_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *jo
 
 extern "C" int skh_align_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array *arr = nullptr; uint64_t lo, hi;
     int r = sharded_array(ctx, comm, job, &lo, &hi, &arr);
     if (r != SKX_OK) return r;
@@ -923,18 +494,18 @@ extern "C" int skh_align_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *jo
     uint64_t offset = 0, total = 0;
     for (int i = 0; i < job->n_samples; i++) { const uint64_t sz = strlen(job->names[i]) + kept + 3; if ((uint64_t)i < lo) offset += sz; total += sz; }
     const int rank = skx_comm_rank(comm);
-    if (!job->output) { skx_set_error("with several GPUs the alignment goes to a file: give -o"); return done(SKX_EINVAL); }
+    if (!job->output) { set_error("with several GPUs the alignment goes to a file: give -o"); return done(SKX_EINVAL); }
     if (rank == 0) {
         int fd0 = open(job->output, O_RDWR | O_CREAT | O_TRUNC, 0644);
-        if (fd0 < 0 || ftruncate(fd0, (off_t)total) != 0) { if (fd0 >= 0) close(fd0); skx_set_error("cannot create output file"); r = SKX_EIO; }
+        if (fd0 < 0 || ftruncate(fd0, (off_t)total) != 0) { if (fd0 >= 0) close(fd0); set_error("cannot create output file"); r = SKX_EIO; }
         else close(fd0);
     }
     const int rb = skx_comm_barrier(comm);                                       // the file exists at its full size
     if (r != SKX_OK) return done(r);
     if (rb != SKX_OK) return done(rb);
     int fd = open(job->output, O_RDWR);
-    if (fd < 0) { skx_set_error("cannot open output file"); return done(SKX_EIO); }
-    if (lseek(fd, (off_t)offset, SEEK_SET) < 0) { close(fd); skx_set_error("cannot seek in output file"); return done(SKX_EIO); }
+    if (fd < 0) { set_error("cannot open output file"); return done(SKX_EIO); }
+    if (lseek(fd, (off_t)offset, SEEK_SET) < 0) { close(fd); set_error("cannot seek in output file"); return done(SKX_EIO); }
     { Phase p("align.write_fasta"); r = skx_array_write_fasta(arr, fd); }
     close(fd);
     const int rb2 = skx_comm_barrier(comm);
@@ -944,7 +515,7 @@ extern "C" int skh_align_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *jo
 
 extern "C" int skh_distance_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job *job)
 {
-    return skx_guarded([&]() -> int {
+    return guarded([&]() -> int {
     skx_array *arr = nullptr; uint64_t lo, hi;
     int r = sharded_array(ctx, comm, job, &lo, &hi, &arr);
     if (r != SKX_OK) return r;
@@ -964,7 +535,7 @@ extern "C" int skh_distance_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job 
         char *buf = nullptr; uint64_t len = 0;
         if ((r = distance_text_names(names, d.data(), &buf, &len)) != SKX_OK) return done(r);
         FILE *f = job->output ? fopen(job->output, "wb") : stdout;
-        if (!f) { skx_free(buf); skx_set_error("cannot create output file"); return done(SKX_EIO); }
+        if (!f) { skx_free(buf); set_error("cannot create output file"); return done(SKX_EIO); }
         fwrite(buf, 1, len, f);
         if (f != stdout) fclose(f); else fflush(stdout);
         skx_free(buf);
@@ -976,20 +547,14 @@ extern "C" int skh_distance_sharded(skx_ctx *ctx, skx_comm *comm, const skh_job 
 // ------------------------------------------------------------------------------------------ CLI
 extern char **environ;
 namespace {
-struct Args {
-    std::vector<std::string> pos;
-    std::vector<std::pair<std::string, std::string>> opt;
-    bool has(const std::string &k) const { for (auto &o : opt) if (o.first == k) return true; return false; }
-    std::string get(const std::string &k, const std::string &d = "") const { for (auto &o : opt) if (o.first == k) return o.second; return d; }
-};
 const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min-qual", "--qual-filter", "--proportion-reads",
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
                             "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels", "--sites", "--sites-max",
                             "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
-int fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 }
+int skh::fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
 const char *skh_usage_line(const char *cmd);       // ska_help.cpp
 // simple_logger's line (lib.rs:559-563: Info with -v, Warn without): "<UTC time> <LEVEL> [<target>] <message>" on stderr
 static bool g_verbose = false;
@@ -1001,24 +566,65 @@ extern "C" void skh_log(int level, const char *target, const char *message)     
     char tb[40]; strftime(tb, sizeof tb, "%Y-%m-%dT%H:%M:%S", &tmv);
     fprintf(stderr, "%s.%03ldZ %-5s [%s] %s\n", tb, ts.tv_nsec / 1000000, level <= 0 ? "ERROR" : level == 1 ? "WARN" : "INFO", target, message);
 }
-namespace {
 // clap's wording for what its derive macros refuse (cli.rs: value_parser / value_enum / required): exit code 2, the reason, the hint
-int clap_invalid(const std::string &value, const char *arg, const char *why)
+int skh::clap_invalid(const std::string &value, const char *arg, const char *why)
 {
     fprintf(stderr, "error: invalid value '%s' for '%s': %s\n\nFor more information, try '--help'.\n", value.c_str(), arg, why);
     return 2;
 }
-int clap_possible(const std::string &value, const char *arg, const char *values)
+int skh::clap_possible(const std::string &value, const char *arg, const char *values)
 {
     fprintf(stderr, "error: invalid value '%s' for '%s'\n  [possible values: %s]\n\nFor more information, try '--help'.\n", value.c_str(), arg, values);
     return 2;
 }
-int clap_missing(const char *cmd, const char *args)
+int skh::clap_missing(const char *cmd, const char *args)
 {
     fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n\nUsage: %s\n\nFor more information, try '--help'.\n", args, skh_usage_line(cmd));
     return 2;
 }
-int engine_fail() { fprintf(stderr, "error: %s\n", skx_last_error()); return 101; }   // Rust panics exit with 101
+// how clap spells an option that takes a value, for every option a refusal names (an option without a value is spelled as it is given)
+const char *skh::clap_arg(const char *flag)
+{
+    static const char *const SPELLING[][2] = {
+        {"-o", "-o <OUTPUT>"}, {"-f", "-f <FILE_LIST>"}, {"--gpus", "--gpus <GPUS>"},
+        {"--groups", "--groups <FILE>"}, {"--min-group-size", "--min-group-size <N>"}, {"--samples", "--samples <NAMES>"}, {"--samples-file", "--samples-file <FILE>"},
+        {"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"}, {"--cluster-mismatches", "--cluster-mismatches <P>"},
+        {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"},
+        {"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"}, {"--closest", "--closest <K>"},
+        {"--mst-clusters", "--mst-clusters <PREFIX>"}, {"--levels", "--levels <L1,L2,...>"}, {"--sites", "--sites <PREFIX>"}, {"--sites-max", "--sites-max <N>"},
+        {"--min-in", "--min-in <P>"}, {"--max-out", "--max-out <Q>"}};
+    for (auto &sp : SPELLING) if (!strcmp(flag, sp[0])) return sp[1];
+    return flag;
+}
+int skh::clap_conflict(const char *cmd, const char *x, const char *y)
+{
+    fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", clap_arg(x), clap_arg(y), skh_usage_line(cmd));
+    return 2;
+}
+int skh::conflicts(const char *cmd, const Args &a, bool multi, std::initializer_list<const char *> owners, std::initializer_list<const char *> others)
+{
+    for (const char *x : owners)
+        for (const char *y : others)
+            if (a.has(x) && (a.has(y) || (multi && !strcmp(y, "--gpus")))) return clap_conflict(cmd, x, y);
+    return 0;
+}
+int skh::clap_uint(const std::string &v, const char *arg, unsigned long long min, const char *why_below, bool check_erange)
+{
+    if (v.empty()) return clap_invalid(v, arg, "cannot parse integer from empty string");
+    if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, arg, "invalid digit found in string");
+    errno = 0;
+    const unsigned long long m = strtoull(v.c_str(), nullptr, 10);
+    if (check_erange && errno == ERANGE) return clap_invalid(v, arg, "number too large to fit in target type");
+    return m < min ? clap_invalid(v, arg, why_below) : 0;
+}
+int skh::clap_float(const std::string &v, const char *arg, double lo, double hi, const char *why_outside)
+{
+    if (!lo_float(v)) return clap_invalid(v, arg, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
+    const double t = strtod(v.c_str(), nullptr);
+    return t >= lo && t <= hi ? 0 : clap_invalid(v, arg, why_outside);
+}
+int skh::engine_fail() { fprintf(stderr, "error: %s\n", skx_last_error()); return 101; }   // Rust panics exit with 101
+namespace {
 int parse_filter(const std::string &s)
 {
     if (s == "no-filter") return SKX_FILTER_NONE;
@@ -1070,89 +676,26 @@ int open_comm(skx_ctx *ctx, int rank, int world, skx_comm **out)
     uint8_t id[SKX_COMM_ID_BYTES];
     const char *idf = getenv("SKX_COMM_ID_FILE");
     if (world == 1 && !idf) return skx_comm_create_local(ctx, 0, 1, nullptr, out);      // a single rank exchanges with nobody: no RCCL needed (the library's own directory, removed with the communicator)
-    if (world > 1 && !idf) { skx_set_error("SKX_WORLD > 1 needs SKX_COMM_ID_FILE (where rank 0 leaves the RCCL id) or SKX_COMM_DIR"); return SKX_EINVAL; }
+    if (world > 1 && !idf) { set_error("SKX_WORLD > 1 needs SKX_COMM_ID_FILE (where rank 0 leaves the RCCL id) or SKX_COMM_DIR"); return SKX_EINVAL; }
     if (rank == 0) {
         int r = skx_comm_unique_id(id);
         if (r != SKX_OK) return r;
         if (idf) {
             const std::string tmp = std::string(idf) + ".tmp";
             FILE *f = fopen(tmp.c_str(), "wb");
-            if (!f || fwrite(id, 1, sizeof id, f) != sizeof id) { if (f) fclose(f); skx_set_error("cannot write %s", tmp.c_str()); return SKX_EIO; }
+            if (!f || fwrite(id, 1, sizeof id, f) != sizeof id) { if (f) fclose(f); set_error("cannot write %s", tmp.c_str()); return SKX_EIO; }
             fclose(f);
-            if (rename(tmp.c_str(), idf) != 0) { skx_set_error("cannot publish %s", idf); return SKX_EIO; }
+            if (rename(tmp.c_str(), idf) != 0) { set_error("cannot publish %s", idf); return SKX_EIO; }
         }
     } else {
         FILE *f = nullptr;
         for (int i = 0; i < 6000 && !(f = fopen(idf, "rb")); i++) usleep(20000);               // two minutes
-        if (!f || fread(id, 1, sizeof id, f) != sizeof id) { if (f) fclose(f); skx_set_error("rank %d: no RCCL id at %s", rank, idf); return SKX_EIO; }
+        if (!f || fread(id, 1, sizeof id, f) != sizeof id) { if (f) fclose(f); set_error("rank %d: no RCCL id at %s", rank, idf); return SKX_EIO; }
         fclose(f);
     }
     return skx_comm_create(ctx, rank, world, id, out);
 }
-// --tree / --clusters / --cluster-snps / --cluster-mismatches of `ska distance`
-struct DistExtras {
-    std::string tree, clusters; skh_dist_extras x{};
-    explicit DistExtras(const Args &a) : tree(a.get("--tree")), clusters(a.get("--clusters"))
-    {
-        x.tree = a.has("--tree") ? tree.c_str() : nullptr; x.clusters = a.has("--clusters") ? clusters.c_str() : nullptr;
-        x.cluster_snps = atof(a.get("--cluster-snps", "10").c_str()); x.cluster_mismatches = atof(a.get("--cluster-mismatches", "1.0").c_str());
-    }
-    const skh_dist_extras *get() const { return x.tree || x.clusters ? &x : nullptr; }
-};
-// --query / --query-file of `ska distance`: the names of both, repeats collapsed.  0, or the exit code after the refusal was printed
-const struct { const char *flag, *arg; } QUERY_OPTS[] = {{"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
-bool has_query(const Args &a) { for (auto &q : QUERY_OPTS) if (a.has(q.flag)) return true; return false; }
-// --max-snps / --max-mismatches / --closest of `ska distance`: the lines of the table picked on the device (skh_distance_select_tsv)
-const struct { const char *flag, *arg; } SELECT_OPTS[] = {{"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"}, {"--closest", "--closest <K>"}};
-bool has_select(const Args &a) { for (auto &q : SELECT_OPTS) if (a.has(q.flag)) return true; return false; }
-skx_select_spec select_spec(const Args &a)
-{
-    skx_select_spec sp{-1.0, -1.0, 0, 0};
-    if (a.has("--max-snps")) sp.max_snps = strtod(a.get("--max-snps").c_str(), nullptr);
-    if (a.has("--max-mismatches")) sp.max_mismatches = strtod(a.get("--max-mismatches").c_str(), nullptr);
-    if (a.has("--closest")) sp.closest = (int32_t)std::min<unsigned long long>(strtoull(a.get("--closest").c_str(), nullptr, 10), INT32_MAX);
-    return sp;
-}
-// --mst / --mst-clusters / --levels of `ska distance`: the table's minimum spanning forest (skx_array_distance_mst) and its clusters at a ladder of levels
-const char *MST_LEVELS_ARG = "--levels <L1,L2,...>", *MST_DEFAULT_LEVELS = "250,100,50,25,10,5,0";
-constexpr size_t MST_MAX_LEVELS = 16;
-bool lo_float(const std::string &v);                                              // (below: what Rust's float parser takes)
-// the comma-separated levels -> out; nullptr, or why the list does not stand (the values are checked by validate_cli before they are used)
-const char *parse_levels(const std::string &v, std::vector<double> &out)
-{
-    out.clear();
-    size_t at = 0;
-    for (;;) {
-        const size_t end = std::min(v.find(',', at), v.size());
-        const std::string t = v.substr(at, end - at);
-        if (t.empty()) return "cannot parse float from empty string";
-        if (!lo_float(t)) return "invalid float literal";
-        const double x = strtod(t.c_str(), nullptr);
-        if (!(x >= 0.0)) return "a level must be zero or more";
-        if (std::find(out.begin(), out.end(), x) != out.end()) return "a level is given twice";
-        out.push_back(x);
-        if (out.size() > MST_MAX_LEVELS) return "at most 16 levels";
-        if (end == v.size()) return nullptr;
-        at = end + 1;
-    }
-}
-int read_query_names(const Args &a, std::vector<std::string> &names)
-{
-    auto add = [&](const std::string &n) { if (!n.empty() && std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n); };
-    for (auto &o : a.opt) {
-        if (o.first == "--query") { std::istringstream ls(o.second); std::string t; while (std::getline(ls, t, ',')) add(t); }
-        else if (o.first == "--query-file") {                                          // io_utils::get_input_list as `ska delete -f` reads it: first column
-            std::ifstream in(o.second);
-            if (!in) return fail("Unable to open file_list");
-            std::string line;
-            while (std::getline(in, line)) { std::istringstream ls(line); std::string t; if (ls >> t) add(t); }
-        }
-    }
-    return 0;
-}
 // --groups / --min-group-size / --samples / --samples-file of `ska align`: alignments of subsets from one load (skh_align_groups, skh_align_samples_fd)
-const struct { const char *flag, *arg; } SUBSET_OPTS[] = {{"--groups", "--groups <FILE>"}, {"--min-group-size", "--min-group-size <N>"}, {"--samples", "--samples <NAMES>"},
-                                                          {"--samples-file", "--samples-file <FILE>"}};
 int read_subset_names(const Args &a, std::vector<std::string> &names)
 {
     auto add = [&](const std::string &n) { if (!n.empty() && std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n); };
@@ -1383,7 +926,8 @@ int main_sharded(skx_ctx *ctx, const std::string &cmd, const Args &a, int rank, 
     skx_comm_destroy(comm);
     return rcode;
 }
-int emit(const std::string &out_path, const char *buf, uint64_t len)                 // io_utils::set_ostream
+}  // namespace
+int skh::emit(const std::string &out_path, const char *buf, uint64_t len)                 // io_utils::set_ostream
 {
     if (out_path.empty()) { fwrite(buf, 1, len, stdout); fflush(stdout); return 0; }
     FILE *f = fopen(out_path.c_str(), "wb");
@@ -1391,13 +935,8 @@ int emit(const std::string &out_path, const char *buf, uint64_t len)            
     fwrite(buf, 1, len, f); fclose(f);
     return 0;
 }
-}  // namespace
-
-namespace {
-// What clap refuses before lib.rs::main runs (cli.rs: required arguments, the argument groups of build / delete, value_parser and value_enum
-// of every option): the same refusals in clap's wording, before the banner and before a device is touched.  0: the command line stands.
 // what Rust's f32::from_str takes: decimal with optional sign / exponent, "inf", "infinity", "nan" (any case)
-bool lo_float(const std::string &v)
+bool skh::lo_float(const std::string &v)
 {
     std::string l; for (char c : v) l.push_back((char)tolower((unsigned char)c));
     const std::string u = (!l.empty() && (l[0] == '+' || l[0] == '-')) ? l.substr(1) : l;
@@ -1413,23 +952,41 @@ bool lo_float(const std::string &v)
     }
     return i == u.size();
 }
+namespace {
+bool number(const std::string &v) { if (v.empty()) return false; char *e; (void)strtod(v.c_str(), &e); return *e == 0; }
+int validate_kmer(const Args &a)
+{
+    const char *arg = "-k <K>";
+    if (!a.has("-k")) return 0;
+    const std::string v = a.get("-k");
+    if (!number(v) || v.find_first_not_of("0123456789") != std::string::npos) return clap_invalid(v, arg, ("`" + v + "` isn't a valid k-mer").c_str());
+    const int k = atoi(v.c_str());
+    return (k < 5 || k > 63 || k % 2 == 0) ? clap_invalid(v, arg, "K-mer must be an odd number between 5 and 63 (inclusive)") : 0;
+}
+}  // namespace
+int skh::validate_min_freq(const Args &a)
+{
+    const std::string v = a.has("--min-freq") ? a.get("--min-freq") : a.has("-m") ? a.get("-m") : "";
+    if (v.empty()) return 0;
+    if (!number(v)) return clap_invalid(v, "--min-freq <MIN_FREQ>", ("`" + v + "` isn't a valid frequency").c_str());
+    const double f = atof(v.c_str());
+    return (f < 0.0 || f > 1.0) ? clap_invalid(v, "--min-freq <MIN_FREQ>", "Frequency must be between 0 and 1 (inclusive)") : 0;
+}
+// `ska build`, and align / distance over several GPUs: sequence files or -f, and the build options
+int skh::validate_build_inputs(const char *cmd, const Args &a)
+{
+    if (a.pos.empty() && !a.has("-f")) return clap_missing(cmd, "<SEQ_FILES|-f <FILE_LIST>>");
+    if (!a.pos.empty() && a.has("-f")) return clap_conflict("build", "[SEQ_FILES]...", "-f");
+    BuildOpts bo;
+    if (int e = validate_kmer(a)) return e;
+    return parse_build_opts(a, bo);
+}
+namespace {
+// What clap refuses before lib.rs::main runs (cli.rs: required arguments, the argument groups of build / delete, value_parser and value_enum
+// of every option): the same refusals in clap's wording, before the banner and before a device is touched.  0: the command line stands.
 int validate_cli(const std::string &cmd, const Args &a, bool multi)
 {
-    auto number = [](const std::string &v) { if (v.empty()) return false; char *e; (void)strtod(v.c_str(), &e); return *e == 0; };
-    auto kmer = [&](const char *arg) -> int {
-        if (!a.has("-k")) return 0;
-        const std::string v = a.get("-k");
-        if (!number(v) || v.find_first_not_of("0123456789") != std::string::npos) return clap_invalid(v, arg, ("`" + v + "` isn't a valid k-mer").c_str());
-        const int k = atoi(v.c_str());
-        return (k < 5 || k > 63 || k % 2 == 0) ? clap_invalid(v, arg, "K-mer must be an odd number between 5 and 63 (inclusive)") : 0;
-    };
-    auto freq = [&]() -> int {
-        const std::string v = a.has("--min-freq") ? a.get("--min-freq") : a.has("-m") ? a.get("-m") : "";
-        if (v.empty()) return 0;
-        if (!number(v)) return clap_invalid(v, "--min-freq <MIN_FREQ>", ("`" + v + "` isn't a valid frequency").c_str());
-        const double f = atof(v.c_str());
-        return (f < 0.0 || f > 1.0) ? clap_invalid(v, "--min-freq <MIN_FREQ>", "Frequency must be between 0 and 1 (inclusive)") : 0;
-    };
+    auto freq = [&]() { return validate_min_freq(a); };
     auto filter = [&]() -> int {
         return a.has("--filter") && parse_filter(a.get("--filter")) < 0 ? clap_possible(a.get("--filter"), "--filter <FILTER>", "no-filter, no-const, no-ambig, no-ambig-or-const") : 0;
     };
@@ -1438,23 +995,17 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (v.find_first_not_of("0123456789") != std::string::npos || v.empty()) return clap_invalid(v, "--threads <THREADS>", ("`" + v + "` isn't a valid number of cores").c_str());
         if (atoi(v.c_str()) < 1) return clap_invalid(v, "--threads <THREADS>", "Threads must be one or higher");
     }
+    if (cmd == "distance") return validate_distance(a, multi);
     if (cmd == "align") {
         // the subsets are cut from one device's array: refused as clap refuses arguments that conflict, values that do not parse and a missing requirement
-        const auto conflict = [](const char *x, const char *y) {
-            fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", x, y, skh_usage_line("align"));
-            return 2;
-        };
-        for (auto &q : SUBSET_OPTS) if (a.has(q.flag) && (a.has("--gpus") || multi)) return conflict(q.arg, "--gpus <GPUS>");
-        for (const char *o : {"--samples", "--samples-file"}) if (a.has("--groups") && a.has(o)) return conflict("--groups <FILE>", o[9] ? "--samples-file <FILE>" : "--samples <NAMES>");
-        if (a.has("--samples") && a.has("--samples-file")) return conflict("--samples <NAMES>", "--samples-file <FILE>");
+        if (int e = conflicts("align", a, multi, {"--groups", "--min-group-size", "--samples", "--samples-file"}, {"--gpus"})) return e;
+        if (int e = conflicts("align", a, false, {"--groups"}, {"--samples", "--samples-file"})) return e;
+        if (int e = conflicts("align", a, false, {"--samples"}, {"--samples-file"})) return e;
         if (a.has("--min-group-size")) {
             if (!a.has("--groups")) return clap_missing("align", "--groups <FILE>");
-            const std::string v = a.get("--min-group-size");                                     // usize::from_str, then the range
-            if (v.empty()) return clap_invalid(v, "--min-group-size <N>", "cannot parse integer from empty string");
-            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--min-group-size <N>", "invalid digit found in string");
-            if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, "--min-group-size <N>", "must be one or higher");
+            if (int e = clap_uint(a.get("--min-group-size"), "--min-group-size <N>", 1, "must be one or higher")) return e;
         }
-        for (auto &q : SUBSET_OPTS) if (a.has(q.flag) && a.get(q.flag).empty()) return clap_invalid("", q.arg, "a value is required");
+        for (const char *o : {"--groups", "--min-group-size", "--samples", "--samples-file"}) if (a.has(o) && a.get(o).empty()) return clap_invalid("", clap_arg(o), "a value is required");
         if (a.has("--groups") && !a.has("-o")) return clap_missing("align", "-o <OUTPUT>");
         if (a.has("--samples") || a.has("--samples-file")) {
             std::vector<std::string> names;
@@ -1462,139 +1013,11 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
             if (names.empty()) return clap_invalid(a.get("--samples", a.get("--samples-file")), a.has("--samples") ? "--samples <NAMES>" : "--samples-file <FILE>", "no sample names given");
         }
     }
-    if (cmd == "distance" && (a.has("--sites") || a.has("--sites-max"))) {
-        // the sites are those of the selected lines of one device's filter-ambiguous table: refused as clap refuses arguments that conflict, a
-        // missing requirement and a value that does not parse
-        const std::pair<const char *, const char *> others[] = {{"--allow-ambiguous", "--allow-ambiguous"}, {"--no-table", "--no-table"}, {"--query", "--query <NAMES>"},
-                                                                {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}, {"--gpus", "--gpus <GPUS>"},
-                                                                {"--mst-clusters", "--mst-clusters <PREFIX>"}};      // (the ladder is cut from the prefiltered load's forest)
-        if (a.has("--sites"))
-            for (auto &o : others)
-                if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
-                    fprintf(stderr, "error: the argument '--sites <PREFIX>' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
-                    return 2;
-                }
-        if (!a.has("--sites")) return clap_missing("distance", "--sites <PREFIX>");
-        if (!has_select(a) && !a.has("--mst")) return clap_missing("distance", "<--max-snps <N>|--max-mismatches <P>|--closest <K>|--mst>");
-        if (a.get("--sites").empty()) return clap_invalid("", "--sites <PREFIX>", "a value is required");
-        if (a.has("--sites-max")) {                                                              // u64::from_str, then the range
-            const std::string v = a.get("--sites-max");
-            if (v.empty()) return clap_invalid(v, "--sites-max <N>", "cannot parse integer from empty string");
-            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--sites-max <N>", "invalid digit found in string");
-            errno = 0;
-            const unsigned long long m = strtoull(v.c_str(), nullptr, 10);
-            if (errno == ERANGE) return clap_invalid(v, "--sites-max <N>", "number too large to fit in target type");
-            if (m < 1) return clap_invalid(v, "--sites-max <N>", "must be one or higher");
-        }
-    }
-    if (cmd == "distance" && a.has("--no-table")) {
-        // the tree and the clusters from the banded sweep, on one device, and nothing else: refused as clap refuses arguments that conflict and
-        // a required group that is missing
-        const std::pair<const char *, const char *> others[] = {{"-o", "-o <OUTPUT>"}, {"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"},
-                                                                {"--closest", "--closest <K>"}, {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"},
-                                                                {"--query-skf", "--query-skf <FILE>"}, {"--gpus", "--gpus <GPUS>"}};
-        for (auto &o : others)
-            if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
-                fprintf(stderr, "error: the argument '--no-table' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
-                return 2;
-            }
-        if (a.has("--mst")) {
-            fprintf(stderr, "error: the argument '--mst' cannot be used with '--no-table'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
-            return 2;
-        }
-        if (!a.has("--tree") && !a.has("--clusters")) return clap_missing("distance", "<--tree <FILE>|--clusters <PREFIX>>");
-    }
-    if (cmd == "distance" && has_select(a)) {
-        // the selection runs on one device and never forms the table the tree, the clusters and the query cut are taken from: refused as clap
-        // refuses arguments that conflict, the earliest selection option named first
-        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--gpus", "--gpus <GPUS>"},
-                                                                {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
-        for (auto &q : SELECT_OPTS)
-            for (auto &o : others)
-                if (a.has(q.flag) && (a.has(o.first) || (multi && !strcmp(o.first, "--gpus")))) {
-                    fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", q.arg, o.second, skh_usage_line("distance"));
-                    return 2;
-                }
-        if (a.has("--closest") && a.has("--mst")) {                                              // (the forest takes the two thresholds only)
-            fprintf(stderr, "error: the argument '--closest <K>' cannot be used with '--mst'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
-            return 2;
-        }
-        for (auto &q : SELECT_OPTS) {
-            if (!a.has(q.flag)) continue;
-            const std::string v = a.get(q.flag);
-            if (!strcmp(q.flag, "--closest")) {                                                  // usize::from_str, then the range
-                if (v.empty()) return clap_invalid(v, q.arg, "cannot parse integer from empty string");
-                if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, q.arg, "invalid digit found in string");
-                if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, q.arg, "must be one or higher");
-                continue;
-            }
-            if (!lo_float(v)) return clap_invalid(v, q.arg, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
-            const double t = strtod(v.c_str(), nullptr);
-            if (!strcmp(q.flag, "--max-snps")) { if (!(t >= 0.0)) return clap_invalid(v, q.arg, "must be zero or more"); }
-            else if (!(t >= 0.0 && t <= 1.0)) return clap_invalid(v, q.arg, "Proportion must be between 0 and 1 (inclusive)");
-        }
-    }
-    if (cmd == "distance" && (a.has("--mst") || a.has("--mst-clusters") || a.has("--levels"))) {
-        // the forest comes from one device's banded sweep, which forms neither the table nor what is cut from it: refused as clap refuses
-        // arguments that conflict (--mst is named when no other selection option is: those were refused above), a missing requirement, a bad value
-        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"},
-                                                                {"--cluster-mismatches", "--cluster-mismatches <P>"}, {"--gpus", "--gpus <GPUS>"}, {"--query", "--query <NAMES>"},
-                                                                {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"}};
-        if (a.has("--mst"))
-            for (auto &o : others)
-                if (a.has(o.first) || (multi && !strcmp(o.first, "--gpus"))) {
-                    fprintf(stderr, "error: the argument '--mst' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", o.second, skh_usage_line("distance"));
-                    return 2;
-                }
-        if (!a.has("--mst")) return clap_missing("distance", a.has("--levels") && !a.has("--mst-clusters") ? "--mst\n  --mst-clusters <PREFIX>" : "--mst");
-        if (a.has("--levels") && !a.has("--mst-clusters")) return clap_missing("distance", "--mst-clusters <PREFIX>");
-        if (a.has("--mst-clusters") && a.get("--mst-clusters").empty()) return clap_invalid("", "--mst-clusters <PREFIX>", "a value is required");
-        std::vector<double> lv;
-        if (a.has("--levels")) if (const char *why = parse_levels(a.get("--levels"), lv)) return clap_invalid(a.get("--levels"), MST_LEVELS_ARG, why);
-    }
-    if (cmd == "distance" && has_query(a)) {
-        // the query is cut from one device's table, and the tree and the clusters need all of it: refused as clap refuses arguments that conflict
-        const std::pair<const char *, const char *> others[] = {{"--tree", "--tree <FILE>"}, {"--clusters", "--clusters <PREFIX>"}, {"--cluster-snps", "--cluster-snps <N>"},
-                                                                {"--cluster-mismatches", "--cluster-mismatches <P>"}, {"--gpus", "--gpus <GPUS>"}};
-        for (auto &q : QUERY_OPTS)
-            for (auto &o : others)
-                if (a.has(q.flag) && (a.has(o.first) || (multi && !strcmp(o.first, "--gpus")))) {
-                    fprintf(stderr, "error: the argument '%s' cannot be used with '%s'\n\nUsage: %s\n\nFor more information, try '--help'.\n", q.arg, o.second, skh_usage_line("distance"));
-                    return 2;
-                }
-        for (auto &q : QUERY_OPTS) if (a.has(q.flag) && a.get(q.flag).empty()) return clap_invalid("", q.arg, "a value is required");
-        std::vector<std::string> names;
-        if (int e = read_query_names(a, names)) return e;
-        if (names.empty() && !a.has("--query-skf")) return clap_invalid(a.get("--query", a.get("--query-file")), a.has("--query") ? "--query <NAMES>" : "--query-file <FILE>", "no sample names given");
-    }
-    const bool files_from_build = multi && (cmd == "align" || cmd == "distance");        // (--gpus N: sequence files or -f, and the build options)
-    if (cmd == "build" || files_from_build) {
-        if (cmd == "build" && !a.has("-o")) return clap_missing("build", "-o <OUTPUT>");
-        if (a.pos.empty() && !a.has("-f")) return clap_missing(cmd.c_str(), "<SEQ_FILES|-f <FILE_LIST>>");
-        if (!a.pos.empty() && a.has("-f")) { fprintf(stderr, "error: the argument '[SEQ_FILES]...' cannot be used with '-f <FILE_LIST>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("build")); return 2; }
-        BuildOpts bo;
-        if (int e = kmer("-k <K>")) return e;
-        if (int e = parse_build_opts(a, bo)) return e;
-    }
+    if (cmd == "build" && !a.has("-o")) return clap_missing("build", "-o <OUTPUT>");
+    if (cmd == "build" || (multi && cmd == "align")) if (int e = validate_build_inputs(cmd.c_str(), a)) return e;      // (--gpus N: sequence files or -f, and the build options)
     if (cmd == "align") { if (!multi && a.pos.empty()) return clap_missing("align", "<INPUT>..."); if (int e = filter()) return e; if (int e = freq()) return e; }
-    else if (cmd == "distance") { if (!multi && a.pos.size() != 1) return a.pos.empty() ? clap_missing("distance", "<SKF_FILE>") : fail("one .skf file required"); if (int e = freq()) return e;
-        // the engine's own options (the reference's scripts/cluster_dists.py: --snps, --mismatches), refused the way clap refuses the others
-        for (auto names : {std::make_pair("--cluster-snps", "--cluster-snps <N>"), std::make_pair("--cluster-mismatches", "--cluster-mismatches <P>")}) {
-            if (!a.has(names.first)) continue;
-            const std::string v = a.get(names.first);
-            if (!a.has("--clusters")) {
-                fprintf(stderr, "error: the following required arguments were not provided:\n  --clusters <PREFIX>\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("distance"));
-                return 2;
-            }
-            if (!lo_float(v)) return clap_invalid(v, names.second, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
-            const double t = strtod(v.c_str(), nullptr);
-            if (!(t >= 0.0)) return clap_invalid(v, names.second, "Threshold must be zero or higher");
-        }
-        for (const char *o : {"--tree", "--clusters"})
-            if (a.has(o) && a.get(o).empty()) return clap_invalid("", o[2] == 't' ? "--tree <FILE>" : "--clusters <PREFIX>", "a value is required");
-    }
     else if (cmd == "nk") { if (a.pos.empty()) return clap_missing("nk", "<SKF_FILE>"); }
-    else if (cmd == "cov") { if (a.pos.size() < 2) return clap_missing("cov", a.pos.empty() ? "<FASTQ_FWD>\n  <FASTQ_REV>" : "<FASTQ_REV>"); if (int e = kmer("-k <K>")) return e; }
+    else if (cmd == "cov") { if (a.pos.size() < 2) return clap_missing("cov", a.pos.empty() ? "<FASTQ_FWD>\n  <FASTQ_REV>" : "<FASTQ_REV>"); if (int e = validate_kmer(a)) return e; }
     else if (cmd == "map") {
         if (a.pos.empty()) return clap_missing("map", "<REFERENCE>");
         const std::string fmt = a.get("--format", a.has("-f") ? a.get("-f") : "aln");
@@ -1604,7 +1027,7 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
     else if (cmd == "delete") {
         if (!a.has("-s") && !a.has("--skf-file")) return clap_missing("delete", "--skf-file <SKF_FILE>");
         if (a.pos.empty() && !a.has("-f")) return clap_missing("delete", "<-f <FILE_LIST>|NAMES>");
-        if (!a.pos.empty() && a.has("-f")) { fprintf(stderr, "error: the argument '[NAMES]...' cannot be used with '-f <FILE_LIST>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("delete")); return 2; }
+        if (!a.pos.empty() && a.has("-f")) return clap_conflict("delete", "[NAMES]...", "-f");
     }
     else if (cmd == "weed") { if (a.pos.empty()) return clap_missing("weed", "<SKF_FILE>"); if (int e = filter()) return e; if (int e = freq()) return e; }
     else if (cmd == "markers") {
@@ -1613,21 +1036,10 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (a.pos.size() > 1) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[1].c_str(), skh_usage_line("markers")); return 2; }
         if (!a.has("--groups")) return clap_missing("markers", "--groups <FILE>");
         if (!a.has("-o")) return clap_missing("markers", "-o <OUTPUT>");
-        if (a.has("--gpus") || multi) { fprintf(stderr, "error: the argument '--gpus <GPUS>' cannot be used with '--groups <FILE>'\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("markers")); return 2; }
+        if (a.has("--gpus") || multi) return clap_conflict("markers", "--gpus", "--groups");
         for (auto o : {std::make_pair("--groups", "--groups <FILE>"), std::make_pair("-o", "-o <OUTPUT>")}) if (a.get(o.first).empty()) return clap_invalid("", o.second, "a value is required");
-        for (auto o : {std::make_pair("--min-in", "--min-in <P>"), std::make_pair("--max-out", "--max-out <Q>")}) {
-            if (!a.has(o.first)) continue;
-            const std::string v = a.get(o.first);
-            if (!lo_float(v)) return clap_invalid(v, o.second, v.empty() ? "cannot parse float from empty string" : "invalid float literal");
-            const double f = strtod(v.c_str(), nullptr);
-            if (!(f >= 0.0 && f <= 1.0)) return clap_invalid(v, o.second, "Proportion must be between 0 and 1 (inclusive)");
-        }
-        if (a.has("--min-group-size")) {
-            const std::string v = a.get("--min-group-size");                                     // usize::from_str, then the range
-            if (v.empty()) return clap_invalid(v, "--min-group-size <N>", "cannot parse integer from empty string");
-            if (v.find_first_not_of("0123456789", v[0] == '+' && v.size() > 1 ? 1 : 0) != std::string::npos) return clap_invalid(v, "--min-group-size <N>", "invalid digit found in string");
-            if (strtoull(v.c_str(), nullptr, 10) < 1) return clap_invalid(v, "--min-group-size <N>", "must be one or higher");
-        }
+        for (const char *o : {"--min-in", "--max-out"}) if (a.has(o)) if (int e = clap_float(a.get(o), clap_arg(o), 0.0, 1.0, "Proportion must be between 0 and 1 (inclusive)")) return e;
+        if (a.has("--min-group-size")) if (int e = clap_uint(a.get("--min-group-size"), "--min-group-size <N>", 1, "must be one or higher")) return e;
         if (a.has("--kind")) { const std::string v = a.get("--kind"); if (v != "presence" && v != "allele" && v != "both") return clap_possible(v, "--kind <KIND>", "presence, allele, both"); }
     }
     else if (cmd == "lo") {                                                                                       // cli.rs:395-425
@@ -1740,17 +1152,11 @@ extern "C" int skh_main(int argc, char **argv)
     else if (cmd == "selftest") rcode = selftest(ctx, 0, 1);
     else if (multi) rcode = main_sharded(ctx, cmd, a, rank, world, threads);
     else if (cmd == "build") {
-        if (!a.has("-o")) return fail("-o <output> is required");
-        if (a.pos.empty() == !a.has("-f")) return fail("give either sequence files or -f <file_list>");
         BuildOpts bo; Inputs in;
         if (int e = parse_build_opts(a, bo)) return e;
         if (int e = read_inputs(a, in)) return e;
-        const int k = bo.k; skx_qual &q = bo.q; const bool auto_count = bo.auto_count; const double prop = bo.prop;
-        std::vector<std::string> &names = in.names, &f1 = in.f1, &f2 = in.f2;
-        std::vector<const char *> &cn = in.cn, &c1 = in.c1, &c2 = in.c2;
-        (void)names; (void)f1; (void)f2;
-        if (auto_count && auto_min_count(ctx, in, k, !a.has("--single-strand"), q, true)) { skx_ctx_destroy(ctx); return engine_fail(); }
-        if (skx_build_and_merge(ctx, cn.data(), c1.data(), c2.data(), (int)cn.size(), k, !a.has("--single-strand"), &q, threads, prop, &arr) != SKX_OK ||
+        if (bo.auto_count && auto_min_count(ctx, in, bo.k, !a.has("--single-strand"), bo.q, true)) { skx_ctx_destroy(ctx); return engine_fail(); }
+        if (skx_build_and_merge(ctx, in.cn.data(), in.c1.data(), in.c2.data(), (int)in.cn.size(), bo.k, !a.has("--single-strand"), &bo.q, threads, bo.prop, &arr) != SKX_OK ||
             skh_save_skf(arr, a.get("-o").c_str()) != SKX_OK)
             rcode = engine_fail();
     } else if (cmd == "align") {
@@ -1781,56 +1187,8 @@ extern "C" int skh_main(int argc, char **argv)
             rcode = engine_fail();
         if (fd != 1) close(fd);
         }
-    } else if (cmd == "distance") {
-        if (a.pos.size() != 1) return fail("one .skf file required");
-        const char *in[1] = {a.pos[0].c_str()};
-        const double mf = atof(a.get("--min-freq", a.get("-m", "0")).c_str());
-        char *buf = nullptr; uint64_t len = 0;
-        (void)in;
-        const DistExtras dx(a);
-        if (has_query(a)) {
-            std::vector<std::string> names; std::vector<const char *> cn;
-            if (int e = read_query_names(a, names)) return e;
-            for (auto &n : names) cn.push_back(n.c_str());
-            const std::string qskf = a.get("--query-skf");
-            if (skh_distance_query_tsv(ctx, a.pos[0].c_str(), a.has("--query-skf") ? qskf.c_str() : nullptr, cn.data(), (int)cn.size(), mf, !a.has("--allow-ambiguous"), &buf, &len) != SKX_OK)
-                rcode = engine_fail();
-            else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
-        }
-        else if (a.has("--no-table")) {
-            if (skh_distance_banded_files(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get()) != SKX_OK) rcode = engine_fail();
-        }
-        else if (a.has("--sites")) {                                                              // (validate_cli: one of the selecting options is there)
-            const skx_select_spec sp = select_spec(a);
-            const skx_mst_spec ms{sp.max_snps, sp.max_mismatches, 0};
-            const unsigned long long cap = a.has("--sites-max") ? strtoull(a.get("--sites-max").c_str(), nullptr, 10) : 1ull << 27;
-            const int r = skh_distance_sites(ctx, a.pos[0].c_str(), mf, a.has("--mst") ? nullptr : &sp, a.has("--mst") ? &ms : nullptr, a.get("--sites").c_str(), cap, &buf, &len);
-            if (buf) { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }                    // the table's lines stand even when the sites are refused
-            if (r != SKX_OK) rcode = engine_fail();
-        }
-        else if (a.has("--mst")) {
-            const skx_select_spec ss = select_spec(a);
-            const skx_mst_spec sp{ss.max_snps, ss.max_mismatches, 0};
-            std::vector<double> lv;
-            if (a.has("--mst-clusters")) (void)parse_levels(a.get("--levels", MST_DEFAULT_LEVELS), lv);      // (validate_cli took the list)
-            char *csv = nullptr; uint64_t csv_len = 0;
-            const int r = skx_guarded([&]() -> int { return distance_mst_run(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), &sp, lv.data(), (int)lv.size(), &buf, &len, &csv, &csv_len); });
-            if (r != SKX_OK) rcode = engine_fail();
-            else {
-                rcode = emit(a.get("-o"), buf, len); skx_free(buf);
-                if (csv && !rcode && write_text_file(a.get("--mst-clusters") + ".levels.csv", csv, csv_len) != SKX_OK) rcode = engine_fail();
-                skx_free(csv);
-            }
-        }
-        else if (has_select(a)) {
-            const skx_select_spec sp = select_spec(a);
-            if (skh_distance_select_tsv(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), &sp, &buf, &len) != SKX_OK) rcode = engine_fail();
-            else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
-        }
-        else if (skh_distance_skf_tsv_extras(ctx, a.pos[0].c_str(), mf, !a.has("--allow-ambiguous"), dx.get(), &buf, &len) != SKX_OK)
-            rcode = engine_fail();
-        else { rcode = emit(a.get("-o"), buf, len); skx_free(buf); }
-    } else if (cmd == "nk") {
+    } else if (cmd == "distance") rcode = run_distance(ctx, a);
+    else if (cmd == "nk") {
         if (a.pos.size() != 1) return fail("one .skf file required");
         const char *in[1] = {a.pos[0].c_str()};
         char *buf = nullptr; uint64_t len = 0;

@@ -1,10 +1,8 @@
 // ska_markers.cpp -- `ska markers`: the split k-mers and middle-base alleles that tell each group of a groups file from everybody else, from one
 // load and one call of skx_array_group_markers (host side above the C ABI).  The reference has no such mode: its users run `ska delete` of a
 // group's samples (generic_modes.rs:192-210) and `ska nk --full-info` (lib.rs:808-827) per group and compare the text.
-#include "../../include/skx_host.h"
+#include "ska_host_util.h"
 #include <algorithm>
-#include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,28 +10,8 @@
 #include <string>
 #include <vector>
 
+using namespace skh;
 namespace {
-
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-void set_error(const char *fmt, ...)
-{
-    char tmp[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(tmp, sizeof tmp, fmt, ap); va_end(ap);
-    skx_set_last_error(tmp);
-}
-template <typename F>
-int guarded(F &&f) noexcept
-{
-    try { return f(); }
-    catch (const std::bad_alloc &) { skx_set_last_error("out of host memory"); return SKX_ENOMEM; }
-    catch (...) { skx_set_last_error("internal error"); return SKX_EINVAL; }
-}
-struct Phase {       // wall-clock phase recorded through the ABI (skx_phase_add)
-    const char *name; std::chrono::steady_clock::time_point t0;
-    explicit Phase(const char *n) : name(n), t0(std::chrono::steady_clock::now()) {}
-    void stop() { if (name) { skx_phase_add(name, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); name = nullptr; } }
-    ~Phase() { stop(); }
-};
 
 int write_file(const std::string &path, const std::string &text)
 {

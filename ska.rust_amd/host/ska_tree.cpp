@@ -2,9 +2,8 @@
 // skx_dist_nj (negative-length rule, midpoint root, fixed child order) and the single-linkage clusters of the distance table (a union-find
 // over a table the CLI already holds is cheaper than formatting that table, so there is no kernel here).  The reference leaves both to
 // scripts/cluster_dists.py (networkx + rapidnj + biopython); its thresholds, CSV header and rooting are kept, the orders are fixed here.
-#include "../../include/skx_host.h"
+#include "ska_host_util.h"
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,22 +11,8 @@
 #include <string>
 #include <vector>
 
+using namespace skh;
 namespace {
-void skx_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-void skx_set_error(const char *fmt, ...)
-{
-    char tmp[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(tmp, sizeof tmp, fmt, ap); va_end(ap);
-    skx_set_last_error(tmp);
-}
-int text_out(const std::string &s, char **buf, uint64_t *len)
-{
-    char *p = (char *)malloc(s.size() + 1);
-    if (!p) return SKX_ENOMEM;
-    memcpy(p, s.data(), s.size()); p[s.size()] = 0;
-    *buf = p; *len = s.size();
-    return SKX_OK;
-}
 std::string newick_name(const char *name)
 {
     const std::string s = name;
@@ -41,14 +26,14 @@ struct Edge { uint32_t to; double len; };
 
 extern "C" int skh_nj_newick(const char *const *names, const skx_nj_join *joins, int n_, char **buf, uint64_t *len)
 {
-    if (!names || !joins || !buf || !len || n_ < 2) { skx_set_error("skh_nj_newick: bad arguments (at least 2 leaves)"); return SKX_EINVAL; }
+    if (!names || !joins || !buf || !len || n_ < 2) { set_error("skh_nj_newick: bad arguments (at least 2 leaves)"); return SKX_EINVAL; }
     const uint32_t n = (uint32_t)n_, N = 2 * n - 2;                // nodes of the unrooted tree: n leaves, n - 2 inner
     std::vector<std::vector<Edge>> adj(N + 1);                     // (+ 1: the root, placed below)
     auto link = [&](uint32_t x, uint32_t y, double l) { adj[x].push_back({y, l}); adj[y].push_back({x, l}); };
     for (uint32_t t = 0; t + 1 < n; t++) {
         const skx_nj_join &j = joins[t];
         const uint32_t u = n + t;
-        if (j.a >= u || j.b >= u || j.a == j.b) { skx_set_error("skh_nj_newick: join %u names a node that does not exist yet", t); return SKX_EINVAL; }
+        if (j.a >= u || j.b >= u || j.a == j.b) { set_error("skh_nj_newick: join %u names a node that does not exist yet", t); return SKX_EINVAL; }
         // Kuhner-Felsenstein: a negative branch becomes 0 and its sibling takes the difference
         double la = j.len_a, lb = j.len_b;
         if (la < 0) { lb += la; la = 0; }
@@ -122,15 +107,15 @@ extern "C" int skh_nj_newick(const char *const *names, const skx_nj_join *joins,
         fs.push_back({c, 0});
     }
     o += ";\n";
-    return text_out(o, buf, len);
+    return to_buf(o, buf, len);
 }
 
 extern "C" int skh_clusters_csv(const char *const *names, const uint32_t *labels, int n_, char **csv, uint64_t *csv_len)
 {
-    if (!names || !labels || n_ < 1 || !csv || !csv_len) { skx_set_error("skh_clusters_csv: bad arguments"); return SKX_EINVAL; }
+    if (!names || !labels || n_ < 1 || !csv || !csv_len) { set_error("skh_clusters_csv: bad arguments"); return SKX_EINVAL; }
     const uint32_t n = (uint32_t)n_;
     for (uint32_t i = 0; i < n; i++)
-        if (labels[i] > i || labels[labels[i]] != labels[i]) { skx_set_error("skh_clusters_csv: label %u of sample %u is not the lowest sample of a cluster", labels[i], i); return SKX_EINVAL; }
+        if (labels[i] > i || labels[labels[i]] != labels[i]) { set_error("skh_clusters_csv: label %u of sample %u is not the lowest sample of a cluster", labels[i], i); return SKX_EINVAL; }
     // clusters by size descending, ties by their lowest sample
     std::vector<uint32_t> size(n, 0), roots;
     for (uint32_t i = 0; i < n; i++) size[labels[i]]++;
@@ -146,15 +131,15 @@ extern "C" int skh_clusters_csv(const char *const *names, const uint32_t *labels
             else c += s;
             c += "," + std::to_string(k + 1) + "\n";
         }
-    return text_out(c, csv, csv_len);
+    return to_buf(c, csv, csv_len);
 }
 
 extern "C" int skh_mst_levels_csv(const char *const *names, const skx_dist_pair *pairs, uint64_t n_pairs, int n_, const double *levels, int n_levels, char **buf, uint64_t *len)
 {
-    if (!names || (!pairs && n_pairs) || n_ < 1 || !levels || n_levels < 1 || !buf || !len) { skx_set_error("skh_mst_levels_csv: bad arguments"); return SKX_EINVAL; }
+    if (!names || (!pairs && n_pairs) || n_ < 1 || !levels || n_levels < 1 || !buf || !len) { set_error("skh_mst_levels_csv: bad arguments"); return SKX_EINVAL; }
     const uint32_t n = (uint32_t)n_;
     for (uint64_t p = 0; p < n_pairs; p++)
-        if (pairs[p].i >= pairs[p].j || pairs[p].j >= n) { skx_set_error("skh_mst_levels_csv: line %llu does not join two of the %u samples", (unsigned long long)p, n); return SKX_EINVAL; }
+        if (pairs[p].i >= pairs[p].j || pairs[p].j >= n) { set_error("skh_mst_levels_csv: line %llu does not join two of the %u samples", (unsigned long long)p, n); return SKX_EINVAL; }
     // the values the table shows, as skh_distance_clusters reads them
     std::vector<double> printed(n_pairs);
     char tmp[512];
@@ -183,13 +168,13 @@ extern "C" int skh_mst_levels_csv(const char *const *names, const skx_dist_pair 
         for (int l = 0; l < n_levels; l++) { const std::string v = std::to_string(column[l][i]); c += "," + v; address += (l ? "." : "") + v; }
         c += "," + address + "\n";
     }
-    return text_out(c, buf, len);
+    return to_buf(c, buf, len);
 }
 
 extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d, int n_, double max_snps, double max_mismatches,
                                      char **csv, uint64_t *csv_len, char **dot, uint64_t *dot_len)
 {
-    if (!names || (!d && n_ > 1) || n_ < 1 || (csv && !csv_len) || (dot && !dot_len)) { skx_set_error("skh_distance_clusters: bad arguments"); return SKX_EINVAL; }
+    if (!names || (!d && n_ > 1) || n_ < 1 || (csv && !csv_len) || (dot && !dot_len)) { set_error("skh_distance_clusters: bad arguments"); return SKX_EINVAL; }
     const uint32_t n = (uint32_t)n_;
     std::vector<uint32_t> up(n);
     std::iota(up.begin(), up.end(), 0u);
@@ -213,6 +198,6 @@ extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d
     for (uint32_t i = 0; i < n; i++) up[i] = find(i);
     int r = SKX_OK;
     if (csv) r = skh_clusters_csv(names, up.data(), n_, csv, csv_len);
-    if (r == SKX_OK && dot) r = text_out(g, dot, dot_len);
+    if (r == SKX_OK && dot) r = to_buf(g, dot, dot_len);
     return r;
 }

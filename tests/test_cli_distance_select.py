@@ -82,6 +82,14 @@ def test_bad_values(tmp_path, flag, arg, value, why):
     _refused(r, f"error: invalid value '{value}' for '{arg}': {why}" + HINT)
 
 
+@pytest.mark.parametrize("flag, arg, why", [("--max-snps", "--max-snps <N>", "cannot parse float from empty string"),
+                                            ("--max-mismatches", "--max-mismatches <P>", "cannot parse float from empty string"),
+                                            ("--closest", "--closest <K>", "cannot parse integer from empty string")])
+def test_empty_values(tmp_path, flag, arg, why):
+    r = _ska("distance", "x.skf", flag, "", cwd=str(tmp_path), ok=False)
+    _refused(r, f"error: invalid value '' for '{arg}': {why}" + HINT)
+
+
 def test_other_subcommands_refuse_the_options(tmp_path):
     r = _ska("align", "x.skf", "--closest", "1", cwd=str(tmp_path), ok=False)
     assert (r.returncode, r.stdout, r.stderr.decode()) == (2, b"", "error: unexpected argument '--closest' found\n\nUsage: ska align [OPTIONS]" + HINT)

@@ -136,6 +136,17 @@ def test_refusals_in_claps_wording(tmp_path):
         assert (r.returncode, r.stdout, r.stderr.decode()) == (2, b"", want), (args, r.stderr)
 
 
+def test_empty_thresholds_and_a_file_that_is_not_there(tmp_path):
+    wd = str(tmp_path)
+    for flag, arg in (("--cluster-snps", "--cluster-snps <N>"), ("--cluster-mismatches", "--cluster-mismatches <P>")):
+        r = _ska("distance", "x.skf", "--clusters", "p", flag, "", cwd=wd, ok=False)
+        assert (r.returncode, r.stdout, r.stderr.decode()) == (2, b"", f"error: invalid value '' for '{arg}': cannot parse float from empty string\n\nFor more information, try '--help'.\n")
+    # what stands goes on to the banner and ends as a Rust panic would, at the missing device or the missing file, and writes nothing
+    r = _ska("distance", "x.skf", "--tree", "t.nwk", "--clusters", "p", cwd=wd, ok=False)
+    assert r.returncode == 101 and r.stdout == b"" and r.stderr.decode().startswith("SKA: Split K-mer Analysis") and os.listdir(wd) == []
+    assert r.stderr.decode().splitlines()[-1].startswith("error: ")
+
+
 def test_help_lists_the_new_options():
     out = _ska("distance", "--help", cwd=ROOT).stdout.decode()
     for f in ("--tree <FILE>", "--clusters <PREFIX>", "--cluster-snps <N>", "--cluster-mismatches <P>", "[default: 10]", "[default: 1.0]"):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from conftest import set_knob
 
+import sites_model as SM
 from select_model import select
 
 pytestmark = pytest.mark.gpu
@@ -218,6 +219,36 @@ def test_select_tsv_of_a_file(case, filt, tmp_path):
             lines = [FMT % (names[i], names[j], t["distance"][n], t["mismatch_prop"][n], t["match_count"][n], t["mismatch_count"][n])
                      for i, j in sorted(select(r["D"], r["M"], **crit)) for n in [_pair_index(S, i, j)]]
             assert arr.ctx.distance_select_tsv(path, mf, filt, **crit).decode() == "\n".join([HEADER] + lines) + "\n", (mf, crit)
+
+
+def test_texts_long_enough_for_a_second_formatting_thread(case, tmp_path):
+    """the host's writers hand rows (the whole table: a second thread from 32 samples) or slices of 4 096 lines (the selected lines, the sites:
+    a second thread from 8 192) to threads.  With every pair selected the S = 130 table has 8 385 lines, and its sites file is cut where it
+    passes 8 192 records: the three texts are the model's, whichever thread wrote a line"""
+    import ora
+    arr, S, names, r = case["arr"], case["S"], case["names"], case["ref"][(0.0, True)]
+    path = str(tmp_path / "s.skf")
+    arr.save(path)
+    t = r["table"]
+    lines = [FMT % (names[i], names[j], t["distance"][n], t["mismatch_prop"][n], t["match_count"][n], t["mismatch_count"][n])
+             for n, (i, j) in enumerate(SM.all_pairs(S))]
+    whole = "\n".join([HEADER] + lines) + "\n"
+    assert (len(lines) >= 8192) == (S == 130) and S >= 32
+    assert arr.ctx.distance_skf_tsv(path, 0.0, True).decode() == whole
+    assert arr.ctx.distance_select_tsv(path, 0.0, True, max_snps=r["above"][0]).decode() == whole
+    # the sites of the nearest pairs, up to the distance at which the records (a line's Distance is its number of sites) pass 8 192
+    d = np.sort(t["distance"])
+    cut = float(d[min(int(np.searchsorted(np.cumsum(d), 8192)), len(d) - 1)])
+    pairs = [p for n, p in enumerate(SM.all_pairs(S)) if t["distance"][n] <= cut]
+    table = arr.ctx.distance_sites(path, str(tmp_path / "p"), 0.0, max_snps=cut).decode()
+    assert table == "\n".join([HEADER] + [lines[_pair_index(S, i, j)] for i, j in pairs]) + "\n"
+    oa = ora.Array.load(path)
+    keys, var, counts = oa.export()
+    assert oa.names == names
+    recs = SM.sites(var, SM.sweep_flags(var, 0.0, counts), pairs)
+    print(f"S={S} k={case['k']}: {len(lines)} lines; --max-snps {cut:g}: {len(pairs)} lines, {len(recs)} records")
+    assert len(recs) >= 8192
+    assert open(str(tmp_path / "p.sites.tsv")).read() == SM.sites_text(names, keys, case["k"], pairs, recs)
 
 
 @pytest.mark.parametrize("filt", [True, False], ids=["filter-ambiguous", "allow-ambiguous"])
