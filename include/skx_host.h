@@ -107,6 +107,29 @@ int skh_mst_levels_csv(const char *const *names, const skx_dist_pair *pairs, uin
  * along the path between them, on the first edge that reaches the half.  Children ordered by the lowest leaf id below them, lengths
  * %.5f, ";" and a newline at the end; a name holding any of ()[]':;, or white space in single quotes with inner quotes doubled. */
 int skh_nj_newick(const char *const *names, const skx_nj_join *joins, int n, char **buf, uint64_t *len);
+/* ---- a user's tree as joins (host only; no device is touched).  The reading half of a per-branch parsimony count on a tree; the device half
+ * is not in the engine yet. ----
+ * A rooted binary tree over n samples as n - 1 joins in the node numbering of skx_nj_join: nodes 0 .. n-1 are the samples, join t makes node
+ * n + t from children (a, b), both < n + t; every node below the root 2n-2 is a child exactly once. */
+typedef struct { uint32_t a, b; } skx_tree_join;
+/* Newick text as such joins: the inverse of skh_nj_newick's spelling, and what IQ-TREE and rapidnj write.
+ * names[n] are the samples, n >= 2; a leaf's label is matched to them exactly (the first of two equal names wins).  Inner nodes are numbered as
+ * their ')' come, so join t is the t-th ')' of the text, children in the order of the text; joins receives n - 1 records.  Read: labels in single
+ * quotes with '' for a quote inside, [comments], white space, branch lengths and inner labels (both read and dropped).  A root with three
+ * children (a, b, c) becomes R = (a, Y), Y = (b, c) -- Y is node 2n-3 -- and *root_three (may be NULL) is set.  The nesting is kept on an
+ * explicit stack: a caterpillar tree is as deep as it has leaves.  SKX_EINVAL with a message that begins "newick:" and names the position in the
+ * text (a byte offset from 0) or the sample for: any other node with more than two children, a node with one child, a leaf that is not a sample,
+ * a sample named twice or missing from the tree, text after the ';', a text that ends early, a comment or a quoted label without its end. */
+int skh_newick_joins(const char *text, const char *const *names, int n, skx_tree_join *joins, int *root_three);
+/* the tree of such joins as one line of Newick: topology, child order and root as the text skh_newick_joins read had them (root_three: its
+ * root's three children again, the branch above the first with length[a] + length[Y]), length[2n-2] = an integer per node below the root (a count
+ * of changes on the branch above it) as branch lengths, leaves spelled as skh_nj_newick spells them, inner nodes labelled n1, n2, ... in the
+ * order of their ')' (n<t+1> is node n+t; the root has no label), ";" and a newline at the end. */
+int skh_parsimony_newick(const char *const *names, const skx_tree_join *joins, int n, int root_three, const uint64_t *branch_changes, char **buf, uint64_t *len);
+/* the same tree as a table: header "Node\tParent\tLeaves\tLowest leaf\tChanges", one line per node below the root in node order -- the samples,
+ * then n1, n2, ... -- with its parent's label ("root" for the root), the leaves below it, the name of the lowest sample below it and the number
+ * given for the branch above it.  The Y of a trifurcating root has no line: its children hang under "root", its number is added to the first child's. */
+int skh_parsimony_branches(const char *const *names, const skx_tree_join *joins, int n, int root_three, const uint64_t *branch_changes, char **buf, uint64_t *len);
 /* single-linkage clusters of a distance table (host only; names[n], d = the n(n-1)/2 pairs of skx_array_distance).  A pair is an edge when
  * its values as the TSV prints them (%.2f, %.5f, parsed back) satisfy snps <= max_snps && mismatches <= max_mismatches.  csv: header
  * "id,Cluster__autocolour", clusters numbered from 1 by size descending (ties: lowest sample index), rows by cluster then sample index,

@@ -201,3 +201,205 @@ extern "C" int skh_distance_clusters(const char *const *names, const skx_dist *d
     if (r == SKX_OK && dot) r = to_buf(g, dot, dot_len);
     return r;
 }
+
+// ---- a user's tree: Newick in (skh_newick_joins), and the tree out again with a count per branch as branch lengths
+namespace {
+// what the two writers need of a join table: parents, the hidden node Y of a trifurcating root, leaves below, lowest leaf
+struct JoinTree {
+    uint32_t S, root, hidden;                                      // hidden: 2S-3 when the text's root had three children, else no node
+    const skx_tree_join *j;
+    std::vector<uint32_t> parent, leaves, low;
+    std::vector<uint64_t> len;                                     // the changes a branch is reported with
+    JoinTree(const skx_tree_join *joins, uint32_t n, bool three, const uint64_t *changes)
+        : S(n), root(2 * n - 2), hidden(three ? 2 * n - 3 : 0xFFFFFFFFu), j(joins), parent(2 * n - 1, 2 * n - 2), leaves(2 * n - 1, 1), low(2 * n - 1), len(2 * n - 2, 0)
+    {
+        for (uint32_t v = 0; v < S; v++) low[v] = v;
+        for (uint32_t t = 0; t + 1 < S; t++) {
+            parent[j[t].a] = parent[j[t].b] = S + t;
+            leaves[S + t] = leaves[j[t].a] + leaves[j[t].b]; low[S + t] = std::min(low[j[t].a], low[j[t].b]);
+        }
+        for (uint32_t c = 0; c < root; c++) len[owner(c)] += changes[c];
+    }
+    uint32_t owner(uint32_t c) const { return c == hidden ? j[S - 2].a : c; }      // the hidden node's changes go to the root's first child
+    uint32_t shown_parent(uint32_t c) const { return parent[c] == hidden ? root : parent[c]; }
+    std::vector<uint32_t> kids(uint32_t v) const
+    {
+        const skx_tree_join &x = j[v - S];
+        if (v == root && hidden != 0xFFFFFFFFu) return {x.a, j[x.b - S].a, j[x.b - S].b};
+        return {x.a, x.b};
+    }
+    std::string label(const char *const *names, uint32_t c) const { return c < S ? names[c] : c == root ? "root" : "n" + std::to_string(c - S + 1); }
+};
+int bad(size_t at, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int bad(size_t at, const char *fmt, ...)                           // what skh_newick_joins refuses, with the place in the text
+{
+    char m[600];
+    va_list ap; va_start(ap, fmt); vsnprintf(m, sizeof m, fmt, ap); va_end(ap);
+    set_error("newick: position %zu: %s", at, m);
+    return SKX_EINVAL;
+}
+int check_join_table(const char *who, const skx_tree_join *joins, int n_, int root_three)
+{
+    const uint32_t n = (uint32_t)n_;
+    std::vector<char> used(2 * n - 1, 0);
+    for (uint32_t t = 0; t + 1 < n; t++)
+        for (const uint32_t c : {joins[t].a, joins[t].b}) {
+            if (c >= n + t || used[c]) { set_error("%s: join %u names a node that does not exist yet, or a child for the second time", who, t); return SKX_EINVAL; }
+            used[c] = 1;
+        }
+    if (root_three && (n < 3 || joins[n - 2].b != 2 * n - 3)) { set_error("%s: a trifurcating root is the join (a, 2S-3)", who); return SKX_EINVAL; }
+    return SKX_OK;
+}
+}  // namespace
+
+extern "C" int skh_newick_joins(const char *text, const char *const *names, int n_, skx_tree_join *joins, int *root_three)
+{
+    return guarded([&]() -> int {
+    if (root_three) *root_three = 0;
+    if (!text || !names || !joins || n_ < 2) { set_error("newick: bad arguments (at least 2 samples)"); return SKX_EINVAL; }
+    const uint32_t S = (uint32_t)n_;
+    const size_t n = strlen(text);
+    // names -> samples: the first of two equal names wins, as everywhere
+    std::vector<uint32_t> by_name(S);
+    std::iota(by_name.begin(), by_name.end(), 0u);
+    std::stable_sort(by_name.begin(), by_name.end(), [&](uint32_t x, uint32_t y) { return strcmp(names[x], names[y]) < 0; });
+    auto find = [&](const std::string &s) -> int64_t {
+        auto it = std::lower_bound(by_name.begin(), by_name.end(), s, [&](uint32_t x, const std::string &v) { return v.compare(names[x]) > 0; });
+        return it != by_name.end() && s == names[*it] ? (int64_t)*it : -1;
+    };
+    static const char SPECIAL[] = "()[]':;, \t\n\r\v\f";
+    auto special = [&](char c) { return c == 0 || strchr(SPECIAL, c) != nullptr; };
+    std::vector<char> seen(S, 0);
+    // an explicit stack (a caterpillar tree is as deep as it has leaves): the children of every open node, one run of `kids` each
+    std::vector<uint32_t> kids; std::vector<size_t> open;          // open[d] = where the children of the d-th open node begin in kids
+    size_t pos = 0; uint32_t made = 0; bool have_root = false, after = false, three = false;
+    auto skip = [&]() -> bool {                                    // white space and [comments]; false: a comment without its end
+        while (pos < n) {
+            if (strchr(" \t\n\r\v\f", text[pos])) pos++;
+            else if (text[pos] == '[') { const char *e = strchr(text + pos, ']'); if (!e) return false; pos = (size_t)(e - text) + 1; }
+            else break;
+        }
+        return true;
+    };
+    // 0: a label (maybe empty) in `out`; else the error is set
+    auto label = [&](std::string &out, bool &quoted) -> int {
+        out.clear(); quoted = false;
+        if (!skip()) return bad(pos, "a comment without its end");
+        if (pos < n && text[pos] == '\'') {
+            const size_t at = pos++; quoted = true;
+            for (;;) {
+                if (pos >= n) return bad(at, "a quoted label without its end");
+                if (text[pos] == '\'') { if (pos + 1 < n && text[pos + 1] == '\'') { out += '\''; pos += 2; continue; } pos++; return 0; }
+                out += text[pos++];
+            }
+        }
+        const size_t s = pos;
+        while (pos < n && !special(text[pos])) pos++;
+        out.assign(text + s, pos - s);
+        return 0;
+    };
+    // a node has closed: its branch length is read and dropped, and it becomes a child of the innermost open node, or the root
+    auto closed = [&](uint32_t node) -> int {
+        if (!skip()) return bad(pos, "a comment without its end");
+        if (pos < n && text[pos] == ':') { pos++; if (!skip()) return bad(pos, "a comment without its end"); while (pos < n && !special(text[pos])) pos++; }
+        after = true;
+        if (!open.empty()) kids.push_back(node); else have_root = true;
+        return 0;
+    };
+    std::string name; bool quoted;
+    for (;;) {
+        if (!skip()) return bad(pos, "a comment without its end");
+        if (pos >= n) return bad(pos, "the text ends inside the tree");
+        const char ch = text[pos];
+        if (have_root) {
+            if (ch != ';') return bad(pos, "text after the tree");
+            pos++;
+            if (!skip()) return bad(pos, "a comment without its end");
+            if (pos < n) return bad(pos, "text after the tree");
+            break;
+        }
+        if (after && ch != ',' && ch != ')' && ch != ';') return bad(pos, "unexpected character '%c'", ch);
+        if (ch == '(') { open.push_back(kids.size()); pos++; }
+        else if (ch == ',') {
+            if (!after) return bad(pos, "a ',' without a node before it");
+            after = false; pos++;
+            if (!skip()) return bad(pos, "a comment without its end");
+            if (pos < n && (text[pos] == ',' || text[pos] == ')')) return bad(pos, "a leaf without a name");
+        }
+        else if (ch == ')') {
+            const size_t at = pos++;
+            if (open.empty()) return bad(at, "a ')' without its '('");
+            const size_t first = open.back(), k = kids.size() - first;
+            open.pop_back();
+            if (k == 1) return bad(at, "a node with one child");
+            if (k == 0) return bad(at, "a leaf without a name");
+            if (k != 2 && !(k == 3 && open.empty())) return bad(at, "a node with %zu children (only the root may have three)", k);
+            if (made + (k - 1) > S - 1) return bad(at, "more nodes than %u samples can have", S);
+            if (k == 3) { joins[made] = {kids[first + 1], kids[first + 2]}; joins[made + 1] = {kids[first], S + made}; made += 2; three = true; }
+            else { joins[made] = {kids[first], kids[first + 1]}; made++; }
+            kids.resize(first);
+            if (int e = label(name, quoted)) return e;             // an inner label: read and dropped
+            if (int e = closed(S + made - 1)) return e;
+        }
+        else if (ch == ';') return bad(pos, "%s", open.empty() ? "a tree without a node" : "the tree ends inside a node");
+        else {
+            const size_t at = pos;
+            if (int e = label(name, quoted)) return e;
+            if (name.empty() && !quoted) return bad(at, "unexpected character '%c'", ch);
+            const int64_t s = find(name);
+            if (s < 0) return bad(at, "leaf '%s' is not a sample of the array", name.c_str());
+            if (seen[s]) return bad(at, "sample '%s' is named twice", name.c_str());
+            seen[s] = 1;
+            if (int e = closed((uint32_t)s)) return e;
+        }
+    }
+    for (uint32_t s = 0; s < S; s++) if (!seen[s]) { set_error("newick: sample '%s' is missing from the tree", names[s]); return SKX_EINVAL; }
+    if (made != S - 1) { set_error("newick: the tree does not join all samples"); return SKX_EINVAL; }
+    if (root_three) *root_three = three;
+    return SKX_OK;
+    });
+}
+
+extern "C" int skh_parsimony_newick(const char *const *names, const skx_tree_join *joins, int n_, int root_three, const uint64_t *branch_changes, char **buf, uint64_t *len)
+{
+    return guarded([&]() -> int {
+    if (!names || !joins || !branch_changes || !buf || !len || n_ < 2) { set_error("skh_parsimony_newick: bad arguments (at least 2 leaves)"); return SKX_EINVAL; }
+    if (int e = check_join_table("skh_parsimony_newick", joins, n_, root_three)) return e;
+    const JoinTree tr(joins, (uint32_t)n_, root_three != 0, branch_changes);
+    // the text, with an explicit stack (a caterpillar tree is as deep as it has leaves)
+    std::string o;
+    struct Frame { uint32_t v; std::vector<uint32_t> kids; size_t next; };
+    std::vector<Frame> fs; fs.push_back({tr.root, tr.kids(tr.root), 0});
+    while (!fs.empty()) {
+        Frame &f = fs.back();
+        const uint32_t v = f.v;
+        if (f.next == f.kids.size()) {
+            if (v < tr.S) o += newick_name(names[v]); else { o += ')'; if (v != tr.root) o += tr.label(names, v); }
+            if (v != tr.root) { o += ':'; o += std::to_string(tr.len[v]); }
+            fs.pop_back();
+            continue;
+        }
+        o += f.next == 0 ? '(' : ',';
+        const uint32_t c = f.kids[f.next++];
+        fs.push_back({c, c < tr.S ? std::vector<uint32_t>() : tr.kids(c), 0});
+    }
+    o += ";\n";
+    return to_buf(o, buf, len);
+    });
+}
+
+extern "C" int skh_parsimony_branches(const char *const *names, const skx_tree_join *joins, int n_, int root_three, const uint64_t *branch_changes, char **buf, uint64_t *len)
+{
+    return guarded([&]() -> int {
+    if (!names || !joins || !branch_changes || !buf || !len || n_ < 2) { set_error("skh_parsimony_branches: bad arguments (at least 2 leaves)"); return SKX_EINVAL; }
+    if (int e = check_join_table("skh_parsimony_branches", joins, n_, root_three)) return e;
+    const JoinTree tr(joins, (uint32_t)n_, root_three != 0, branch_changes);
+    std::string o = "Node\tParent\tLeaves\tLowest leaf\tChanges\n";
+    for (uint32_t c = 0; c < tr.root; c++) {
+        if (c == tr.hidden) continue;
+        o += tr.label(names, c); o += '\t'; o += tr.label(names, tr.shown_parent(c)); o += '\t'; o += std::to_string(tr.leaves[c]); o += '\t';
+        o += names[tr.low[c]]; o += '\t'; o += std::to_string(tr.len[c]); o += '\n';
+    }
+    return to_buf(o, buf, len);
+    });
+}

@@ -27,6 +27,7 @@ MARKER_DT = np.dtype([("row", "<u8"), ("group", "<u4"), ("n_in", "<u4"), ("n_out
 MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])                      # skx_marker_info
 MARKER_PRESENCE, MARKER_ALLELE = 1, 2
 PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
+TREE_JOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4")])                                                                        # skx_tree_join
 
 
 class Qual(C.Structure):
@@ -136,7 +137,8 @@ skx_array_subset_filtered skh_read_groups skh_align_groups skh_align_samples_fd
 skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv skh_mst_levels_csv
 skx_ctx_filter_cut
 skx_array_group_markers skh_markers skh_key_arms
-skx_array_pair_sites skh_distance_sites""".split()
+skx_array_pair_sites skh_distance_sites
+skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
 
@@ -191,6 +193,9 @@ def load_library():
     lib.skh_key_arms.restype = None
     lib.skx_array_pair_sites.argtypes = [vp, d, vp, u64, u64, pp, pp, vp, C.POINTER(u64)]
     lib.skh_distance_sites.argtypes = [vp, cp, d, C.POINTER(SelectSpec), C.POINTER(MstSpec), cp, u64, pp, C.POINTER(u64)]
+    lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
+    lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
+    lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skx_ctx_destroy.argtypes = [vp]
     lib.skx_ctx_sync.argtypes = [vp]
     lib.skx_ctx_stream.argtypes = [vp]
@@ -584,6 +589,50 @@ def default_context():
     if _default_ctx is None:
         _default_ctx = Context(int(os.environ.get("LOCAL_RANK", "0")) if os.environ.get("SKX_USE_LOCAL_RANK") else 0)
     return _default_ctx
+
+
+
+def _join_table(joins):
+    """joins as TREE_JOIN_DT records or as pairs -> [n - 1, 2] uint32"""
+    j = np.asarray(joins)
+    if j.dtype.names:
+        j = np.stack([j["a"], j["b"]], axis=1) if len(j) else np.zeros((0, 2), np.uint32)
+    return np.ascontiguousarray(j, np.uint32).reshape(-1, 2)
+
+
+def newick_joins(text, names):
+    """skh_newick_joins: Newick text over the samples `names` -> (joins as TREE_JOIN_DT, root_three) (host only)"""
+    load_library()
+    n = len(names)
+    arr = (C.c_char_p * max(n, 1))(*[x.encode() for x in names])
+    joins, three = np.zeros(max(n - 1, 1), TREE_JOIN_DT), C.c_int()
+    _check(_lib.skh_newick_joins(text.encode(), arr, n, _np_ptr(joins), C.byref(three)))
+    return joins[:n - 1], bool(three.value)
+
+
+def _parsimony_text(fn, names, joins, root_three, branch_changes):
+    load_library()
+    n = len(names)
+    arr = (C.c_char_p * n)(*[x.encode() for x in names])
+    j = _join_table(joins)
+    b = np.ascontiguousarray(branch_changes, np.uint64)
+    if len(j) != n - 1 or len(b) != 2 * n - 2:
+        raise ValueError("n - 1 joins and 2 n - 2 branches are required")
+    p, ln = C.c_void_p(), C.c_uint64()
+    _check(fn(arr, _np_ptr(j), n, int(root_three), _np_ptr(b), C.byref(p), C.byref(ln)))
+    return _take(p, ln).decode()
+
+
+def parsimony_newick(names, joins, root_three, branch_changes):
+    """skh_parsimony_newick: the tree of skh_newick_joins again, the changes as branch lengths (host only)"""
+    load_library()
+    return _parsimony_text(_lib.skh_parsimony_newick, names, joins, root_three, branch_changes)
+
+
+def parsimony_branches(names, joins, root_three, branch_changes):
+    """skh_parsimony_branches: the same tree as PREFIX.branches.tsv (host only)"""
+    load_library()
+    return _parsimony_text(_lib.skh_parsimony_branches, names, joins, root_three, branch_changes)
 
 
 def nj_newick(names, joins):
