@@ -395,6 +395,29 @@ int  skx_array_group_markers(skx_array *a, const int32_t *segment_of, int n_grou
 typedef struct { uint64_t row; uint32_t pair; uint8_t base_i, base_j, reserved[2]; } skx_pair_site;
 int  skx_array_pair_sites(skx_array *a, double min_freq, const uint32_t *ij, uint64_t n_pairs, uint64_t max_records,
                           skx_pair_site **records, skx_key **keys, uint64_t *counts, uint64_t *n);
+/* `ska curve`: how the collection behaves as it grows -- the rows present, the rows that pass a frequency threshold and the variant sites after
+ * each sample of an order has been added, for any number of orders from one load.  The reference has no counterpart: `ska nk` prints one number
+ * for the whole file, and its users chain `ska delete` down to a prefix (merge_ska_array.rs:231-271) and `ska align` once per prefix and shuffle.
+ * Definition.  The array holds S samples and U rows, in its current order.  code(cell) is the 4-bit IUPAC set as above (skx_array_group_markers:
+ * A 1, C 2, T 4, G 8; '-' and the 0 byte are 0); a cell is unambiguous when popcount(code) == 1.  An order is a permutation o[0..S) of the sample
+ * indices.  For t = 1..S the prefix is o[0..t); per row n = cells of the prefix with code != 0 and B = OR of the codes of its unambiguous cells.
+ * The threshold, computed in doubles exactly like this: thr(t) = max(1, (uint64)ceil(t * min_freq)).  Four counts over the rows per (order, t):
+ *     pan           n >= 1                           the rows `ska delete` of everybody outside the prefix leaves
+ *     core          n >= thr(t)                      the rows --min-freq f --filter no-filter keeps on the prefix
+ *     variant       popcount(B) >= 2
+ *     core_variant  n >= thr(t) and popcount(B) >= 2   the columns of `ska align --min-freq f --filter no-ambig-or-const --no-gap-only-sites`
+ * core is not monotone in t when min_freq < 1: it is counted at every step.
+ * orders: n_orders x S sample indices, every run of S a permutation; counts: the caller's memory, n_orders x S x 4 in the order pan, core,
+ * variant, core_variant (counts[(p * S + t - 1) * 4 + c]).  `a` keeps its content (an array held as pieces or lazily is materialised first);
+ * both key widths are taken, and so is an array without split k-mers (skx_array_load_filtered, skx_array_subset_filtered): nothing here needs
+ * keys.  SKX_EINVAL with a message that begins "curve:" for NULL arguments, n_orders == 0, NaN or min_freq outside [0, 1], a run that is not a
+ * permutation (a repeat, an index out of range), a cell outside the alphabet; SKX_EUNSUP with the same beginning above 65 535 samples.  U == 0:
+ * SKX_OK with zeros.  The results are sums of integers: the same bytes whatever the order of arrival.
+ * One workgroup walks one order over SKX_CURVE_TILE_ROWS rows and keeps SKX_CURVE_LDS_STEPS steps of counters on chip at a time; a launch takes
+ * at most SKX_CURVE_BATCH_ORDERS orders and 2^22 (order, step) pairs.  Device memory beside the array: 36 bytes per (order, step) of a launch
+ * (at most 151 MB) and 4 S bytes of thresholds. */
+enum { SKX_CURVE_TILE_ROWS = 4096, SKX_CURVE_LDS_STEPS = 1024, SKX_CURVE_BATCH_ORDERS = 1024 };
+int  skx_array_curve(skx_array *a, const int32_t *orders, uint32_t n_orders, double min_freq, uint64_t *counts);
 /* MergeSkaArray::weed (merge_ska_array.rs:452-487): rows whose split k-mer is (reverse: is not) in `weed` are removed;
  * `weed` = the split k-mers of the weed FASTA (RefSka::new + kmer_iter, ska_ref.rs:189-262,541), i.e. the key set of its
  * dictionary: skx_dictset_build_files (1 sample) -> skx_keyset_union. */

@@ -59,6 +59,25 @@ int skh_read_groups(const char *path, char **buf, uint64_t *len, uint64_t *n_pai
  * Phases: markers.load / markers.pass / markers.text. */
 int skh_markers(skx_ctx *ctx, const char *skf_file, const char *groups_file, const char *out_prefix, double min_in, double max_out,
                 int min_group_size, int kinds, int fasta);
+/* the seeded orders of `ska curve`, from one stream: splitmix64 (state = seed; next: state += 0x9E3779B97F4A7C15, z = state,
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^ z >> 31), order 0 drawn first; each order starts as
+ * 0..S-1 and is shuffled by Fisher-Yates from i = S-1 down to 1, swapping o[i] and o[j] with j from [0, i] by rejection: draws x >= 2^64 -
+ * 2^64 mod (i + 1) are thrown away, j = x mod (i + 1).  orders: the caller's n_orders x S.  Host only (tests/curve_model.py states the same). */
+int skh_curve_orders(uint64_t seed, uint32_t n_samples, uint32_t n_orders, int32_t *orders);
+/* <PREFIX>.curve.tsv from the counts of skx_array_curve (host only): header "t\tpan_min\tpan_median\tpan_max\tpan_mean\tcore_min\t...
+ * \tcore_variant_mean", then one line per t = 1..S with, for each of pan, core, variant and core_variant, the minimum, the lower median (place
+ * (P - 1) / 2 of the sorted values), the maximum and the mean over the P orders.  The mean has three decimals and is rounded half up in integers,
+ * (sum * 1000 + P / 2) / P: no floating point reaches the text.  *buf is malloc'd (skx_free). */
+int skh_curve_tsv(const uint64_t *counts, uint32_t n_orders, uint32_t n_samples, char **buf, uint64_t *len);
+/* `ska curve <SKF_FILE> -o PREFIX [--permutations P] [--seed N] [--min-freq F] [--order-file FILE] [--all-permutations]` (no counterpart in the
+ * reference): the file is loaded once (skh_load_array) and one call of skx_array_curve answers every order -- n_permutations (1..10 000) orders
+ * of skh_curve_orders for `seed`, or, with order_file != NULL, the one order of that file: sample names, one a line (blank lines and a trailing
+ * carriage return ignored), every sample of the array exactly once; a name that is unknown, given twice or missing is SKX_EINVAL with the name in
+ * the message.  <PREFIX>.curve.tsv as skh_curve_tsv writes it; with all_permutations or an order file also <PREFIX>.curve.permutations.tsv:
+ * header "permutation\tt\tsample\tpan\tcore\tvariant\tcore_variant\tnew", one line per order (from 0) and t, sample = the one added at t,
+ * new = pan(t) - pan(t - 1) with pan(0) = 0.  Phases: curve.load / curve.orders / curve.kernel / curve.text. */
+int skh_curve(skx_ctx *ctx, const char *skf_file, const char *out_prefix, uint32_t n_permutations, uint64_t seed, double min_freq,
+              const char *order_file, int all_permutations);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

@@ -123,6 +123,14 @@ const std::vector<Cmd> &commands()
           {"--min-group-size", "<N>", "Do not report groups of fewer than N samples (they still count as others) [default: 1]"},
           {"--kind", "<KIND>", "Markers to report [default: both] [possible values: presence, allele, both]"},
           {"--fasta", "", "Also write <OUTPUT>.<label>.markers.fa per group: `ska weed <SKF_FILE> <that file> --reverse --min-freq 0` keeps exactly its marker rows"}}},
+        {"curve", "(MI355X engine) Count the split k-mers present, those passing --min-freq and the variant sites as samples are added one by one", "ska curve [OPTIONS] -o <OUTPUT> <SKF_FILE>",
+         {{"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on"}},
+         {{"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.curve.tsv (per number of samples: minimum, median, maximum and mean over the orders of pan, core, variant and core_variant)"},
+          {"--permutations", "<P>", "Number of random orders of the samples, 1 to 10000 [default: 20]"},
+          {"--seed", "<N>", "Seed of the random orders [default: 1]"},
+          {"--min-freq", "<MIN_FREQ>", "Minimum fraction of the samples added so far a core k-mer has to appear in [default: 0.9]"},
+          {"--order-file", "<FILE>", "One order instead of random ones: every sample name of <SKF_FILE> once, one per line (for instance by collection date); also writes <OUTPUT>.curve.permutations.tsv"},
+          {"--all-permutations", "", "Also write <OUTPUT>.curve.permutations.tsv: every order's counts, the sample added and the new split k-mers at each step"}}},
     };
     return C;
 }

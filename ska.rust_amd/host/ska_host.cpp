@@ -551,7 +551,8 @@ const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min
                             "--min-freq", "-m", "--filter", "-s", "--skf-file", "--format", "--gpus",
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
                             "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels", "--sites", "--sites-max",
-                            "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind", nullptr};
+                            "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind",
+                            "--permutations", "--seed", "--order-file", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 }
 int skh::fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
@@ -592,7 +593,8 @@ const char *skh::clap_arg(const char *flag)
         {"--query", "--query <NAMES>"}, {"--query-file", "--query-file <FILE>"}, {"--query-skf", "--query-skf <FILE>"},
         {"--max-snps", "--max-snps <N>"}, {"--max-mismatches", "--max-mismatches <P>"}, {"--closest", "--closest <K>"},
         {"--mst-clusters", "--mst-clusters <PREFIX>"}, {"--levels", "--levels <L1,L2,...>"}, {"--sites", "--sites <PREFIX>"}, {"--sites-max", "--sites-max <N>"},
-        {"--min-in", "--min-in <P>"}, {"--max-out", "--max-out <Q>"}};
+        {"--min-in", "--min-in <P>"}, {"--max-out", "--max-out <Q>"},
+        {"--permutations", "--permutations <P>"}, {"--seed", "--seed <N>"}, {"--order-file", "--order-file <FILE>"}};
     for (auto &sp : SPELLING) if (!strcmp(flag, sp[0])) return sp[1];
     return flag;
 }
@@ -1042,6 +1044,21 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (a.has("--min-group-size")) if (int e = clap_uint(a.get("--min-group-size"), "--min-group-size <N>", 1, "must be one or higher")) return e;
         if (a.has("--kind")) { const std::string v = a.get("--kind"); if (v != "presence" && v != "allele" && v != "both") return clap_possible(v, "--kind <KIND>", "presence, allele, both"); }
     }
+    else if (cmd == "curve") {
+        // the engine's own mode: one device's array, refused as clap refuses a missing requirement, a conflict and a value that does not parse
+        if (a.pos.empty()) return clap_missing("curve", "<SKF_FILE>");
+        if (a.pos.size() > 1) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[1].c_str(), skh_usage_line("curve")); return 2; }
+        if (!a.has("-o")) return clap_missing("curve", "-o <OUTPUT>");
+        if (a.has("--gpus") || multi) return clap_conflict("curve", "--gpus", "<SKF_FILE>");
+        if (int e = conflicts("curve", a, false, {"--order-file"}, {"--permutations", "--seed"})) return e;
+        for (const char *o : {"-o", "--order-file"}) if (a.has(o) && a.get(o).empty()) return clap_invalid("", clap_arg(o), "a value is required");
+        if (a.has("--permutations")) {
+            if (int e = clap_uint(a.get("--permutations"), "--permutations <P>", 1, "must be between 1 and 10000 (inclusive)", true)) return e;
+            if (strtoull(a.get("--permutations").c_str(), nullptr, 10) > 10000) return clap_invalid(a.get("--permutations"), "--permutations <P>", "must be between 1 and 10000 (inclusive)");
+        }
+        if (a.has("--seed")) if (int e = clap_uint(a.get("--seed"), "--seed <N>", 0, "", true)) return e;
+        if (int e = freq()) return e;
+    }
     else if (cmd == "lo") {                                                                                       // cli.rs:395-425
         if (a.pos.size() < 2) return clap_missing("lo", a.pos.empty() ? "<INPUT_SKF>\n  <OUTPUT>" : "<OUTPUT>");
         if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("lo")); return 2; }
@@ -1099,6 +1116,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"weed", " -o --reverse -m --min-freq --filter-ambig-as-missing --filter --ambig-mask --no-gap-only-sites "},
             {"nk", " --full-info "}, {"cov", " -k --single-strand "}, {"selftest", " --gpus "},
             {"markers", " -o --groups --min-in --max-out --min-group-size --kind --fasta --gpus "},
+            {"curve", " -o --permutations --seed --min-freq --order-file --all-permutations --gpus "},
             {"lo", " -r --reference -m --missing -d --depth -n --indel-kmers --threads "}};
         for (auto &kc : KNOWN)
             if (cmd == kc.cmd)
@@ -1201,6 +1219,12 @@ extern "C" int skh_main(int argc, char **argv)
         if (skh_markers(ctx, a.pos[0].c_str(), a.get("--groups").c_str(), a.get("-o").c_str(), strtod(a.get("--min-in", "1.0").c_str(), nullptr),
                         strtod(a.get("--max-out", "0.0").c_str(), nullptr), min_size, kinds, a.has("--fasta")) != SKX_OK)
             rcode = engine_fail();
+    } else if (cmd == "curve") {                                                                                  // the engine's own: skh_curve
+        const std::string order_file = a.get("--order-file");
+        if (skh_curve(ctx, a.pos[0].c_str(), a.get("-o").c_str(), (uint32_t)strtoull(a.get("--permutations", "20").c_str(), nullptr, 10),
+                      strtoull(a.get("--seed", "1").c_str(), nullptr, 10), strtod(a.get("--min-freq", "0.9").c_str(), nullptr),
+                      a.has("--order-file") ? order_file.c_str() : nullptr, a.has("--all-permutations")) != SKX_OK)
+            rcode = engine_fail();
     } else if (cmd == "cov") {                                                                                    // cli.rs Cov, lib.rs:828-851
         if (a.pos.size() != 2) return fail("usage: ska cov <fastq_fwd> <fastq_rev> [-k K] [--single-strand]");
         const int k = atoi(a.get("-k", "31").c_str());
@@ -1257,7 +1281,7 @@ extern "C" int skh_main(int argc, char **argv)
         if (r == SKX_EEMPTY) rcode = 1;                                                                          // extremities.rs: std::process::exit(1)
         else if (r != SKX_OK) rcode = engine_fail();
     } else {
-        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers)");
+        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers, curve)");
     }
     const double t_done = since();
     if (dbg) fprintf(stderr, "[skx] main: %s done after %.2f s\n", cmd.c_str(), t_done);

@@ -26,6 +26,7 @@ MARKER_DT = np.dtype([("row", "<u8"), ("group", "<u4"), ("n_in", "<u4"), ("n_out
                       ("reserved", "u1")])                                               # skx_marker
 MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])                      # skx_marker_info
 MARKER_PRESENCE, MARKER_ALLELE = 1, 2
+CURVE_TILE_ROWS, CURVE_LDS_STEPS, CURVE_BATCH_ORDERS = 4096, 1024, 1024      # SKX_CURVE_* (include/skx.h): the shape of skx_array_curve's kernel
 PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
 TREE_JOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4")])                                                                        # skx_tree_join
 
@@ -138,6 +139,7 @@ skx_array_distance_mst skx_array_distance_mst_prefiltered skh_distance_mst_tsv s
 skx_ctx_filter_cut
 skx_array_group_markers skh_markers skh_key_arms
 skx_array_pair_sites skh_distance_sites
+skx_array_curve skh_curve skh_curve_orders skh_curve_tsv
 skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
@@ -193,6 +195,10 @@ def load_library():
     lib.skh_key_arms.restype = None
     lib.skx_array_pair_sites.argtypes = [vp, d, vp, u64, u64, pp, pp, vp, C.POINTER(u64)]
     lib.skh_distance_sites.argtypes = [vp, cp, d, C.POINTER(SelectSpec), C.POINTER(MstSpec), cp, u64, pp, C.POINTER(u64)]
+    lib.skx_array_curve.argtypes = [vp, vp, C.c_uint32, d, vp]
+    lib.skh_curve_orders.argtypes = [u64, C.c_uint32, C.c_uint32, vp]
+    lib.skh_curve_tsv.argtypes = [vp, C.c_uint32, C.c_uint32, pp, C.POINTER(u64)]
+    lib.skh_curve.argtypes = [vp, cp, cp, C.c_uint32, u64, d, cp, i]
     lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
     lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
@@ -318,6 +324,23 @@ def _take(ptr, n):
 
 def qual(min_count=5, min_qual=20, qual_filter=QUAL_STRICT):
     return Qual(min_count, min_qual, qual_filter)
+
+
+def curve_orders(seed, n_samples, n_orders):
+    """skh_curve_orders: the seeded orders of `ska curve` (host only) -> int32 [n_orders, n_samples]"""
+    load_library()
+    o = np.zeros((n_orders, n_samples), np.int32)
+    _check(_lib.skh_curve_orders(int(seed), int(n_samples), int(n_orders), _np_ptr(o)))
+    return o
+
+
+def curve_tsv(counts):
+    """skh_curve_tsv: the text of <PREFIX>.curve.tsv from counts [P, S, 4] (host only)"""
+    load_library()
+    c = np.ascontiguousarray(counts, np.uint64)
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_curve_tsv(_np_ptr(c), c.shape[0], c.shape[1], C.byref(p), C.byref(n)))
+    return _take(p, n).decode()
 
 
 def cov_histogram(fq1, fq2, k=31, rc=True, ctx=None):
@@ -561,6 +584,11 @@ class Context:
         PREFIX.<label>.markers.fa per group, from one load"""
         _check(_lib.skh_markers(self.h, os.fsencode(skf_file), os.fsencode(groups_file), os.fsencode(out_prefix), float(min_in), float(max_out),
                                 int(min_group_size), int(kinds), int(fasta)))
+
+    def curve(self, skf_file, out_prefix, permutations=20, seed=1, min_freq=0.9, order_file=None, all_permutations=False):
+        """`ska curve <skf> -o PREFIX` (skh_curve): PREFIX.curve.tsv and, with all_permutations or an order file, PREFIX.curve.permutations.tsv"""
+        _check(_lib.skh_curve(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), int(permutations), int(seed), float(min_freq),
+                              None if order_file is None else os.fsencode(order_file), int(all_permutations)))
 
     def align_samples(self, inputs, names, fd, threads=1, min_freq=0.9, filter_ambig_as_missing=False, filter_type=FILTER_NO_CONST, mask_ambig=False,
                       ignore_const_gaps=False):
@@ -1094,6 +1122,17 @@ class Array:
         _lib.skx_free(pr)
         _lib.skx_free(pk)
         return rec, keys, info[:n_groups]
+
+    def curve(self, orders, min_freq=0.9):
+        """skx_array_curve: pan, core, variant and core_variant rows after each sample of every order has been added, this array left as it is.
+        orders: [P, S] (or [S]) sample indices, every row a permutation -> uint64 [P, S, 4]"""
+        o = np.ascontiguousarray(orders, np.int32)
+        o = o.reshape(1, -1) if o.ndim == 1 else o
+        if o.ndim != 2 or o.shape[1] != self.nsamples:
+            raise ValueError("every order names each of the array's samples")
+        counts = np.zeros((o.shape[0], o.shape[1], 4), np.uint64)
+        _check(_lib.skx_array_curve(self.h, _np_ptr(o), o.shape[0], float(min_freq), _np_ptr(counts)))
+        return counts
 
     def pair_sites(self, ij, min_freq=0.0, max_records=0, keys=True):
         """skx_array_pair_sites: the rows that make up the filter-ambiguous distance of each pair of ij ([n_pairs, 2], i < j), this array left as
