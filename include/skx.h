@@ -437,6 +437,35 @@ int  skx_cov_histogram(skx_ctx *ctx, const char *fastq_fwd, const char *fastq_re
  * The text is malloc'd (skx_free).  Errors where the reference panics: "Cannot create reference from FASTQ files",
  * "<file> has no valid sequence" (SKX_EEMPTY), "No split k-mers mapped to reference". */
 int  skx_array_map(skx_array *a, const char *reference_fasta, int ambig_mask, int repeat_mask, int format, int threads, char **buf, uint64_t *len);
+/* `ska screen`: which samples carry which sequences of a panel, and how well they match -- three integers per (record, sample) of a multi-FASTA
+ * panel (resistance genes, virulence factors, replicons, typing loci) from one pass, without the S x panel-length cells `ska map` writes.  The
+ * reference has no counterpart: its users count columns of `ska map`'s alignment, or run `ska weed --reverse` and `ska nk` once per record.
+ * Definition (tests/screen_model.py states the same).  A panel is a FASTA file of R records.  A record's windows are exactly those `ska map`
+ * gives a chromosome: runs of ACGT in either case, N splitting runs, and the end-of-record quirk (a run that starts less than k + 1 letters
+ * before the end of its record gives none); each window has the position of its middle base, its canonical split k-mer and its is_rc.  Every
+ * window counts on its own: a split k-mer that occurs twice counts twice, within a record or across records.  A window hits when its split
+ * k-mer is a row of the array.  For a hit window and sample s the cell is the array's byte for (row, s), passed through RC_IUPAC when is_rc
+ * (ska_ref.rs:519-530); the 0 byte an array may hold for '-' is '-'.  Per (record r, sample s), over r's hit windows:
+ *     found   the cells that are not '-'
+ *     match   the cells equal to the record's own middle base, upper-cased
+ *     ambig   the cells that are present and none of A, C, G, T
+ *     snp     found - match - ambig                                       (derived, not stored)
+ * Per record: length = its bytes of sequence, windows = its windows, rows_hit = its hit windows.  A pair (r, s) passes, for a cover C and an
+ * identity I in [0, 1], when windows > 0 and found >= max(1, ceil(C * windows)) and match >= ceil(I * found), the products in doubles
+ * (skh_screen: --min-cover, --min-identity).
+ * records[r] = {length, windows, rows_hit}; ids = the R record ids (the header up to white space), each NUL-terminated, one after the other;
+ * cells[r * S + s] = {found, match, ambig}.  All three are malloc'd (skx_free); on an error none is.  `a` keeps its content (an array held as
+ * pieces or lazily is materialised first); both key widths, engine-ordered or not.  SKX_EINVAL "split k-mers and variants are out of step ..."
+ * as skx_array_map; "Cannot create reference from FASTQ files" for a FASTQ panel; SKX_EEMPTY "<file> has no valid sequence" for a panel
+ * without a window; SKX_EINVAL naming the id for a record id that occurs twice, and for a cell outside the alphabet; SKX_EUNSUP above 2^31
+ * (record, sample) pairs.  A panel none of whose windows hit (or an array without rows) is no error: every count is 0.  The counts are sums of
+ * integers: the same bytes whatever the order of arrival.
+ * One workgroup walks SKX_SCREEN_TILE consecutive hit windows for SKX_SCREEN_SAMPLES samples, a lane a sample.  Device memory beside the array:
+ * `ska map`'s window buffers (25 bytes a panel byte, 33 at k > 31), 9 bytes a hit window, 12 bytes a (record, sample) pair. */
+enum { SKX_SCREEN_TILE = 1024, SKX_SCREEN_SAMPLES = 256 };
+typedef struct { uint64_t length, windows, rows_hit; } skx_screen_record;
+typedef struct { uint32_t found, match, ambig; } skx_screen_cell;
+int  skx_array_screen(skx_array *a, const char *panel_fasta, uint64_t *n_records, skx_screen_record **records, char **ids, skx_screen_cell **cells);
 /* the `k` a .skf file states in its first fields, without loading it (0: not found there, or the file cannot be read): lets a caller that
  * would try 64-bit keys first and 128-bit keys next (lib.rs:635-661) go to the right width at once */
 int  skx_skf_peek_k(const char *path);

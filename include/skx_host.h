@@ -78,6 +78,24 @@ int skh_curve_tsv(const uint64_t *counts, uint32_t n_orders, uint32_t n_samples,
  * new = pan(t) - pan(t - 1) with pan(0) = 0.  Phases: curve.load / curve.orders / curve.kernel / curve.text. */
 int skh_curve(skx_ctx *ctx, const char *skf_file, const char *out_prefix, uint32_t n_permutations, uint64_t seed, double min_freq,
               const char *order_file, int all_permutations);
+/* the three texts of `ska screen` from what skx_array_screen returns (host only; definition of the counts and of "passes" in include/skx.h,
+ * restated in tests/screen_model.py).  names: the array's n_samples sample names.
+ * SKH_SCREEN_PAIRS   <PREFIX>.screen.tsv: header "record\tlength\twindows\tsample\tfound\tmatch\tambig\tsnp\tcover\tidentity", then one line
+ *                    per passing (record, sample), in panel order and then array order; snp = found - match - ambig, cover = found / windows
+ *                    and identity = match / found, each the double quotient printed as %.4f.
+ * SKH_SCREEN_SUMMARY <PREFIX>.screen.summary.tsv: header "record\tlength\twindows\trows_hit\tsamples_passing", one line per record, those
+ *                    without a window included.
+ * SKH_SCREEN_MATRIX  <PREFIX>.screen.matrix.tsv: header "record" and the sample names, one line per record: its id, then 1 where the pair
+ *                    passes and 0 where it does not.
+ * SKX_EINVAL for NULL arguments, another `which`, NaN or a cover or identity outside [0, 1].  *buf is malloc'd (skx_free). */
+enum { SKH_SCREEN_PAIRS = 0, SKH_SCREEN_SUMMARY = 1, SKH_SCREEN_MATRIX = 2 };
+int skh_screen_text(int which, uint64_t n_records, const skx_screen_record *records, const char *ids, const skx_screen_cell *cells,
+                    const char *const *names, uint64_t n_samples, double min_cover, double min_identity, char **buf, uint64_t *len);
+/* `ska screen <SKF_FILE> <PANEL> -o PREFIX [--min-cover C] [--min-identity I] [--matrix]` (no counterpart in the reference): the file is loaded
+ * once (skh_load_array), one call of skx_array_screen counts every (record, sample) pair, and <PREFIX>.screen.tsv, <PREFIX>.screen.summary.tsv
+ * and, with matrix != 0, <PREFIX>.screen.matrix.tsv are written as skh_screen_text forms them.  The refusals are skx_array_screen's.
+ * Phases: screen.load / screen.counts (inside it screen.read_panel, screen.windows, screen.lookup, screen.kernel) / screen.text. */
+int skh_screen(skx_ctx *ctx, const char *skf_file, const char *panel_fasta, const char *out_prefix, double min_cover, double min_identity, int matrix);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

@@ -131,6 +131,12 @@ const std::vector<Cmd> &commands()
           {"--min-freq", "<MIN_FREQ>", "Minimum fraction of the samples added so far a core k-mer has to appear in [default: 0.9]"},
           {"--order-file", "<FILE>", "One order instead of random ones: every sample name of <SKF_FILE> once, one per line (for instance by collection date); also writes <OUTPUT>.curve.permutations.tsv"},
           {"--all-permutations", "", "Also write <OUTPUT>.curve.permutations.tsv: every order's counts, the sample added and the new split k-mers at each step"}}},
+        {"screen", "(MI355X engine) Report which samples carry which sequences of a panel, with the coverage and identity of each", "ska screen [OPTIONS] -o <OUTPUT> <SKF_FILE> <PANEL>",
+         {{"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on"}, {"<PANEL>", "", "FASTA file of the sequences to look for (genes, replicons, typing loci), one record each"}},
+         {{"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.screen.tsv (one line per record and sample that pass) and <OUTPUT>.screen.summary.tsv (one line per record)"},
+          {"--min-cover", "<C>", "Smallest fraction of a record's split k-mers a sample must have, 0 to 1 [default: 0.9]"},
+          {"--min-identity", "<I>", "Smallest fraction of the split k-mers found whose middle base must be the record's, 0 to 1 [default: 0]"},
+          {"--matrix", "", "Also write <OUTPUT>.screen.matrix.tsv: records by samples, 1 where the pair passes and 0 where it does not"}}},
     };
     return C;
 }

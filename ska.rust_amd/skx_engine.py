@@ -27,6 +27,10 @@ MARKER_DT = np.dtype([("row", "<u8"), ("group", "<u4"), ("n_in", "<u4"), ("n_out
 MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])                      # skx_marker_info
 MARKER_PRESENCE, MARKER_ALLELE = 1, 2
 CURVE_TILE_ROWS, CURVE_LDS_STEPS, CURVE_BATCH_ORDERS = 4096, 1024, 1024      # SKX_CURVE_* (include/skx.h): the shape of skx_array_curve's kernel
+SCREEN_TILE, SCREEN_SAMPLES = 1024, 256                                     # SKX_SCREEN_* (include/skx.h): the shape of skx_array_screen's kernel
+SCREEN_RECORD_DT = np.dtype([("length", "<u8"), ("windows", "<u8"), ("rows_hit", "<u8")])      # skx_screen_record
+SCREEN_CELL_DT = np.dtype([("found", "<u4"), ("match", "<u4"), ("ambig", "<u4")])              # skx_screen_cell
+SCREEN_PAIRS, SCREEN_SUMMARY, SCREEN_MATRIX = 0, 1, 2                       # SKH_SCREEN_* (include/skx_host.h)
 PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
 TREE_JOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4")])                                                                        # skx_tree_join
 
@@ -140,6 +144,7 @@ skx_ctx_filter_cut
 skx_array_group_markers skh_markers skh_key_arms
 skx_array_pair_sites skh_distance_sites
 skx_array_curve skh_curve skh_curve_orders skh_curve_tsv
+skx_array_screen skh_screen skh_screen_text
 skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
@@ -199,6 +204,9 @@ def load_library():
     lib.skh_curve_orders.argtypes = [u64, C.c_uint32, C.c_uint32, vp]
     lib.skh_curve_tsv.argtypes = [vp, C.c_uint32, C.c_uint32, pp, C.POINTER(u64)]
     lib.skh_curve.argtypes = [vp, cp, cp, C.c_uint32, u64, d, cp, i]
+    lib.skx_array_screen.argtypes = [vp, cp, C.POINTER(u64), pp, pp, pp]
+    lib.skh_screen_text.argtypes = [i, u64, vp, vp, vp, C.POINTER(cp), u64, d, d, pp, C.POINTER(u64)]
+    lib.skh_screen.argtypes = [vp, cp, cp, cp, d, d, i]
     lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
     lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
@@ -340,6 +348,20 @@ def curve_tsv(counts):
     c = np.ascontiguousarray(counts, np.uint64)
     p, n = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_curve_tsv(_np_ptr(c), c.shape[0], c.shape[1], C.byref(p), C.byref(n)))
+    return _take(p, n).decode()
+
+
+def screen_text(which, ids, records, cells, names, min_cover=0.9, min_identity=0.0):
+    """skh_screen_text: one of the three texts of `ska screen` (SCREEN_PAIRS, SCREEN_SUMMARY, SCREEN_MATRIX) from what Array.screen returns
+    (host only)"""
+    load_library()
+    rec = np.ascontiguousarray(records, SCREEN_RECORD_DT)
+    cel = np.ascontiguousarray(cells, SCREEN_CELL_DT).reshape(len(rec), len(names))
+    blob = b"".join(x.encode() + b"\0" for x in ids)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_screen_text(int(which), len(rec), _np_ptr(rec), blob, _np_ptr(cel), nm, len(names), float(min_cover), float(min_identity),
+                                C.byref(p), C.byref(n)))
     return _take(p, n).decode()
 
 
@@ -589,6 +611,10 @@ class Context:
         """`ska curve <skf> -o PREFIX` (skh_curve): PREFIX.curve.tsv and, with all_permutations or an order file, PREFIX.curve.permutations.tsv"""
         _check(_lib.skh_curve(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), int(permutations), int(seed), float(min_freq),
                               None if order_file is None else os.fsencode(order_file), int(all_permutations)))
+
+    def screen(self, skf_file, panel, out_prefix, min_cover=0.9, min_identity=0.0, matrix=False):
+        """`ska screen <skf> <panel> -o PREFIX` (skh_screen): PREFIX.screen.tsv, PREFIX.screen.summary.tsv and, with matrix, PREFIX.screen.matrix.tsv"""
+        _check(_lib.skh_screen(self.h, os.fsencode(skf_file), os.fsencode(panel), os.fsencode(out_prefix), float(min_cover), float(min_identity), int(matrix)))
 
     def align_samples(self, inputs, names, fd, threads=1, min_freq=0.9, filter_ambig_as_missing=False, filter_type=FILTER_NO_CONST, mask_ambig=False,
                       ignore_const_gaps=False):
@@ -1133,6 +1159,23 @@ class Array:
         counts = np.zeros((o.shape[0], o.shape[1], 4), np.uint64)
         _check(_lib.skx_array_curve(self.h, _np_ptr(o), o.shape[0], float(min_freq), _np_ptr(counts)))
         return counts
+
+    def screen(self, path):
+        """skx_array_screen: per (record, sample) of the FASTA panel at `path` the hit windows' cells that are present, equal the record's base
+        and are ambiguous, this array left as it is -> (ids, records as SCREEN_RECORD_DT [R], cells as SCREEN_CELL_DT [R, S])"""
+        n, pr, pi, pc = C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(_lib.skx_array_screen(self.h, os.fsencode(path), C.byref(n), C.byref(pr), C.byref(pi), C.byref(pc)))
+        R, S = n.value, self.nsamples
+        rec = np.frombuffer(C.string_at(pr, R * SCREEN_RECORD_DT.itemsize), SCREEN_RECORD_DT).copy()
+        cells = np.frombuffer(C.string_at(pc, R * S * SCREEN_CELL_DT.itemsize), SCREEN_CELL_DT).copy().reshape(R, S)
+        ids, at = [], pi.value
+        for _ in range(R):
+            s = C.string_at(at)
+            ids.append(s.decode())
+            at += len(s) + 1
+        for p in (pr, pi, pc):
+            _lib.skx_free(p)
+        return ids, rec, cells
 
     def pair_sites(self, ij, min_freq=0.0, max_records=0, keys=True):
         """skx_array_pair_sites: the rows that make up the filter-ambiguous distance of each pair of ij ([n_pairs, 2], i < j), this array left as
