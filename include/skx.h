@@ -466,6 +466,41 @@ enum { SKX_SCREEN_TILE = 1024, SKX_SCREEN_SAMPLES = 256 };
 typedef struct { uint64_t length, windows, rows_hit; } skx_screen_record;
 typedef struct { uint32_t found, match, ambig; } skx_screen_cell;
 int  skx_array_screen(skx_array *a, const char *panel_fasta, uint64_t *n_records, skx_screen_record **records, char **ids, skx_screen_cell **cells);
+/* `ska qc`: which samples should not be in this file -- six counts per sample that each depend on a statistic of the row a cell sits in, from
+ * two passes over the matrix.  The reference has no counterpart: `ska nk` (lib.rs:808-827) prints one k-mer count per sample, and its users run
+ * `ska delete` and `ska nk` once per sample and compare.
+ * Definition (tests/qc_model.py states the same).  The array holds S samples and U rows in its current order.  code(cell) is the 4-bit IUPAC
+ * set of skx_array_group_markers (A 1, C 2, T 4, G 8; '-' and the 0 byte are 0).  A cell is present when its code != 0 and unambiguous when
+ * popcount(code) == 1.  Per row r:
+ *     n       = its present cells
+ *     c[b]    = its cells that are exactly the unambiguous base b (b in A, C, T, G)
+ *     unamb   = c[A] + c[C] + c[T] + c[G]
+ *     major   = the base with the largest c[b], ties going to the lowest code (A < C < T < G); undefined when unamb == 0
+ *     core    when n >= thr, thr = max(1, (uint64)ceil(S * min_freq)) computed in doubles exactly so (skx_array_curve's rule at t = S)
+ *     variant when at least two bases have c[b] > 0
+ * Per sample s six counts over the rows; a cell of s counts into
+ *     kmers            when it is present                                   (equals skx_array_sample_kmers)
+ *     ambiguous        when it is present and popcount(code) >= 2
+ *     singletons       when it is present and n == 1
+ *     core_present     when it is present and the row is core
+ *     private_alleles  when it is unambiguous with base b, c[b] == 1 and unamb >= 2   (another sample carries a different plain base there)
+ *     minor_alleles    when it is unambiguous, the row is core and its base != major
+ * For the whole array: rows = U, rows_present (n >= 1), core_rows, core_variant_rows (core and variant), threshold = thr; the last three counts
+ * equal skx_array_curve's pan, core and core_variant at t = S for any order.
+ * samples: the caller's S records; info may be NULL.  `a` keeps its content (an array held as pieces or lazily is materialised first); both key
+ * widths are taken, and so is an array without split k-mers: nothing here needs keys.  SKX_EINVAL with a message that begins "qc:" for NULL
+ * arguments, NaN or min_freq outside [0, 1], a cell outside the alphabet; SKX_EUNSUP with the same beginning above 65 535 samples (the per-row
+ * counters are 16 bits), for 2^32 rows or more, and for an array that holds only a part of its samples (skx_array_set_total_samples: a rank's
+ * share of a collection spread over several devices).  U == 0: SKX_OK, zeros, threshold still set.  All results are sums of integers: the same bytes whatever the order of
+ * arrival.
+ * Two launches.  The first reads the matrix once, a lane 16 rows, and leaves a 16-bit descriptor per row (present, singleton, core, variant, the
+ * bases with c == 1 where unamb >= 2, the major base one-hot); the second runs over (SKX_QC_TILE_ROWS rows, SKX_QC_SAMPLES samples) units,
+ * classifies each cell against its row's descriptor and adds each unit's sums to the samples' counters.  Device memory beside the array:
+ * 2 bytes a row (rounded up to SKX_QC_TILE_ROWS), 48 bytes a sample, 28 bytes of totals. */
+enum { SKX_QC_TILE_ROWS = 4096, SKX_QC_SAMPLES = 64 };   /* the shape of the second kernel as built */
+typedef struct { uint64_t kmers, ambiguous, singletons, core_present, private_alleles, minor_alleles; } skx_qc_sample;
+typedef struct { uint64_t rows, rows_present, core_rows, core_variant_rows, threshold; } skx_qc_info;
+int  skx_array_sample_qc(skx_array *a, double min_freq, skx_qc_sample *samples, skx_qc_info *info);
 /* the `k` a .skf file states in its first fields, without loading it (0: not found there, or the file cannot be read): lets a caller that
  * would try 64-bit keys first and 128-bit keys next (lib.rs:635-661) go to the right width at once */
 int  skx_skf_peek_k(const char *path);

@@ -96,6 +96,29 @@ int skh_screen_text(int which, uint64_t n_records, const skx_screen_record *reco
  * and, with matrix != 0, <PREFIX>.screen.matrix.tsv are written as skh_screen_text forms them.  The refusals are skx_array_screen's.
  * Phases: screen.load / screen.counts (inside it screen.read_panel, screen.windows, screen.lookup, screen.kernel) / screen.text. */
 int skh_screen(skx_ctx *ctx, const char *skf_file, const char *panel_fasta, const char *out_prefix, double min_cover, double min_identity, int matrix);
+/* the three texts of `ska qc` from what skx_array_sample_qc returns (host only; the counts are defined in include/skx.h, the rule and the texts
+ * restated in tests/qc_model.py).  names: the array's n_samples sample names; mad: the M of the rule.
+ * Six metrics per sample: kmers, ambiguous, singletons, core_missing = core_rows - core_present (0 where a made-up core_present is the larger),
+ * private_alleles, minor_alleles.  The flag rule, in integers and one double product: for a metric with values x[0..S), med = place (S - 1) / 2
+ * of the sorted values, mad = the same place of the sorted |x - med|, d = max(mad, 1); a sample is high when x > med and (double)(x - med) >
+ * M * (double)d, and low symmetrically.  kmers is flagged on both sides (low_kmers, high_kmers), the other five on the high side under their
+ * own names.  S = 1 has no flags (x = med); at S = 2 med is the smaller value and mad 0, so the larger one is high once it is more than M above.
+ * SKH_QC_SAMPLES  <PREFIX>.qc.tsv: header "sample\tkmers\tambiguous\tsingletons\tcore_present\tcore_missing\tprivate_alleles\tminor_alleles\t
+ *                 flags", then a line per sample in the array's order; flags in the order low_kmers, high_kmers, ambiguous, singletons,
+ *                 core_missing, private_alleles, minor_alleles, comma separated, or "-".
+ * SKH_QC_SUMMARY  <PREFIX>.qc.summary.tsv: the lines "samples", "rows", "rows_present", "core_rows", "core_variant_rows", "threshold", each
+ *                 with its value behind a tab; the line "metric\tmin\tmedian\tmax\tmad\tflagged"; a line per metric in the order above
+ *                 (flagged = the samples flagged through it; all zeros without samples).
+ * SKH_QC_FLAGGED  <PREFIX>.qc.flagged.txt: the names with at least one flag, one per line, in the array's order: what `ska delete -f` reads.
+ * SKX_EINVAL for NULL arguments, another `which`, a negative or NaN mad.  *buf is malloc'd (skx_free). */
+enum { SKH_QC_SAMPLES = 0, SKH_QC_SUMMARY = 1, SKH_QC_FLAGGED = 2 };
+int skh_qc_text(int which, const skx_qc_sample *samples, const char *const *names, uint64_t n_samples, const skx_qc_info *info, double mad,
+                char **buf, uint64_t *len);
+/* `ska qc <SKF_FILE> -o PREFIX [--min-freq F] [--mad M]` (no counterpart in the reference): the file is loaded once, unfiltered
+ * (skh_load_array), one call of skx_array_sample_qc counts, and the three files are written as skh_qc_text forms them (the flagged list always,
+ * empty when nobody is flagged).  SKX_EINVAL for NULL arguments, min_freq outside [0, 1] and a negative or NaN mad before anything is loaded;
+ * otherwise the refusals are skx_array_sample_qc's.  Phases: qc.load / qc.kernels / qc.text. */
+int skh_qc(skx_ctx *ctx, const char *skf_file, const char *out_prefix, double min_freq, double mad);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

@@ -137,6 +137,11 @@ const std::vector<Cmd> &commands()
           {"--min-cover", "<C>", "Smallest fraction of a record's split k-mers a sample must have, 0 to 1 [default: 0.9]"},
           {"--min-identity", "<I>", "Smallest fraction of the split k-mers found whose middle base must be the record's, 0 to 1 [default: 0]"},
           {"--matrix", "", "Also write <OUTPUT>.screen.matrix.tsv: records by samples, 1 where the pair passes and 0 where it does not"}}},
+        {"qc", "(MI355X engine) Count per sample what tells a sample that should not be in the file, and flag the outliers", "ska qc [OPTIONS] -o <OUTPUT> <SKF_FILE>",
+         {{"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on"}},
+         {{"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.qc.tsv (per sample: split k-mers, ambiguous bases, singletons, core k-mers present and missing, private and minor alleles, flags), <OUTPUT>.qc.summary.tsv and <OUTPUT>.qc.flagged.txt (the flagged names, as `ska delete -f` reads them)"},
+          {"--min-freq", "<MIN_FREQ>", "Minimum fraction of the samples a core k-mer has to appear in [default: 0.9]"},
+          {"--mad", "<M>", "Flag a sample whose count lies more than M median absolute deviations from the median [default: 5]"}}},
     };
     return C;
 }

@@ -28,6 +28,10 @@ MARKER_INFO_DT = np.dtype([("presence", "<u8"), ("allele", "<u8")])             
 MARKER_PRESENCE, MARKER_ALLELE = 1, 2
 CURVE_TILE_ROWS, CURVE_LDS_STEPS, CURVE_BATCH_ORDERS = 4096, 1024, 1024      # SKX_CURVE_* (include/skx.h): the shape of skx_array_curve's kernel
 SCREEN_TILE, SCREEN_SAMPLES = 1024, 256                                     # SKX_SCREEN_* (include/skx.h): the shape of skx_array_screen's kernel
+QC_TILE_ROWS, QC_SAMPLES = 4096, 64                                          # SKX_QC_* (include/skx.h): the shape of skx_array_sample_qc's second kernel
+QC_SAMPLE_DT = np.dtype([(f, "<u8") for f in ("kmers", "ambiguous", "singletons", "core_present", "private_alleles", "minor_alleles")])      # skx_qc_sample
+QC_INFO_DT = np.dtype([(f, "<u8") for f in ("rows", "rows_present", "core_rows", "core_variant_rows", "threshold")])                           # skx_qc_info
+QC_SAMPLES_TEXT, QC_SUMMARY_TEXT, QC_FLAGGED_TEXT = 0, 1, 2                     # SKH_QC_* (include/skx_host.h)
 SCREEN_RECORD_DT = np.dtype([("length", "<u8"), ("windows", "<u8"), ("rows_hit", "<u8")])      # skx_screen_record
 SCREEN_CELL_DT = np.dtype([("found", "<u4"), ("match", "<u4"), ("ambig", "<u4")])              # skx_screen_cell
 SCREEN_PAIRS, SCREEN_SUMMARY, SCREEN_MATRIX = 0, 1, 2                       # SKH_SCREEN_* (include/skx_host.h)
@@ -145,6 +149,7 @@ skx_array_group_markers skh_markers skh_key_arms
 skx_array_pair_sites skh_distance_sites
 skx_array_curve skh_curve skh_curve_orders skh_curve_tsv
 skx_array_screen skh_screen skh_screen_text
+skx_array_sample_qc skh_qc skh_qc_text
 skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
@@ -207,6 +212,9 @@ def load_library():
     lib.skx_array_screen.argtypes = [vp, cp, C.POINTER(u64), pp, pp, pp]
     lib.skh_screen_text.argtypes = [i, u64, vp, vp, vp, C.POINTER(cp), u64, d, d, pp, C.POINTER(u64)]
     lib.skh_screen.argtypes = [vp, cp, cp, cp, d, d, i]
+    lib.skx_array_sample_qc.argtypes = [vp, d, vp, vp]
+    lib.skh_qc_text.argtypes = [i, vp, C.POINTER(cp), u64, vp, d, pp, C.POINTER(u64)]
+    lib.skh_qc.argtypes = [vp, cp, cp, d, d]
     lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
     lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
@@ -362,6 +370,18 @@ def screen_text(which, ids, records, cells, names, min_cover=0.9, min_identity=0
     p, n = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_screen_text(int(which), len(rec), _np_ptr(rec), blob, _np_ptr(cel), nm, len(names), float(min_cover), float(min_identity),
                                 C.byref(p), C.byref(n)))
+    return _take(p, n).decode()
+
+
+def qc_text(which, samples, names, info, mad=5.0):
+    """skh_qc_text: one of the three texts of `ska qc` (QC_SAMPLES_TEXT, QC_SUMMARY_TEXT, QC_FLAGGED_TEXT) from what Array.sample_qc returns
+    (host only)"""
+    load_library()
+    rec = np.ascontiguousarray(samples, QC_SAMPLE_DT).reshape(len(names))
+    inf = np.ascontiguousarray(info, QC_INFO_DT).reshape(1)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_qc_text(int(which), _np_ptr(rec), nm, len(names), _np_ptr(inf), float(mad), C.byref(p), C.byref(n)))
     return _take(p, n).decode()
 
 
@@ -611,6 +631,10 @@ class Context:
         """`ska curve <skf> -o PREFIX` (skh_curve): PREFIX.curve.tsv and, with all_permutations or an order file, PREFIX.curve.permutations.tsv"""
         _check(_lib.skh_curve(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), int(permutations), int(seed), float(min_freq),
                               None if order_file is None else os.fsencode(order_file), int(all_permutations)))
+
+    def qc(self, skf_file, out_prefix, min_freq=0.9, mad=5.0):
+        """`ska qc <skf> -o PREFIX` (skh_qc): PREFIX.qc.tsv, PREFIX.qc.summary.tsv and PREFIX.qc.flagged.txt"""
+        _check(_lib.skh_qc(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), float(min_freq), float(mad)))
 
     def screen(self, skf_file, panel, out_prefix, min_cover=0.9, min_identity=0.0, matrix=False):
         """`ska screen <skf> <panel> -o PREFIX` (skh_screen): PREFIX.screen.tsv, PREFIX.screen.summary.tsv and, with matrix, PREFIX.screen.matrix.tsv"""
@@ -1159,6 +1183,14 @@ class Array:
         counts = np.zeros((o.shape[0], o.shape[1], 4), np.uint64)
         _check(_lib.skx_array_curve(self.h, _np_ptr(o), o.shape[0], float(min_freq), _np_ptr(counts)))
         return counts
+
+    def sample_qc(self, min_freq=0.9):
+        """skx_array_sample_qc: six counts per sample that depend on their rows' statistics, this array left as it is
+        -> (QC_SAMPLE_DT [S], the array's totals as a QC_INFO_DT record)"""
+        rec = np.zeros(max(self.nsamples, 1), QC_SAMPLE_DT)
+        info = np.zeros(1, QC_INFO_DT)
+        _check(_lib.skx_array_sample_qc(self.h, float(min_freq), _np_ptr(rec), _np_ptr(info)))
+        return rec[:self.nsamples], info[0]
 
     def screen(self, path):
         """skx_array_screen: per (record, sample) of the FASTA panel at `path` the hit windows' cells that are present, equal the record's base
