@@ -26,7 +26,10 @@
 //     for unseen rows here;
 //   * what the cells add up to per row (present, unambiguous, code set: merge_ska_array.rs:139-186) is counted from the finished pieces by
 //     pieces_stats_kernel, nibble-parallel and without atomics; a sample's k-mer count, when asked for, by pieces_cells_kernel;
-//   * when the last sample of a round is in, the table is emitted in key order: the block's row keys and perm (rank -> row of the block).
+//   * when the last sample of a round is in, the table is emitted in key order: the block's row keys and perm (rank -> row of the block);
+//   * two tiers (append_kernel<false, HI, true>, where the host's two_tier_plan takes the split one step coarser): the block has twice the
+//     rows and a region half the readers; the LDS table closes at a meeting of the waves and the rows first met after that live in a table
+//     in global memory that only this workgroup touches -- a thousand related samples look those rows up a handful of times.
 // Measurement builds: -DSKX_AP_PROF (cycle stamps and counters per phase), -DAP_X_NOBATCH / _NOFILTER / _NORECORD / _NOPROBE / _FAKE4 (the kernel with
 // one part left out: what showed that loads + filter + queues are 6.8 of its 24 ms; results are wrong by construction) -- tools/mkvariant.sh.
 #include "skx_device.h"
@@ -122,29 +125,44 @@ __device__ static inline uint32_t ap_mbcnt(unsigned long long b)
 // wave's vector-memory counter -- that is, for the chunk of words on its way -- before and after each
 typedef volatile uint32_t __attribute__((address_space(3))) *lds_vol_t;
 __device__ static inline lds_vol_t lds_vol(void *p) { return (lds_vol_t)(__attribute__((address_space(3))) void *)p; }
-// ctl words: 0 ranks handed out, 1 failure, 8..24 scan scratch
-constexpr int CTL_NROWS = 0, CTL_FAIL = 1, CTL_TMP = 8, CTL_WORDS = 32;
+// ctl words: 0 ranks handed out, 1 failure, 2 the LDS tier is closed, 3 its rows when it closed, 4 the meeting that closed it, 8..24 scan scratch
+constexpr int CTL_NROWS = 0, CTL_FAIL = 1, CTL_CLOSED = 2, CTL_NLDS = 3, CTL_CLOSE_IT = 4, CTL_TMP = 8, CTL_WORDS = 32;
+constexpr uint32_t T2_TOTAL = APPEND_T2_SLOTS + APPEND_T2_PAD, T2_SHIFT = 32u - 14u;      // the second tier: home slot = the key's top 14 bits, monotone like the LDS table's
+static_assert(APPEND_T2_SLOTS == 1u << 14, "T2_SHIFT");
 
-static inline size_t append_lds_bytes(uint32_t nslots, uint32_t cap, bool count_only)
+// At 8 192 slots and one tier: 74 304 (table + bytes) + 40 960 (queues) + 128 + 16 x 3 008 (row buffers of 6 016 ranks) = 163 520 of the
+// 163 584 allowed.  Two tiers: row buffers of 5 760 ranks are 16 x 128 bytes less, which is the sixteen lists of APPEND_TT_LIST dwords.
+size_t append_lds_bytes(uint32_t nslots, uint32_t rb_ranks, bool count_only, bool two_tier)
 {
     size_t b = (size_t)(nslots + AP_PAD) * 8 + (size_t)(nslots + AP_PAD) + (size_t)AP_WAVES * (AP_Q + AP_SQ) * 8 + CTL_WORDS * 4;      // (AP_PAD is a multiple of 16)
-    if (!count_only) b += (size_t)AP_WAVES * (cap / 8) * 4;
+    if (!count_only) b += (size_t)AP_WAVES * (rb_ranks / 8) * 4;
+    if (two_tier) b += (size_t)AP_WAVES * APPEND_TT_LIST * 4;
     return b;
 }
 
 // HI: at least 32 hash bits below the block bits (rem >= 32): the table is addressed by their top 32 and the part bits of a word lie in its
 // upper half -- 32-bit operations throughout.  !HI (short k-mers, small inputs): the same steps on left-aligned fields.
-template <bool COUNT_ONLY, bool HI>
+// TT: two tiers.  The LDS table takes rows until it is CLOSED, which happens only between the two barriers of a meeting of the workgroup's
+// waves (thread 0, once CTL_NROWS has reached a.lds_close) or before the round's first barrier (a.lds_close = 0): every wave sees the same
+// state from one meeting to the next, so a key is never in both tiers -- while the table is open nothing looks at tier 2, and once it is
+// closed nothing is inserted into it: a word that the full probe sequence does not find there is looked up, or inserted, in the workgroup's
+// table in global memory (same entry, same claim protocol, ranks from the same CTL_NROWS).  Ranks beyond the row buffer (a.rb_ranks) can only
+// be tier 2's; their cells wait in the wave's list and are OR-ed into the sample's piece in memory when the piece has been written.
+template <bool COUNT_ONLY, bool HI, bool TT = false>
 __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
 {
+    static_assert(!(COUNT_ONLY && TT), "the count-only form has one tier");
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const uint32_t total_slots = a.nslots + AP_PAD;
-    const uint32_t cap = a.cap, rbw = cap / 8;                       // ranks per block; dwords of one row buffer
+    const uint32_t cap = a.cap, rbcap = TT ? a.rb_ranks : cap, rbw = rbcap / 8;      // ranks per block; ranks and dwords of one row buffer
     unsigned char *s_fp = s_raw;                                     // [total_slots] a byte of every slot's key (0: empty), what a look-up reads first -- at LDS address 0: a slot's byte is at the slot's number
     unsigned long long *s_tab = reinterpret_cast<unsigned long long *>(s_raw + total_slots);      // [total_slots] (total_slots is a multiple of 16)
-    unsigned long long *s_q = s_tab + total_slots;                   // [AP_WAVES][AP_Q kept words + AP_SQ words for the insert loop]
-    uint32_t *s_ctl = reinterpret_cast<uint32_t *>(s_q + (size_t)AP_WAVES * (AP_Q + AP_SQ));
-    uint32_t *s_rb = s_ctl + CTL_WORDS;                              // [AP_WAVES][rbw] 4-bit base sets by rank, one buffer per wave
+    // the control words: between the queues and the row buffers; TT: in front of the queues, so that queues, row buffers and lists are one
+    // stretch of 43 008 + 8 rbcap bytes for the emit to take when the samples are in
+    uint32_t *s_ctl = reinterpret_cast<uint32_t *>(s_tab + total_slots + (TT ? 0 : (size_t)AP_WAVES * (AP_Q + AP_SQ)));
+    unsigned long long *s_q = TT ? reinterpret_cast<unsigned long long *>(s_ctl + CTL_WORDS) : s_tab + total_slots;      // [AP_WAVES][AP_Q kept words + AP_SQ words for the insert loop]
+    uint32_t *s_rb = TT ? reinterpret_cast<uint32_t *>(s_q + (size_t)AP_WAVES * (AP_Q + AP_SQ)) : s_ctl + CTL_WORDS;      // [AP_WAVES][rbw] 4-bit base sets by rank, one buffer per wave
+    uint32_t *s_list = s_rb + (size_t)AP_WAVES * rbw;                // TT: [AP_WAVES][APPEND_TT_LIST] cells of ranks beyond the row buffer: rank << 4 | base set
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int S = a.n_samples;
@@ -166,6 +184,8 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
     uint8_t *piece0 = nullptr;
     unsigned long long *q = s_q + (size_t)wv * (AP_Q + AP_SQ), *sq = q + AP_Q;      // kept words ; words for the insert loop
     uint32_t *rb = s_rb + (size_t)wv * rbw;
+    unsigned long long *const t2 = TT ? a.t2 + (size_t)blockIdx.x * T2_TOTAL : nullptr;      // the workgroup's second tier
+    uint32_t *const lst = s_list + (size_t)wv * APPEND_TT_LIST;
     for (uint32_t rnd = 0; rnd < a.rounds; rnd++) {
     if (xmap) {
         const uint32_t xcd = blockIdx.x & 7u, ls = blockIdx.x >> 3, gpr = (G >> 3) >> shA;      // groups of A workgroups per XCD
@@ -178,12 +198,14 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
     for (uint32_t i = tid; i < total_slots; i += AP_THREADS) s_tab[i] = 0ull;
     for (uint32_t i = tid; i < total_slots / 4u; i += AP_THREADS) reinterpret_cast<uint32_t *>(s_fp)[i] = 0u;
     if (!COUNT_ONLY) for (uint32_t i = tid; i < AP_WAVES * rbw; i += AP_THREADS) s_rb[i] = 0u;
-    if (tid < CTL_WORDS) s_ctl[tid] = 0u;
+    if (tid < CTL_WORDS) s_ctl[tid] = TT && tid == CTL_CLOSED && a.lds_close == 0u ? 1u : 0u;
+    if (TT) for (uint32_t i = tid; i < T2_TOTAL; i += AP_THREADS) __hip_atomic_store(&t2[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (complete at the barrier below)
     if (tid == 0 && (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s_fp != 0u) atomicOr(a.overflow, 4);      // (a look-up takes a slot's number for the address of its byte)
     if (xmap && A > 1u && a.bar && tid == 0) {                       // the region's readers start together (bounded: late ones are not waited for for ever)
         atomicAdd(&a.bar[region], 1);
         for (int it = 0; it < (1 << 18) && __hip_atomic_load(&a.bar[region], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (int)A; it++) __builtin_amdgcn_s_sleep(8);
     }
+    if (TT) __threadfence();                                         // (tier 2's zeros are in memory before any wave of the workgroup probes it)
     __syncthreads();
 
     // region offsets and fills are read through the constant address space: scalar loads
@@ -196,6 +218,10 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
     // step's two write addresses and the new end are two scalar shift-adds)
     const uint32_t qbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned long long *)q, qfull = qbase + 128u * 8u;
     uint32_t qw = qbase, nsq = 0;
+    // TT, wave-uniform: the sample in hand, the cells in the wave's list, and the 16-byte groups of the sample's piece beyond the row buffer
+    // that a flush inside the sample has zero-filled already (0: none)
+    int s_cur = wv;
+    uint32_t nl = 0, filled = 0;
     AP_PROF_START;
     __builtin_amdgcn_s_setprio(AP_PRIO_STREAM);
 
@@ -219,12 +245,31 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
         const uint32_t rank = rank1 - 1u;
         atomicOr(&rb[rank >> 3], m4 << ((rank & 7u) * 4u));
     };
+    // TT: the wave's listed cells into the piece of the sample in hand, of which n ranks exist by now (every listed rank among them: a rank
+    // is handed out before it is listed).  The piece's bytes beyond the row buffer are zero-filled as far as n reaches (16 bytes = 32 ranks at
+    // a time, like every writer and reader of pieces; `filled` remembers how far for the next call), the stores are waited for -- with them
+    // the chunk on its way: vmcnt(0) -- and the cells are OR-ed in with 32-bit atomics.  No other wave writes this piece.
+    auto list_out = [&](uint32_t n, uint8_t *dst) {
+        const uint32_t g0 = filled > rbcap / 32u ? filled : rbcap / 32u, g1 = (n + 31u) / 32u;
+        for (uint32_t g = g0 + (uint32_t)lane; g < g1; g += 64u) *reinterpret_cast<uint4 *>(dst + (size_t)g * 16u) = make_uint4(0u, 0u, 0u, 0u);
+        if (g1 > g0) filled = g1;
+        if (nl) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if ((uint32_t)lane < nl) {
+                const uint32_t e = lst[lane], rank = e >> 4;
+                atomicOr(reinterpret_cast<uint32_t *>(dst) + (rank >> 3), (e & 15u) << ((rank & 7u) * 4u));
+            }
+            nl = 0;
+        }
+    };
     // up to 64 words of the insert queue: the full probe sequence, new keys inserted
     auto slow_batch = [&]() {
         __builtin_amdgcn_s_setprio(AP_PRIO_INSERT);
         const uint32_t take = nsq < 64u ? nsq : 64u;
         nsq -= take;
         if (lane == 0) { AP_COUNT(8, 1); AP_COUNT(9, take); }
+        const bool closed = TT && lds_vol(&s_ctl[CTL_CLOSED])[0] != 0u;      // (changes at the waves' meetings only: never inside a batch)
+        uint32_t far_cell = 0;                                                // TT: (rank << 4 | base set) + 1 of a cell beyond the row buffer
         if ((uint32_t)lane < take) {
             const unsigned long long w = sq[nsq + lane];
             const uint32_t wlo = (uint32_t)w, whi = (uint32_t)(w >> 32);
@@ -248,14 +293,16 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
                 if (!(m0 | m1 | m2 | m3)) {
                     // not in these four: into the first empty one, if there is one (a lost race for it: the same four again)
                     at = e0 == 0ull ? 0u : e1 == 0ull ? 1u : e2 == 0ull ? 2u : e3 == 0ull ? 3u : 4u;
-                    if (at < 4u) won = atomicCAS(&s_tab[t + at], 0ull, keyE | AP_RANK_MASK) == 0ull;
+                    if (TT && closed) { if (at < 4u) break; }                 // (an empty slot ends the key's probe sequence: it is not in this tier)
+                    else if (at < 4u) won = atomicCAS(&s_tab[t + at], 0ull, keyE | AP_RANK_MASK) == 0ull;
                 }
                 if (won) {
                     const uint32_t mine = atomicAdd(&s_ctl[CTL_NROWS], 1u) + 1u;
-                    if (mine > (COUNT_ONLY ? AP_RANK_MASK - 1u : cap)) s_ctl[CTL_FAIL] = 1u;
-                    lds_vol(&s_tab[t + at])[0] = kl | (mine < AP_RANK_MASK ? mine : AP_RANK_MASK - 1u);
+                    if (mine > (COUNT_ONLY ? AP_RANK_MASK - 1u : rbcap)) s_ctl[CTL_FAIL] = 1u;      // (TT: the LDS tier filled before a meeting could close it)
+                    if (TT) lds_vol(&s_tab[t + at])[0] = kl | (mine <= rbcap ? mine : rbcap);      // (a failed block's look-ups stay inside the row buffers)
+                    else lds_vol(&s_tab[t + at])[0] = kl | (mine < AP_RANK_MASK ? mine : AP_RANK_MASK - 1u);
                     s_fp[t + at] = (unsigned char)key_fp(kh, kl);
-                    rank1 = mine;
+                    rank1 = TT && mine > rbcap ? rbcap : mine;
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (m0 | m1 | m2 | m3) {
@@ -269,9 +316,56 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
                 if (won) break;
                 if (at == 4u) t += 4u;
             }
+            if (TT && closed && rank1 == 0) {
+                // Not in the closed LDS tier: the workgroup's table in global memory, one slot per step from the key's home (monotone in the key,
+                // no wrap, at most half full: runs are short).  Same entry and same protocol as above, in the same two statements -- the lane whose
+                // CAS wins takes the rank and stores it before any lane of the wave waits for one.  Every access is an atomic of agent scope: the
+                // sixteen waves meet in L2, not in a CU's vector cache.  The accesses join the chunk loads in the wave's vector-memory counter:
+                // the compiler waits for each result with the count of ITS operations in flight, which the loads (older, returned in order) only
+                // lengthen -- in effect vmcnt(0) before a tier-2 result is used -- and a rank's store still on its way when the chunk loop goes on
+                // makes that loop's vmcnt(7) wait longer, never shorter.
+                for (uint32_t t = kh >> T2_SHIFT; t < T2_TOTAL; t++) {
+                    // (the CAS is the read as well: one round trip to L2 per step -- it returns the entry that is there, and most words that
+                    // come here are new rows)
+                    const unsigned long long e = atomicCAS(&t2[t], 0ull, keyE | AP_RANK_MASK);
+                    const bool won = e == 0ull;
+                    if (won) {
+                        const uint32_t mine = atomicAdd(&s_ctl[CTL_NROWS], 1u) + 1u;
+                        if (mine > cap) s_ctl[CTL_FAIL] = 1u;
+                        __hip_atomic_store(&t2[t], keyE | (mine <= cap ? mine : cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        rank1 = mine;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    if (!won && (e ^ keyE) - 1ull < AP_RANK_MASK) {
+                        uint32_t r = (uint32_t)e & AP_RANK_MASK;
+                        for (int it = 0; it < (1 << 16) && r == AP_RANK_MASK; it++) r = (uint32_t)__hip_atomic_load(&t2[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & AP_RANK_MASK;
+                        if (r == AP_RANK_MASK) r = 0;
+                        rank1 = r;
+                        break;
+                    }
+                    if (won) break;
+                }
+            }
             if (rank1 > cap && !COUNT_ONLY) rank1 = 0;
             if (rank1 == 0) s_ctl[CTL_FAIL] = 1u;
-            else if (!COUNT_ONLY) record(rank1, wlo & 15u);
+            else if (!COUNT_ONLY) {
+                if (!TT || rank1 <= rbcap) record(rank1, wlo & 15u);
+                else far_cell = (((rank1 - 1u) << 4) | (wlo & 15u)) + 1u;
+            }
+        }
+        if (TT) {
+            // cells beyond the row buffer into the wave's list; a full list leaves for the piece first (its ranks exist: list_out)
+            for (unsigned long long pend = __ballot(far_cell != 0u); pend; pend = __ballot(far_cell != 0u)) {
+                if (nl == APPEND_TT_LIST) {
+                    uint32_t n = *lds_vol(&s_ctl[CTL_NROWS]);
+                    n = __builtin_amdgcn_readfirstlane(n);
+                    list_out(n < cap ? n : cap, piece0 + (uint64_t)s_cur * (cap / 2));
+                    if (lane == 0 && a.tt_stat) atomicAdd(&a.tt_stat[4], 1ull);
+                }
+                const uint32_t room = APPEND_TT_LIST - nl, idx = ap_mbcnt(pend), cnt = (uint32_t)__popcll(pend);
+                if (far_cell && idx < room) { lst[nl + idx] = far_cell - 1u; far_cell = 0u; }
+                nl += cnt < room ? cnt : room;
+            }
         }
         __builtin_amdgcn_s_setprio(AP_PRIO_STREAM);
     };
@@ -498,17 +592,21 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
                     n = __builtin_amdgcn_readfirstlane(n);
                     if (n > cap) n = cap;
                     uint8_t *dst = piece0 + (uint64_t)s * (cap / 2);
-                    for (uint32_t v = lane; v * 32u < n; v += 64u) {
+                    const uint32_t nb = TT && n > rbcap ? rbcap : n;       // the ranks the row buffer covers
+                    for (uint32_t v = lane; v * 32u < nb; v += 64u) {
                         uint4 *src = reinterpret_cast<uint4 *>(rb) + v;
                         const uint4 x = *src;
                         *reinterpret_cast<uint4 *>(dst + v * 16u) = x;
                         *src = make_uint4(0u, 0u, 0u, 0u);
                     }
+                    // TT: then the zeros from the row buffer's end to plen, the wait for these stores, the listed cells (list_out, in this order)
+                    if (TT) { list_out(n, dst); filled = 0; }
                     if (lane == 0) a.plen[j * (uint64_t)S + s] = (uint16_t)n;
                 }
                 AP_PROF(4);
                 if (!more) break;
                 s += AP_WAVES; c = 0; off_c = off_n; cnt_c = cnt_n;
+                s_cur = s;
                 // The readers of a region meet again every AP_RESYNC samples of a wave: the workgroup's waves at a barrier, then the region's A
                 // workgroups through a counter (bounded).  Readers that drift apart fetch a region's lines up to A times: without the meetings
                 // FETCH_SIZE x 2 is 54.5 GB for the 40 GB of words of 1 000 x 5 Mbp, with one every 16 samples 43.8 GB -- for 0.15 ms of the pass's
@@ -516,13 +614,21 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
                 // take issue slots, r05p).  0 = none.
                 if (AP_RESYNC > 0) {
                     const int it = (s - wv) / AP_WAVES;                       // the wave's sample number (the same count in every wave up to S / 16)
-                    if (xmap && A > 1u && a.bar && it % (AP_RESYNC > 0 ? AP_RESYNC : 1) == 0 && it <= (S - AP_WAVES) / AP_WAVES) {
+                    // TT: the waves meet whatever A is (a.resync samples apart), because a meeting is where the LDS tier closes: thread 0,
+                    // between the two barriers, once the rows have reached a.lds_close -- no wave is inside a batch then, and all see the
+                    // flag from the second barrier on.  (it <= (S - 16) / 16: every one of the sixteen waves has a sample number `it`.)
+                    const int rs = TT ? (int)a.resync : (AP_RESYNC > 0 ? AP_RESYNC : 1);
+                    const bool readers_meet = xmap && A > 1u && a.bar;
+                    if ((TT || readers_meet) && it % rs == 0 && it <= (S - AP_WAVES) / AP_WAVES) {
                         __syncthreads();
                         if (tid == 0) {
-                            int *ctr = a.bar + (1 << a.logB) + region;
-                            const int want = (int)A * (it / (AP_RESYNC > 0 ? AP_RESYNC : 1));
-                            atomicAdd(ctr, 1);
-                            for (int spin = 0; spin < (1 << 16) && __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want; spin++) __builtin_amdgcn_s_sleep(4);
+                            if (TT && !s_ctl[CTL_CLOSED] && s_ctl[CTL_NROWS] >= a.lds_close) { s_ctl[CTL_CLOSED] = 1u; s_ctl[CTL_NLDS] = s_ctl[CTL_NROWS]; s_ctl[CTL_CLOSE_IT] = (uint32_t)it; }
+                            if (readers_meet) {
+                                int *ctr = a.bar + (1 << a.logB) + region;
+                                const int want = (int)A * (it / rs);
+                                atomicAdd(ctr, 1);
+                                for (int spin = 0; spin < (1 << 16) && __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want; spin++) __builtin_amdgcn_s_sleep(4);
+                            }
                         }
                         __syncthreads();
                     }
@@ -541,6 +647,94 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
         for (uint32_t i = tid; i < total_slots; i += AP_THREADS) c += s_tab[i] != 0ull;
         uint32_t tot; (void)ap_block_excl(c, s_tmp, &tot);
         if (tid == 0) { atomicAdd(&a.probe[0], (unsigned long long)tot); atomicMax(&a.probe[1], (unsigned long long)tot); }
+        continue;
+    }
+    if (TT) {
+        // Emit from both tiers.  Either table is monotone in the key, so each gives its entries in key order by the run sort below (a 64-bit
+        // entry compares as its key: the rank sits in the lowest bits and no two entries share a key): the LDS tier's go to the stretch the
+        // queues and row buffers have left (<= rbcap entries, then perm: 8 rbcap + 2 cap <= 43 008 + 8 rbcap bytes), tier 2's to the table's own
+        // bytes once it has been read (<= total_slots entries: more fail the block).  An entry's row is its place in its own list plus the
+        // entries of the other list below it (a binary search in LDS).  Measured against sorting everything in LDS: there is no room for that.
+        unsigned long long *s_l1 = s_q, *s_l2 = s_tab;
+        uint16_t *s_perm = reinterpret_cast<uint16_t *>(s_q + rbcap);
+        for (uint32_t i = tid; i < cap; i += AP_THREADS) s_perm[i] = 0xFFFFu;
+        const uint32_t per = (total_slots + AP_THREADS - 1) / AP_THREADS;
+        const uint32_t lo = tid * per < total_slots ? tid * per : total_slots, hi = lo + per < total_slots ? lo + per : total_slots;
+        uint32_t c = 0;
+        for (uint32_t i = lo; i < hi; i++) c += s_tab[i] != 0ull;
+        uint32_t n1;
+        uint32_t pos = ap_block_excl(c, s_tmp, &n1);
+        for (uint32_t i = lo; i < hi; i++) {
+            const unsigned long long e = s_tab[i];
+            if (!e) continue;
+            uint32_t gl = 0, lr = 0;
+            for (int64_t t = (int64_t)i - 1; t >= 0; t--) { const unsigned long long o = s_tab[t]; if (!o) break; gl += o > e; }
+            for (uint32_t t = i + 1; t < total_slots; t++) { const unsigned long long o = s_tab[t]; if (!o) break; lr += o < e; }
+            const uint32_t idx = pos - gl + lr;
+            pos++;
+            if (idx < rbcap) s_l1[idx] = e;
+        }
+        constexpr uint32_t per2 = (T2_TOTAL + AP_THREADS - 1) / AP_THREADS;
+        const uint32_t lo2 = tid * per2 < T2_TOTAL ? tid * per2 : T2_TOTAL, hi2 = lo2 + per2 < T2_TOTAL ? lo2 + per2 : T2_TOTAL;
+        auto t2_at = [&](uint32_t i) { return __hip_atomic_load(&t2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+        // (a thread's slots stay in registers -- every index below is a constant of the unrolled loops: a trip to L2 per neighbour of every
+        // entry made the emit some 50 us of a round)
+        unsigned long long v2[per2];
+#pragma unroll
+        for (uint32_t i = 0; i < per2; i++) v2[i] = lo2 + i < hi2 ? t2_at(lo2 + i) : 0ull;
+        c = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < per2; i++) c += v2[i] != 0ull;
+        uint32_t n2;
+        uint32_t pos2 = ap_block_excl(c, s_tmp, &n2);                 // (its barriers: the LDS table has been read by every thread)
+        const bool fits = n1 <= rbcap && n2 <= total_slots && n1 + n2 <= a.stride;
+        if (!fits) { if (tid == 0) atomicOr(a.overflow, 1); __syncthreads(); continue; }
+#pragma unroll
+        for (uint32_t i = 0; i < per2; i++) {
+            const unsigned long long e = v2[i];
+            if (e) {
+                uint32_t gl = 0, lr = 0;
+                bool open = true;                                      // the run reaches on (to the thread's first slot and beyond; to its last and beyond)
+#pragma unroll
+                for (uint32_t t = i; t-- > 0;) { open = open && v2[t] != 0ull; gl += open && v2[t] > e; }
+                if (open) for (int64_t t = (int64_t)lo2 - 1; t >= 0; t--) { const unsigned long long o = t2_at((uint32_t)t); if (!o) break; gl += o > e; }
+                open = true;
+#pragma unroll
+                for (uint32_t t = i + 1; t < per2; t++) { open = open && v2[t] != 0ull; lr += open && v2[t] < e; }
+                if (open && lo2 + per2 == hi2) for (uint32_t t = hi2; t < T2_TOTAL; t++) { const unsigned long long o = t2_at(t); if (!o) break; lr += o < e; }
+                s_l2[pos2 - gl + lr] = e;
+                pos2++;
+            }
+        }
+        __syncthreads();
+        uint64_t *slab = a.stage + j * (uint64_t)a.stride;
+        auto below = [&](const unsigned long long *v, uint32_t n, unsigned long long e) -> uint32_t {      // entries of v[0, n) below e
+            uint32_t l = 0, h = n;
+            while (l < h) { const uint32_t m = (l + h) >> 1; if (v[m] < e) l = m + 1; else h = m; }
+            return l;
+        };
+        auto place = [&](unsigned long long e, uint32_t idx) {
+            const uint32_t rank = ((uint32_t)e & AP_RANK_MASK) - 1u;
+            if (idx >= a.stride || rank >= cap) return;
+            uint64_t hl;
+            if (HI) hl = ((uint64_t)(uint32_t)(e >> 32) << lowb) | (uint64_t)((uint32_t)e >> AP_RANK_BITS);
+            else hl = rem == 0 ? 0ull : (uint64_t)((uint32_t)(e >> 32) >> (32 - rem));
+            slab[idx] = ((((uint64_t)j << rem) | hl) << 4) | 1ull;
+            s_perm[rank] = (uint16_t)idx;
+        };
+        for (uint32_t i = tid; i < n1; i += AP_THREADS) { const unsigned long long e = s_l1[i]; place(e, i + below(s_l2, n2, e)); }
+        for (uint32_t i = tid; i < n2; i += AP_THREADS) { const unsigned long long e = s_l2[i]; place(e, i + below(s_l1, n1, e)); }
+        __syncthreads();
+        uint16_t *pj = a.perm + j * (uint64_t)cap;
+        for (uint32_t i = tid; i < cap; i += AP_THREADS) pj[i] = s_perm[i];
+        if (tid == 0) {
+            a.ncnt[j] = n1 + n2; a.nrank[j] = nr < cap ? nr : cap;
+            if (a.tt_stat) {
+                if (s_ctl[CTL_CLOSED]) { atomicAdd(&a.tt_stat[0], 1ull); atomicAdd(&a.tt_stat[1], (unsigned long long)s_ctl[CTL_NLDS]); atomicMax(&a.tt_stat[3], (unsigned long long)s_ctl[CTL_CLOSE_IT]); }
+                atomicAdd(&a.tt_stat[2], (unsigned long long)n2);
+            }
+        }
+        __syncthreads();
         continue;
     }
     // emit in key order: row keys, rank -> row
@@ -582,8 +776,21 @@ __global__ __launch_bounds__(AP_THREADS) void append_kernel(AppendArgs a)
 template <bool COUNT_ONLY>
 static void launch_append_t(const AppendArgs &a, unsigned blocks, hipStream_t st)
 {
-    const size_t lds = append_lds_bytes(a.nslots, a.cap, COUNT_ONLY);
     const bool hi = a.bits - a.logQ >= 32;
+    if constexpr (!COUNT_ONLY) {
+        if (a.two_tier) {
+            const size_t lds = append_lds_bytes(a.nslots, a.rb_ranks, false, true);
+            if (hi) {
+                (void)hipFuncSetAttribute((const void *)append_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((append_kernel<false, true, true>), dim3(blocks), dim3(AP_THREADS), lds, st, a);
+            } else {
+                (void)hipFuncSetAttribute((const void *)append_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((append_kernel<false, false, true>), dim3(blocks), dim3(AP_THREADS), lds, st, a);
+            }
+            return;
+        }
+    }
+    const size_t lds = append_lds_bytes(a.nslots, a.cap, COUNT_ONLY, false);
     if (hi) {
         (void)hipFuncSetAttribute((const void *)append_kernel<COUNT_ONLY, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((append_kernel<COUNT_ONLY, true>), dim3(blocks), dim3(AP_THREADS), lds, st, a);
@@ -594,12 +801,15 @@ static void launch_append_t(const AppendArgs &a, unsigned blocks, hipStream_t st
 }
 // what the pass takes: hash bits below the block bits that leave room for a rank in a table entry; a table, sixteen row buffers and the
 // queues that fit the LDS
-bool append_ok(int bits, int logB, int logQ, uint32_t region_cap, uint32_t nslots, uint32_t cap)
+bool append_ok(int bits, int logB, int logQ, uint32_t region_cap, uint32_t nslots, uint32_t cap, uint32_t tt_rb_ranks)
 {
     const int rem = bits - logQ;
     (void)region_cap;
-    return logQ >= logB && rem >= 0 && rem <= 50 && cap % 128u == 0 && cap >= 128u && cap <= APPEND_MAX_CAP && nslots >= cap && (nslots & (nslots - 1u)) == 0u &&
-           append_lds_bytes(nslots, cap, false) <= 160u * 1024u - 256u;
+    if (!(logQ >= logB && rem >= 0 && rem <= 50 && cap % 128u == 0 && cap >= 128u && (nslots & (nslots - 1u)) == 0u)) return false;
+    if (tt_rb_ranks)                                                   // two tiers: the table holds what the row buffers cover, the block hands out more
+        return cap <= APPEND_MAX_RANKS && tt_rb_ranks % 128u == 0 && tt_rb_ranks >= 128u && tt_rb_ranks <= cap && tt_rb_ranks <= APPEND_TT_LDS_RANKS && nslots >= tt_rb_ranks &&
+               append_lds_bytes(nslots, tt_rb_ranks, false, true) <= 160u * 1024u - 256u;
+    return cap <= APPEND_MAX_CAP && nslots >= cap && append_lds_bytes(nslots, cap, false, false) <= 160u * 1024u - 256u;
 }
 void launch_append(const AppendArgs &a, uint32_t region_cap, hipStream_t st) { (void)region_cap; launch_append_t<false>(a, (1u << a.logQ) / a.rounds, st); }
 void launch_append_probe(const AppendArgs &a, uint32_t region_cap, unsigned blocks, hipStream_t st) { (void)region_cap; launch_append_t<true>(a, blocks, st); }
@@ -717,14 +927,20 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
     }
     const uint32_t nseen = (lim + 31u) / 32u * 32u < nr ? (lim + 31u) / 32u * 32u : nr;      // the ranks of the columns read
     // column groups of 64 and sample slices (staged only; per-rank stores keep a column per thread and one slice)
-    const uint32_t ncol = (lim + 31u) / 32u, ncg = ncol < 64u ? ncol : 64u;                   // columns read; the most that one group holds
+    // A staged workgroup has 256 columns -- 8 192 ranks -- at a time: a block of a two-tier append pass (up to 12 032 ranks) whose `lim` reaches
+    // beyond takes its columns in two turns, without sample slices (their exchange would overwrite the first turn's staged rows).
+    const uint32_t ncol_all = (lim + 31u) / 32u;
+    const uint32_t nturn = gridDim.y == 1 && ncol_all > 256u ? (ncol_all + 255u) / 256u : 1u;      // (staged or not: one workgroup has the block)
+    const uint16_t *pj = perm + j * (uint64_t)cap;
+    for (uint32_t turn = 0; turn < nturn; turn++) {
+    const uint32_t ncol = ncol_all - turn * 256u < 256u || !staged ? ncol_all - turn * 256u : 256u, ncg = ncol < 64u ? ncol : 64u;      // columns read this turn; the most that one group holds
     uint32_t G = 4, P = 1;
     if (staged && ncol) {
         G = (ncol + 63u) / 64u;
-        for (P = 4u / G; P > 1u && (P / 2u) * G * 36u * 4u * ncg > PS_STAGE * 6u; P >>= 1) { }      // (4 / G is 4, 2 or 1; the exchange: P / 2 x G areas)
+        for (P = nturn > 1u ? 1u : 4u / G; P > 1u && (P / 2u) * G * 36u * 4u * ncg > PS_STAGE * 6u; P >>= 1) { }      // (4 / G is 4, 2 or 1; the exchange: P / 2 x G areas)
     }
     const uint32_t grp = (uint32_t)wv % G, slice = (uint32_t)wv / G;
-    const uint32_t d = blockIdx.y * 256u + grp * 64u + (uint32_t)lane;            // 16-byte column: ranks 32 d .. 32 d + 31
+    const uint32_t d = (blockIdx.y + turn) * 256u + grp * 64u + (uint32_t)lane;   // 16-byte column: ranks 32 d .. 32 d + 31
     const uint4 *col = reinterpret_cast<const uint4 *>(pieces + j * (uint64_t)S * (cap / 2)) + d;
     const uint32_t step = cap / 32;                                   // 16-byte pieces from one sample's piece to the next
     bool mine = slice < P && d * 32u < lim;
@@ -809,11 +1025,10 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
         }
         if (slice) mine = false;
     }
-    if (staged) {
+    if (staged && turn == 0) {
         for (uint32_t p = threadIdx.x; p < nrows; p += 256) { s_pr[p] = 0; s_un[p] = 0; s_mk[p] = 0; }      // (a row without a rank here: no cell in these samples)
         __syncthreads();
     }
-    const uint16_t *pj = perm + j * (uint64_t)cap;
     if (mine) {
 #pragma unroll
         for (int w = 0; w < W; w++) {
@@ -843,10 +1058,11 @@ __global__ __launch_bounds__(256) void pieces_stats_kernel(const uint8_t *pieces
             }
         }
     }
+    }   // turns
     if (!staged) __threadfence();                                      // (the walk below reads what the ranks' threads stored)
     __syncthreads();
     // rows with an ambiguous cell: their code sets cell by cell, a wave per row, found by a walk over the workgroup's ranks (64 at a time)
-    const uint32_t rk0 = blockIdx.y * 256u * 8u * W, rk1 = rk0 + 256u * 8u * W < nseen ? rk0 + 256u * 8u * W : nseen;
+    const uint32_t rk0 = blockIdx.y * 256u * 8u * W, rk1 = rk0 + 256u * 8u * W < nseen && gridDim.y > 1 ? rk0 + 256u * 8u * W : nseen;
     for (uint32_t rb = rk0 + (uint32_t)wv * 64u; rb < rk1; rb += 256u) {
         const uint32_t rr = rb + (uint32_t)lane;
         uint32_t pp = 0xFFFFu; bool hit = false;
@@ -888,8 +1104,8 @@ struct StatsLaunch { unsigned gy; int direct; uint32_t stage; bool bounded() con
 StatsLaunch stats_launch(uint32_t cap)
 {
     static const int direct = knob("stats_direct") ? 1 : 0;           // (tests: the per-rank stores of blocks the stage does not hold)
-    // stage: <= 6 016 (12 032 with gy > 1, where nothing is staged): <= 36 KB
-    return {(cap / 32 + 255u) / 256u, direct, (cap + 63u) / 64u * 64u};
+    // stage: <= 6 016 rows, 36 KB; <= 12 032 rows of a two-tier pass's blocks, 72 KB, the columns in two turns; beyond that gy > 1 and nothing is staged
+    return {cap <= APPEND_MAX_RANKS ? 1u : (cap / 32 + 255u) / 256u, direct, (cap + 63u) / 64u * 64u};
 }
 }
 void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint16_t *perm, const uint32_t *nrank, const uint32_t *ncnt, const uint64_t *roff, uint32_t cap,
@@ -899,6 +1115,7 @@ void launch_pieces_stats(const uint8_t *pieces, const uint16_t *plen, const uint
     const StatsLaunch l = stats_launch(cap);
     if (!l.bounded()) min_count = 0;                                   // (per-rank stores fill no zeros: such a launch is never bounded)
     // (the stage's bytes take the cut's histogram first: (cap + 1) * 4 <= stage * 6 for every cap >= 2)
+    if ((size_t)l.stage * 6 > 48u * 1024u) (void)hipFuncSetAttribute((const void *)pieces_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)l.stage * 6));
     hipLaunchKernelGGL(pieces_stats_kernel, dim3((unsigned)n_blocks, l.gy), dim3(256), (size_t)l.stage * 6, st, pieces, plen, perm, nrank, ncnt, roff, cap, n_samples, present, unambig, mask, vcount,
                        l.direct, l.stage, min_count, tally);
 }
@@ -1082,8 +1299,11 @@ void launch_pieces_rows(const PiecesRowsArgs &a, uint32_t n_blocks, hipStream_t 
     if (!n_blocks || a.n_samples <= 0) return;
     PiecesRowsArgs b = a;
     // enough workgroups to fill the chip several times over, few enough that listing a block's columns is shared by many samples
+    // (the blocks of a two-tier append pass have twice the ranks to list and half the workgroups share a CU's LDS: half as many workgroups,
+    // so that a listing serves as many samples as it does at 6 016 ranks)
     int spw = a.n_samples;
-    while (spw > PR_WAVES * 4 && (uint64_t)n_blocks * ((a.n_samples + spw - 1) / spw) < 8192) spw = (spw + 1) / 2;
+    const uint64_t want = a.cap > APPEND_MAX_SLOTS ? 4096 : 8192;      // (1 000 x 5 Mbp, 2 048 blocks of 11 776 ranks: 2.38 ms aiming for 8 192, 2.10-2.12 for 4 096, 2.05 for 2 048)
+    while (spw > PR_WAVES * 4 && (uint64_t)n_blocks * ((a.n_samples + spw - 1) / spw) < want) spw = (spw + 1) / 2;
     b.samples_per_wg = spw;
     const unsigned gy = (unsigned)((a.n_samples + spw - 1) / spw);
     const size_t lds = (((size_t)a.cap + 16) * 2 + 15) / 16 * 16 + (size_t)PR_WAVES * (a.cap / 8 + 4) * 4;

@@ -199,6 +199,14 @@ void launch_union_side_wide(const DictView &d, int logN, u128 *stage, uint32_t s
 // sample, a *piece*: the sample's cells of the block as 4-bit base sets indexed by first-seen rank, plen[j * S + s] of them, at
 // pieces + (j * S + s) * (cap / 2).  perm[j * cap + rank] = row of the block (key order) or 0xFFFF; nrank[j] = ranks handed out.
 constexpr uint32_t APPEND_MAX_CAP = 6016, APPEND_MAX_SLOTS = 8192;    // what sixteen row buffers, the queues and the table leave of 160 KB
+// Two tiers (64-bit keys): a block hands out up to APPEND_MAX_RANKS ranks (the 14-bit rank field would allow 16 382 and the u16 plen / perm
+// more; 12 032 = 2 x 6 016 is what the piece kernels are launched for).  The rows met first -- up to APPEND_TT_LDS_RANKS of them, what a wave's
+// row buffer covers -- live in the LDS table; rows first met after the table was closed live in the workgroup's table in global memory
+// (APPEND_T2_SLOTS + APPEND_T2_PAD entries of 8 bytes: 128.5 KB a workgroup, 32 MB for 256 -- L2 and MALL, never HBM), and their cells
+// beyond the row buffer go through a wave's list of APPEND_TT_LIST (rank, base set) pairs.  6 016 - 5 760 = 256 ranks less a row buffer are
+// 128 bytes a wave: the list's 32 dwords.
+constexpr uint32_t APPEND_MAX_RANKS = 12032, APPEND_TT_LDS_RANKS = 5760, APPEND_TT_LIST = 32, APPEND_T2_SLOTS = 16384, APPEND_T2_PAD = 64;
+constexpr int APPEND_TT_STATS = 8;                                     // words of AppendArgs::tt_stat
 struct AppendArgs {
     const uint64_t *words; const uint64_t *off; const uint32_t *raw;      // regions as extract_kernel left them (off in words, raw = fill)
     int n_samples, logB, bits, logQ;
@@ -209,8 +217,16 @@ struct AppendArgs {
     int *overflow;                                                       // |= 1 table / ranks / slab full, |= 2 queue full
     uint32_t rounds = 1;                                                 // row blocks per workgroup: the launch has (1 << logQ) / rounds workgroups (launch_append)
     int *bar = nullptr;                                                  // [1 << logB] zeroed: where the readers of a region meet before a round
+    // two tiers (append_kernel only; all zero: one tier, the row buffers cover `cap`)
+    int two_tier = 0;
+    uint32_t rb_ranks = 0;                                               // ranks of a wave's row buffer = the most the LDS tier may hold (multiple of 128, <= cap)
+    uint32_t lds_close = 0;                                              // the LDS tier closes at the first meeting of the waves that finds this many rows (0: closed from the start)
+    uint32_t resync = 0;                                                 // samples of a wave between two meetings
+    unsigned long long *t2 = nullptr;                                    // [workgroups][APPEND_T2_SLOTS + APPEND_T2_PAD] the second tier (cleared by its workgroup)
+    unsigned long long *tt_stat = nullptr;                               // zeroed: [0] blocks that closed, [1] their LDS rows, [2] rows in tier 2, [3] the latest closing (sample of a wave), [4] list flushes inside a sample
 };
-bool append_ok(int bits, int logB, int logQ, uint32_t region_cap, uint32_t nslots, uint32_t cap);
+size_t append_lds_bytes(uint32_t nslots, uint32_t rb_ranks, bool count_only, bool two_tier);
+bool append_ok(int bits, int logB, int logQ, uint32_t region_cap, uint32_t nslots, uint32_t cap, uint32_t tt_rb_ranks = 0);      // tt_rb_ranks: two tiers, the row buffers' ranks
 void launch_append(const AppendArgs &a, uint32_t region_cap, hipStream_t st);
 void launch_append_probe(const AppendArgs &a, uint32_t region_cap, unsigned blocks, hipStream_t st);     // the first `blocks` row blocks, rows counted only
 // the same pass over 16-byte words (k > 31; skx_append_wide.inc): words / stage address u128 elements, off counts them; 16-byte table entries

@@ -337,12 +337,15 @@ static int estimate_rows(skx_ctx *ctx, const skx_dictset *d, AppendArgs aa, int 
 // unrelated and the sorted path reads less), 32 where the regions have grown with the samples (one XCD's workgroups: 256 / 8) -- unless
 // the words read stay few (allowed).  grid: workgroups of the persistent launch -- one per CU, whole groups of a region's readers (8 XCDs x
 // amp), `rounds` row blocks each -- when the blocks divide that way; 0: one workgroup per row block.
-struct AppendSplit { uint32_t cap, nslots; uint64_t amp; bool allowed; uint32_t rounds; uint64_t grid; };
-static AppendSplit append_split(double u_est, double est_relvar, int logQ, int logB, uint32_t region_cap, bool wide, int cus, uint64_t raw_sum)
+// two_tier: the block hands out up to APPEND_MAX_RANKS ranks and its LDS table holds what a row buffer covers (rb_ranks).
+struct AppendSplit { uint32_t cap, nslots; uint64_t amp; bool allowed; uint32_t rounds; uint64_t grid; uint32_t rb_ranks; };
+static AppendSplit append_split(double u_est, double est_relvar, int logQ, int logB, uint32_t region_cap, bool wide, int cus, uint64_t raw_sum, bool two_tier = false)
 {
     AppendSplit s{};
     const uint64_t nsub = 1ull << logQ;
-    s.cap = ranks_for(u_est / (double)nsub, est_relvar, append_max_cap(wide)); s.nslots = slots_for(s.cap, append_max_slots(wide));
+    s.cap = ranks_for(u_est / (double)nsub, est_relvar, two_tier ? APPEND_MAX_RANKS : append_max_cap(wide));
+    s.rb_ranks = two_tier ? std::min(s.cap, APPEND_TT_LDS_RANKS) : s.cap;
+    s.nslots = slots_for(s.rb_ranks, append_max_slots(wide));
     s.amp = 1ull << (logQ - logB);
     const uint64_t amp_max = region_cap > lds_sort_max(wide) ? 32 : 8;
     s.allowed = !(s.amp > amp_max && (double)raw_sum * (double)s.amp > 4e8);
@@ -351,6 +354,52 @@ static AppendSplit append_split(double u_est, double est_relvar, int logQ, int l
     const bool persistent = g <= (uint64_t)std::max(cus, 1) && nsub % g == 0 && g % (8 * s.amp) == 0 && logB >= 3;
     s.grid = persistent ? g : 0; s.rounds = persistent ? (uint32_t)(nsub / g) : 1;
     return s;
+}
+
+// Two tiers: whether the split one step COARSER than the coarsest whose blocks fit the LDS ranks should run, and when its LDS tier closes --
+// host arithmetic only, from the row estimate and the samples' window counts.  Half the readers per region, if
+//   (a) a block's rows, with the same six sigma, fit APPEND_MAX_RANKS;
+//   (b) the population is related: the longest sample's windows per block (the rows the block has after its first sample, and about what every
+//       sample looks up) are at most TT_HOT of the LDS tier's ranks.  TT_HOT is not derivable; see profiles/append_two_tier_policy_*.log;
+//       and a later sample brings at most TT_NEW of a sample's rows as new ones (per <= TT_NEW x first: 0.35 % at the flagship, 100 % for
+//       unrelated samples, whose late rows are looked up as often as the early ones);
+//   (c) the waves meet while the LDS tier still has room: rows arrive as the first sample's and then an even share of the rest per sample
+//       (per), the waves meet every 16 x resync samples, and what a block has by the first meeting fits the tier with six sigma.
+//   (d) the blocks of the finer split are nearly full (their mean is at least TT_FULL of APPEND_MAX_CAP).  Measured: 1 000 x 5 Mbp, 5 520 rows
+//       of 6 016 (0.92), the coarser split wins 1.1 ms; 500 x 5 Mbp, 3 392 (0.56), it LOSES 0.8 ms -- the finer split's table is 41 % full
+//       there and the coarser split's LDS tier 65 %, so more look-ups leave the eight-slot window
+//       (profiles/append_two_tier_policy_2026-10-21.log).
+// The tier closes at the first meeting that finds lds_close rows: the tier's ranks less what may arrive before the NEXT meeting (16 x resync x
+// per, six sigma, + 32) -- closing later would risk the block (a full LDS table fails it), closing earlier sends rows to tier 2 that the LDS
+// had room for.  The table's slots follow slots_for(): a third more than the ranks, where all but 2 % of the keys lie in the look-up's window
+// of eight slots.  A wrong guess costs time only: a block that fills either tier fails, and the pass comes back at the finer split, one tier.
+constexpr double TT_HOT = 0.5, TT_NEW = 0.02, TT_FULL = 0.8;
+struct TwoTierPlan { bool on = false; uint32_t lds_close = 0, resync = 16; };
+static TwoTierPlan two_tier_plan(double u_est, double est_relvar, uint64_t raw_max, int S, int logQ_fine, int min_logQ)
+{
+    TwoTierPlan p;
+    p.resync = (uint32_t)std::min(16, std::max(1, S / 64));
+    if (logQ_fine - 1 < min_logQ || S < 2) return p;
+    if ((int)p.resync > (S - 16) / 16) return p;                          // (no meeting at which every wave has a sample: append_kernel)
+    const double nsub = (double)(1ull << (logQ_fine - 1));
+    const double first = (double)raw_max / nsub, per = std::max(0.0, u_est - (double)raw_max) / nsub / (double)(S - 1), between = 16.0 * p.resync * per;
+    if (ranks_need(u_est / nsub, est_relvar) > (double)APPEND_MAX_RANKS) return p;                       // (a)
+    if (first > TT_HOT * (double)APPEND_TT_LDS_RANKS) return p;                                            // (b)
+    if (per > TT_NEW * first) return p;                                                                    // (b)
+    if (ranks_need(first + between, est_relvar) > (double)APPEND_TT_LDS_RANKS) return p;                 // (c)
+    if (u_est / (2.0 * nsub) < TT_FULL * (double)APPEND_MAX_CAP) return p;                                  // (d)
+    p.lds_close = (uint32_t)std::max(1.0, (double)APPEND_TT_LDS_RANKS - ranks_need(between, 0.0));
+    p.on = true;
+    return p;
+}
+
+// a test hook of the library (not in include/skx.h): the plan for these numbers -- out[0] taken, out[1] lds_close, out[2] resync
+extern "C" int skx_debug_two_tier_plan(double u_est, double est_relvar, uint64_t raw_max, int n_samples, int logQ_fine, int min_logQ, uint32_t *out)
+{
+    if (!out) { set_error("bad arguments"); return SKX_EINVAL; }
+    const TwoTierPlan p = two_tier_plan(u_est, est_relvar, raw_max, n_samples, logQ_fine, min_logQ);
+    out[0] = p.on ? 1u : 0u; out[1] = p.lds_close; out[2] = p.resync;
+    return SKX_OK;
 }
 
 // the pass itself: the row blocks' keys (ks: stage / ncnt / roff, stride = cap) and the samples' pieces
@@ -378,14 +427,25 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
     int logQ = min_logQ;
     while (logQ < bits && ranks_need(e.u_est / (double)(1ull << logQ), e.est_relvar) > (double)append_max_cap(wide)) logQ++;
     // (tests: SKX_KNOBS=append_coarse=N starts N steps coarser, so that row blocks overflow and the retries below run -- no input reaches them)
+    // Two tiers (64-bit keys; SKX_KNOBS=append_two_tier=0: never): one step coarser where two_tier_plan() says so -- the first attempt only,
+    // a block that fails comes back at the split above with one tier.  Tests: SKX_KNOBS=append_lds_ranks=N runs every attempt with two tiers
+    // at whatever split it has, the waves meeting after every sample and the LDS tier closing at the first meeting that finds N rows (N = 1:
+    // closed from the start, every row in tier 2).
+    const long tt_knob = wide || knob("append_two_tier", 1) == 0 ? 0 : knob("append_lds_ranks");
+    TwoTierPlan tt;
+    if (!wide && knob("append_two_tier", 1) != 0 && tt_knob <= 0) tt = two_tier_plan(e.u_est, e.est_relvar, raw_max, S, logQ, min_logQ);
+    if (tt.on) logQ--;
+    if (tt_knob > 0) { tt.lds_close = tt_knob <= 1 ? 0u : (uint32_t)tt_knob; tt.resync = 1; }
     if (knob("append_coarse") > 0) logQ = std::max<long>(min_logQ, logQ - knob("append_coarse"));
     int cus = 0; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     for (int attempt = 0;; attempt++, logQ++) {
-        if (logQ > bits || attempt > 3) return append_not_taken(ctx, "row blocks kept overflowing (a sample that is one repeat, or far more rows than the probe saw)");
+        const bool two = tt_knob > 0 || (tt.on && attempt == 0);
+        if (logQ > bits || attempt > (tt.on ? 4 : 3)) return append_not_taken(ctx, "row blocks kept overflowing (a sample that is one repeat, or far more rows than the probe saw)");
         const uint64_t nsub = 1ull << logQ;
-        const AppendSplit sp = append_split(e.u_est, e.est_relvar, logQ, logB, d->region_cap, wide, cus, raw_sum);
+        const AppendSplit sp = append_split(e.u_est, e.est_relvar, logQ, logB, d->region_cap, wide, cus, raw_sum, two);
         if (!sp.allowed) return append_not_taken(ctx, "too many row blocks per region: every region would be read too often");
-        if (!append_fits(wide, bits, logB, logQ, d->region_cap, sp.nslots, sp.cap)) return append_not_taken(ctx, "no row-block split that fits the LDS");
+        if (!(two ? append_ok(bits, logB, logQ, d->region_cap, sp.nslots, sp.cap, sp.rb_ranks) : append_fits(wide, bits, logB, logQ, d->region_cap, sp.nslots, sp.cap)))
+            return append_not_taken(ctx, "no row-block split that fits the LDS");
         std::unique_ptr<skx_keyset> ks(new skx_keyset());
         ks->ctx = ctx; ks->k = d->k; ks->rc = d->rc; ks->logN = logQ; ks->hp = d->hp; ks->wh = d->wh; ks->wide = wide; ks->stride = sp.cap;
         std::unique_ptr<skx_pieces> pc(new skx_pieces());
@@ -399,12 +459,27 @@ static int append_pass(skx_ctx *ctx, skx_dictset *d, std::unique_ptr<skx_keyset>
         aa.logQ = logQ; aa.nslots = sp.nslots; aa.cap = sp.cap; aa.rounds = sp.rounds; aa.bar = d_bar.p;
         aa.pieces = pc->data.p; aa.plen = pc->plen.p; aa.perm = pc->perm.p; aa.nrank = pc->nrank.p;
         aa.stage = ks->stage.p; aa.stride = sp.cap; aa.ncnt = ks->ncnt.p;
+        DevBuf<unsigned long long> d_t2, d_tts;
+        aa.two_tier = two ? 1 : 0; aa.rb_ranks = sp.rb_ranks; aa.lds_close = tt.lds_close; aa.resync = tt.resync; aa.t2 = nullptr; aa.tt_stat = nullptr;
+        if (two) {
+            const uint64_t wgs = nsub / sp.rounds;                     // (the launch's workgroups: launch_append)
+            if (d_t2.alloc(wgs * (uint64_t)(APPEND_T2_SLOTS + APPEND_T2_PAD)) != SKX_OK) return append_not_taken(ctx, "no room for the second tier");
+            SKX_TRY(d_tts.alloc(APPEND_TT_STATS)); SKX_TRY(d_tts.zero(st));
+            aa.t2 = d_t2.p; aa.tt_stat = d_tts.p;
+        }
         { KernelTimer kt(ctx, &ctx->tm.append); if (wide) launch_append_wide(aa, st); else launch_append(aa, d->region_cap, st); }
         int ov = 0;
+        unsigned long long tts[APPEND_TT_STATS] = {};
         SKX_HIP(hipMemcpyAsync(&ov, d_flag.p, 4, hipMemcpyDeviceToHost, st));
+        if (two && getenv("SKX_DEBUG")) SKX_HIP(hipMemcpyAsync(tts, d_tts.p, sizeof tts, hipMemcpyDeviceToHost, st));
         SKX_HIP(hipStreamSynchronize(st));
         SKX_HIP(hipGetLastError());
-        if (getenv("SKX_DEBUG")) fprintf(stderr, "[skx] append%s: logQ=%d (x%llu per region) cap=%u slots=%u rows~%.0f -> %s [sized by %s]\n", wide ? " (128-bit keys)" : "", logQ, (unsigned long long)sp.amp, sp.cap, sp.nslots, e.u_est, ov ? "overflow" : "ok", e.sized);
+        if (getenv("SKX_DEBUG")) {
+            fprintf(stderr, "[skx] append%s: logQ=%d (x%llu per region) cap=%u slots=%u rows~%.0f -> %s [sized by %s]\n", wide ? " (128-bit keys)" : "", logQ, (unsigned long long)sp.amp, sp.cap, sp.nslots, e.u_est, ov ? "overflow" : "ok", e.sized);
+            // (blocks that failed are not counted: closed / tier-2 rows are those of the blocks that were emitted)
+            if (two) fprintf(stderr, "[skx] append two tiers: %s split, lds_ranks=%u close_at=%u meet_every=%u closed_blocks=%llu of %llu lds_rows=%llu last_close_meeting=%llu tier2_rows=%llu list_flushes=%llu\n",
+                             tt.on ? "coarser" : "same", sp.rb_ranks, tt.lds_close, tt.resync, tts[0], (unsigned long long)nsub, tts[1], tts[3], tts[2], tts[4]);
+        }
         if (ov & 4) return append_not_taken(ctx, "the table's bytes are not at LDS address 0");
         if (ov) continue;
         SKX_TRY(keyset_finish(ks.get()));
