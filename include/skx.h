@@ -501,6 +501,57 @@ enum { SKX_QC_TILE_ROWS = 4096, SKX_QC_SAMPLES = 64 };   /* the shape of the sec
 typedef struct { uint64_t kmers, ambiguous, singletons, core_present, private_alleles, minor_alleles; } skx_qc_sample;
 typedef struct { uint64_t rows, rows_present, core_rows, core_variant_rows, threshold; } skx_qc_info;
 int  skx_array_sample_qc(skx_array *a, double min_freq, skx_qc_sample *samples, skx_qc_info *info);
+/* `ska density`: the stretches of a reference in which one sample carries far more SNPs than descent alone explains (recombination, to be taken
+ * out before a tree is built), from one streamed pass over the matrix instead of the S x L alignment `ska map` writes.  The reference has no
+ * counterpart: its users write that alignment and run a separate tool over it.
+ * Definition (tests/density_model.py states the same).
+ * Reference and windows.  The reference is a FASTA file of C chromosomes.  Its windows are `ska map`'s: runs of ACGT in either case, N splitting
+ *     runs, and the end-of-record quirk (a run that starts less than k + 1 letters before the end of its record gives none); each window has the
+ *     position of its middle base, its canonical split k-mer and its is_rc.
+ * Sites.  A window is a site when its split k-mer is a row of the array and that split k-mer occurs exactly once among all windows of the
+ *     reference.  The repeated windows are the ones `ska map --repeat-mask` masks; they are never sites, so every row is the row of at most one site.
+ * Cells.  For site x and sample s the cell is the array's byte for (row, s), passed through RC_IUPAC when is_rc; the 0 byte counts as '-'.
+ * Classes.  With r = the reference's middle base, upper-cased, a cell is missing when it is '-'; ambiguous when it is present and none of A, C,
+ *     G, T; snp when it is one of A, C, G, T and != r; otherwise it matches.  callable = matching + snp, so missing + ambiguous + callable = sites
+ *     for every sample.
+ * Dense SNPs.  Per (sample, chromosome) take the SNP positions p_0 < p_1 < ...; SNP i is dense when some j with j <= i <= j + T - 1 has
+ *     p_{j+T-1} - p_j < W: i is one of T consecutive SNPs that lie inside W consecutive reference positions.
+ * Regions.  A region is a maximal run of consecutive dense SNPs of one (sample, chromosome): sample, chromosome, start = first position, end =
+ *     last position (0-based here), snps = their number.  Regions never span chromosomes.
+ * Bins.  Chromosome c has ceil(len_c / W) bins of W positions; per bin, summed over samples, snps and dense_snps.
+ * Per sample.  sites, callable, ambiguous, missing, snps, dense_snps, regions and region_bases (the sum of end - start + 1).
+ * Whole call.  windows, repeat_windows (windows whose split k-mer occurs more than once) and sites.
+ * Everything is an integer: the same bytes whatever the order of arrival.  1 <= W <= 2^31, 2 <= T <= 65 535.
+ * Results (each malloc'd, skx_free; on an error none is returned and *out is zeroed): samples[S]; regions[info.n_regions] ascending by (sample,
+ * chromosome, start); bins[info.n_bins], chromosome after chromosome; chrom_ids = the C ids (the header up to white space), each NUL-terminated,
+ * one after the other; chrom_lens[C]; with SKX_DENSITY_WANT_SNPS snps[info.n_snps], ascending by (sample, x), = sample << 34 | x << 2 | base, x the position in
+ * the concatenated reference, base the cell as read on the reference's strand (A 0, C 1, T 2, G 3), bit SKX_DENSITY_DENSE_BIT set when the SNP
+ * is dense, and snp_ref[info.n_snps] = the reference's byte there, upper-cased.
+ * `a` keeps its content (an array held as pieces or lazily is materialised first); both key widths, engine-ordered or not.  SKX_EINVAL with a
+ * message that begins "density:" for NULL arguments, W or T out of range, a cell of a site outside the alphabet, a chromosome id that occurs twice;
+ * "Cannot create reference from FASTQ files", SKX_EEMPTY "<file> has no valid sequence" and "split k-mers and variants are out of step ..." as
+ * skx_array_map; SKX_EUNSUP with "density:" for an array that holds only a part of its samples, 2^28 samples or more, 2^32 - 2 SNP records or
+ * more.  No site, or an array without rows, is no error: the counts are zeros.
+ * Device side.  density_rows_kernel leaves per row the byte a matching cell holds (0: no site) and the site's position.  density_kernel runs over
+ * units of (SKX_DENSITY_TILE_ROWS rows, SKX_DENSITY_SAMPLES samples), a lane 16 rows, twice: a count launch (four counts per sample, the unit's
+ * SNPs) and, after a scan of the units, a write launch (one 64-bit record per SNP).  The records are sorted; the dense flags, regions, bins and
+ * per-sample sums come from passes over the sorted list in blocks of SKX_DENSITY_SCAN_BLOCK.  Device memory beside the array: `ska map`'s window
+ * buffers (25 bytes a reference byte at k <= 31, 33 above) and the repeat sort's (28 bytes a window), 5 bytes a row (rounded up to
+ * SKX_DENSITY_TILE_ROWS), 8 bytes a unit, 64 bytes a sample, 8 bytes a bin, and per SNP record 16 bytes and the radix sort's own buffers while
+ * the list is sorted, 27 bytes after it, 20 bytes a region. */
+enum { SKX_DENSITY_TILE_ROWS = 4096, SKX_DENSITY_SAMPLES = 64, SKX_DENSITY_SCAN_BLOCK = 4096 };   /* the shapes of the kernels as built */
+enum { SKX_DENSITY_WANT_SNPS = 1, SKX_DENSITY_DENSE_BIT = 62 };
+typedef struct { uint32_t sample, chrom, start, end, snps; } skx_density_region;
+typedef struct { uint64_t sites, callable, ambiguous, missing, snps, dense_snps, regions, region_bases; } skx_density_sample;
+typedef struct { uint32_t snps, dense_snps; } skx_density_bin;
+typedef struct { uint64_t windows, repeat_windows, sites, n_chrom, n_bins, n_snps, n_regions; } skx_density_info;
+typedef struct {
+    skx_density_info info;
+    skx_density_sample *samples; skx_density_region *regions; skx_density_bin *bins;
+    char *chrom_ids; uint64_t *chrom_lens;
+    uint64_t *snps; uint8_t *snp_ref;
+} skx_density_result;
+int  skx_array_snp_density(skx_array *a, const char *reference_fasta, uint64_t window, uint32_t min_snps, int flags, skx_density_result *out);
 /* the `k` a .skf file states in its first fields, without loading it (0: not found there, or the file cannot be read): lets a caller that
  * would try 64-bit keys first and 128-bit keys next (lib.rs:635-661) go to the right width at once */
 int  skx_skf_peek_k(const char *path);

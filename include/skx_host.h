@@ -119,6 +119,32 @@ int skh_qc_text(int which, const skx_qc_sample *samples, const char *const *name
  * empty when nobody is flagged).  SKX_EINVAL for NULL arguments, min_freq outside [0, 1] and a negative or NaN mad before anything is loaded;
  * otherwise the refusals are skx_array_sample_qc's.  Phases: qc.load / qc.kernels / qc.text. */
 int skh_qc(skx_ctx *ctx, const char *skf_file, const char *out_prefix, double min_freq, double mad);
+/* the four texts of `ska density` from what skx_array_snp_density returns (host only; the counts are defined in include/skx.h, the texts restated
+ * in tests/density_model.py).  names: the array's n_samples sample names; window: the W of the call.  Positions are 1-based and inclusive.
+ * SKH_DENSITY_REGIONS <PREFIX>.density.regions.tsv: header "sample\tchromosome\tstart\tend\tlength\tsnps", a line per region in the result's order.
+ * SKH_DENSITY_SUMMARY <PREFIX>.density.summary.tsv: header "sample\tsites\tcallable\tambiguous\tmissing\tsnps\tdense_snps\tregions\tregion_bases\t
+ *                     snps_outside", a line per sample in the array's order; snps_outside = snps - dense_snps.
+ * SKH_DENSITY_BINS    <PREFIX>.density.bins.tsv: header "chromosome\tstart\tend\tsnps\tdense_snps", a line per bin, chromosome after chromosome;
+ *                     the last bin of a chromosome ends at its length.
+ * SKH_DENSITY_SNPS    <PREFIX>.density.snps.tsv: header "sample\tchromosome\tposition\tref\talt\tdense", a line per SNP in the list's order;
+ *                     ref = the reference's base upper-cased, alt = the sample's base on the reference's strand, dense = 1 or 0.
+ * SKX_EINVAL for NULL arguments, another `which`, window 0, a result that names a sample, chromosome or position that is not there, bins that are
+ * not those of `window`, SKH_DENSITY_SNPS on a result without the list.  *buf is malloc'd (skx_free). */
+enum { SKH_DENSITY_REGIONS = 0, SKH_DENSITY_SUMMARY = 1, SKH_DENSITY_BINS = 2, SKH_DENSITY_SNPS = 3 };
+int skh_density_text(int which, const skx_density_result *r, const char *const *names, uint64_t n_samples, uint64_t window, char **buf, uint64_t *len);
+/* what --masked-aln does to `ska map`'s alignment of the same array and reference (format aln: per sample '>' name '\n', the concatenated
+ * chromosomes, '\n'), in place: in each sample's line every byte of a region [start, end] that is not '-' becomes 'N'.  SKX_EINVAL when the
+ * text's length is not that of these samples on this reference, or a region lies outside it. */
+int skh_density_mask_alignment(char *aln, uint64_t len, const skx_density_result *r, const char *const *names, uint64_t n_samples);
+/* `ska density <REFERENCE> <SKF_FILE> -o PREFIX [--window W] [--min-snps T] [--snps] [--masked-aln FILE]` (no counterpart in the reference): the
+ * file is loaded once, unfiltered (skh_load_array), one call of skx_array_snp_density counts, and <PREFIX>.density.regions.tsv, .summary.tsv,
+ * .bins.tsv and, with snps != 0, .snps.tsv are written as skh_density_text forms them.  masked_aln != NULL: skx_array_map's alignment of the same
+ * reference (format aln, no ambig mask, repeat mask on) through skh_density_mask_alignment into that file: what a tree builder takes.
+ * SKX_EINVAL for NULL arguments and W or T out of range before anything is loaded; otherwise the refusals are skx_array_snp_density's (and
+ * skx_array_map's).  Phases: density.load / density.kernels (inside it density.read_reference, .windows, .lookup, .rows, .count, .write, .sort,
+ * .dense) / density.text / density.masked_aln. */
+int skh_density(skx_ctx *ctx, const char *reference_fasta, const char *skf_file, const char *out_prefix, uint64_t window, uint32_t min_snps, int snps,
+                const char *masked_aln);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

@@ -142,6 +142,13 @@ const std::vector<Cmd> &commands()
          {{"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.qc.tsv (per sample: split k-mers, ambiguous bases, singletons, core k-mers present and missing, private and minor alleles, flags), <OUTPUT>.qc.summary.tsv and <OUTPUT>.qc.flagged.txt (the flagged names, as `ska delete -f` reads them)"},
           {"--min-freq", "<MIN_FREQ>", "Minimum fraction of the samples a core k-mer has to appear in [default: 0.9]"},
           {"--mad", "<M>", "Flag a sample whose count lies more than M median absolute deviations from the median [default: 5]"}}},
+        {"density", "(MI355X engine) Find per sample the stretches of a reference that carry a dense run of SNPs (recombination, to be masked before a tree is built)", "ska density [OPTIONS] -o <OUTPUT> <REFERENCE> <SKF_FILE>",
+         {{"<REFERENCE>", "", "Reference FASTA file, as for `ska map`"}, {"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on"}},
+         {{"-o", "<OUTPUT>", "Output prefix: writes <OUTPUT>.density.regions.tsv (sample, chromosome, start, end, length, snps), <OUTPUT>.density.summary.tsv (one line per sample) and <OUTPUT>.density.bins.tsv (SNPs and dense SNPs of all samples per window of the reference)"},
+          {"--window", "<W>", "Reference positions T SNPs of a sample must lie inside to count as dense, 1 to 2147483648; a convention, not a calibration [default: 1000]"},
+          {"--min-snps", "<T>", "Number of consecutive SNPs of a sample inside a window that makes them dense, 2 to 65535; a convention, not a calibration [default: 5]"},
+          {"--snps", "", "Also write <OUTPUT>.density.snps.tsv: every SNP (sample, chromosome, position, ref, alt) and whether it is dense"},
+          {"--masked-aln", "<FILE>", "Also write `ska map --repeat-mask`'s alignment with every sample's regions overwritten by 'N': what a tree builder takes"}}},
     };
     return C;
 }

@@ -552,7 +552,7 @@ const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
                             "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels", "--sites", "--sites-max",
                             "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind",
-                            "--permutations", "--seed", "--order-file", "--min-cover", "--min-identity", "--mad", nullptr};
+                            "--permutations", "--seed", "--order-file", "--min-cover", "--min-identity", "--mad", "--window", "--min-snps", "--masked-aln", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 }
 int skh::fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
@@ -595,7 +595,8 @@ const char *skh::clap_arg(const char *flag)
         {"--mst-clusters", "--mst-clusters <PREFIX>"}, {"--levels", "--levels <L1,L2,...>"}, {"--sites", "--sites <PREFIX>"}, {"--sites-max", "--sites-max <N>"},
         {"--min-in", "--min-in <P>"}, {"--max-out", "--max-out <Q>"},
         {"--permutations", "--permutations <P>"}, {"--seed", "--seed <N>"}, {"--order-file", "--order-file <FILE>"},
-        {"--min-cover", "--min-cover <C>"}, {"--min-identity", "--min-identity <I>"}, {"--mad", "--mad <M>"}};
+        {"--min-cover", "--min-cover <C>"}, {"--min-identity", "--min-identity <I>"}, {"--mad", "--mad <M>"},
+        {"--window", "--window <W>"}, {"--min-snps", "--min-snps <T>"}, {"--masked-aln", "--masked-aln <FILE>"}};
     for (auto &sp : SPELLING) if (!strcmp(flag, sp[0])) return sp[1];
     return flag;
 }
@@ -1079,6 +1080,22 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
         if (int e = freq()) return e;
         if (a.has("--mad")) if (int e = clap_float(a.get("--mad"), clap_arg("--mad"), 0.0, HUGE_VAL, "must be zero or higher")) return e;
     }
+    else if (cmd == "density") {
+        // the engine's own mode: a reference and one device's array, refused as clap refuses a missing requirement, a conflict and a value that does not parse
+        if (a.pos.size() < 2) return clap_missing("density", a.pos.empty() ? "<REFERENCE>\n  <SKF_FILE>" : "<SKF_FILE>");
+        if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("density")); return 2; }
+        if (!a.has("-o")) return clap_missing("density", "-o <OUTPUT>");
+        if (a.has("--gpus") || multi) return clap_conflict("density", "--gpus", "<SKF_FILE>");
+        for (const char *o : {"-o", "--masked-aln"}) if (a.has(o) && a.get(o).empty()) return clap_invalid("", clap_arg(o), "a value is required");
+        if (a.has("--window")) {
+            if (int e = clap_uint(a.get("--window"), "--window <W>", 1, "must be between 1 and 2147483648 (inclusive)", true)) return e;
+            if (strtoull(a.get("--window").c_str(), nullptr, 10) > (1ull << 31)) return clap_invalid(a.get("--window"), "--window <W>", "must be between 1 and 2147483648 (inclusive)");
+        }
+        if (a.has("--min-snps")) {
+            if (int e = clap_uint(a.get("--min-snps"), "--min-snps <T>", 2, "must be between 2 and 65535 (inclusive)", true)) return e;
+            if (strtoull(a.get("--min-snps").c_str(), nullptr, 10) > 65535) return clap_invalid(a.get("--min-snps"), "--min-snps <T>", "must be between 2 and 65535 (inclusive)");
+        }
+    }
     else if (cmd == "lo") {                                                                                      // cli.rs:395-425
         if (a.pos.size() < 2) return clap_missing("lo", a.pos.empty() ? "<INPUT_SKF>\n  <OUTPUT>" : "<OUTPUT>");
         if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("lo")); return 2; }
@@ -1139,6 +1156,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"curve", " -o --permutations --seed --min-freq --order-file --all-permutations --gpus "},
             {"screen", " -o --min-cover --min-identity --matrix --gpus "},
             {"qc", " -o --min-freq --mad --gpus "},
+            {"density", " -o --window --min-snps --snps --masked-aln --gpus "},
             {"lo", " -r --reference -m --missing -d --depth -n --indel-kmers --threads "}};
         for (auto &kc : KNOWN)
             if (cmd == kc.cmd)
@@ -1256,6 +1274,13 @@ extern "C" int skh_main(int argc, char **argv)
     } else if (cmd == "qc") {                                                                                     // the engine's own: skh_qc
         if (skh_qc(ctx, a.pos[0].c_str(), a.get("-o").c_str(), strtod(a.get("--min-freq", "0.9").c_str(), nullptr), strtod(a.get("--mad", "5").c_str(), nullptr)) != SKX_OK)
             rcode = engine_fail();
+    } else if (cmd == "density") {                                                                                // the engine's own: skh_density
+        const std::string masked = a.get("--masked-aln");
+        if (skh_density(ctx, a.pos[0].c_str(), a.pos[1].c_str(), a.get("-o").c_str(), strtoull(a.get("--window", "1000").c_str(), nullptr, 10),
+                        (uint32_t)strtoull(a.get("--min-snps", "5").c_str(), nullptr, 10), a.has("--snps"), a.has("--masked-aln") ? masked.c_str() : nullptr) != SKX_OK) {
+            fprintf(stderr, "error: %s\n", skx_last_error());                                                     // a reference or a file that cannot be taken: exit code 1
+            rcode = 1;
+        }
     } else if (cmd == "cov") {                                                                                    // cli.rs Cov, lib.rs:828-851
         if (a.pos.size() != 2) return fail("usage: ska cov <fastq_fwd> <fastq_rev> [-k K] [--single-strand]");
         const int k = atoi(a.get("-k", "31").c_str());
@@ -1312,7 +1337,7 @@ extern "C" int skh_main(int argc, char **argv)
         if (r == SKX_EEMPTY) rcode = 1;                                                                          // extremities.rs: std::process::exit(1)
         else if (r != SKX_OK) rcode = engine_fail();
     } else {
-        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers, curve, screen, qc)");
+        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers, curve, screen, qc, density)");
     }
     const double t_done = since();
     if (dbg) fprintf(stderr, "[skx] main: %s done after %.2f s\n", cmd.c_str(), t_done);

@@ -35,6 +35,13 @@ QC_SAMPLES_TEXT, QC_SUMMARY_TEXT, QC_FLAGGED_TEXT = 0, 1, 2                     
 SCREEN_RECORD_DT = np.dtype([("length", "<u8"), ("windows", "<u8"), ("rows_hit", "<u8")])      # skx_screen_record
 SCREEN_CELL_DT = np.dtype([("found", "<u4"), ("match", "<u4"), ("ambig", "<u4")])              # skx_screen_cell
 SCREEN_PAIRS, SCREEN_SUMMARY, SCREEN_MATRIX = 0, 1, 2                       # SKH_SCREEN_* (include/skx_host.h)
+DENSITY_TILE_ROWS, DENSITY_SAMPLES, DENSITY_SCAN_BLOCK = 4096, 64, 4096      # SKX_DENSITY_* (include/skx.h): the shapes of skx_array_snp_density's kernels
+DENSITY_WANT_SNPS, DENSITY_DENSE_BIT = 1, 62
+DENSITY_REGION_DT = np.dtype([(f, "<u4") for f in ("sample", "chrom", "start", "end", "snps")])                                                 # skx_density_region
+DENSITY_SAMPLE_DT = np.dtype([(f, "<u8") for f in ("sites", "callable", "ambiguous", "missing", "snps", "dense_snps", "regions", "region_bases")])   # skx_density_sample
+DENSITY_BIN_DT = np.dtype([("snps", "<u4"), ("dense_snps", "<u4")])                                                                             # skx_density_bin
+DENSITY_INFO_DT = np.dtype([(f, "<u8") for f in ("windows", "repeat_windows", "sites", "n_chrom", "n_bins", "n_snps", "n_regions")])             # skx_density_info
+DENSITY_REGIONS, DENSITY_SUMMARY, DENSITY_BINS, DENSITY_SNPS = 0, 1, 2, 3   # SKH_DENSITY_* (include/skx_host.h)
 PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
 TREE_JOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4")])                                                                        # skx_tree_join
 
@@ -119,6 +126,12 @@ class SubsetInfo(C.Structure):
     _fields_ = [("rows_present", C.c_uint64), ("removed", C.c_uint64), ("silent", C.c_uint64), ("sites", C.c_uint64)]
 
 
+class DensityResult(C.Structure):
+    """skx_density_result (include/skx.h)"""
+    _fields_ = [("info", C.c_uint64 * 7), ("samples", C.c_void_p), ("regions", C.c_void_p), ("bins", C.c_void_p), ("chrom_ids", C.c_void_p),
+                ("chrom_lens", C.c_void_p), ("snps", C.c_void_p), ("snp_ref", C.c_void_p)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[skx {code}] {msg}")
@@ -150,6 +163,7 @@ skx_array_pair_sites skh_distance_sites
 skx_array_curve skh_curve skh_curve_orders skh_curve_tsv
 skx_array_screen skh_screen skh_screen_text
 skx_array_sample_qc skh_qc skh_qc_text
+skx_array_snp_density skh_density skh_density_text skh_density_mask_alignment
 skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
@@ -215,6 +229,10 @@ def load_library():
     lib.skx_array_sample_qc.argtypes = [vp, d, vp, vp]
     lib.skh_qc_text.argtypes = [i, vp, C.POINTER(cp), u64, vp, d, pp, C.POINTER(u64)]
     lib.skh_qc.argtypes = [vp, cp, cp, d, d]
+    lib.skx_array_snp_density.argtypes = [vp, cp, u64, C.c_uint32, i, C.POINTER(DensityResult)]
+    lib.skh_density_text.argtypes = [i, C.POINTER(DensityResult), C.POINTER(cp), u64, u64, pp, C.POINTER(u64)]
+    lib.skh_density_mask_alignment.argtypes = [vp, u64, C.POINTER(DensityResult), C.POINTER(cp), u64]
+    lib.skh_density.argtypes = [vp, cp, cp, cp, u64, C.c_uint32, i, cp]
     lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
     lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
@@ -383,6 +401,44 @@ def qc_text(which, samples, names, info, mad=5.0):
     p, n = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_qc_text(int(which), _np_ptr(rec), nm, len(names), _np_ptr(inf), float(mad), C.byref(p), C.byref(n)))
     return _take(p, n).decode()
+
+
+def _density_struct(res):
+    """a skx_density_result over the arrays of what Array.snp_density returns -> (struct, what must stay alive while it is used)"""
+    info = np.ascontiguousarray(res["info"], DENSITY_INFO_DT).reshape(1)
+    keep = [np.ascontiguousarray(res["samples"], DENSITY_SAMPLE_DT), np.ascontiguousarray(res["regions"], DENSITY_REGION_DT),
+            np.ascontiguousarray(res["bins"], DENSITY_BIN_DT), C.create_string_buffer(b"".join(x.encode() + b"\0" for x in res["chrom_ids"]) + b"\0"),
+            np.ascontiguousarray(res["chrom_lens"], np.uint64)]
+    r = DensityResult()
+    for j, f in enumerate(DENSITY_INFO_DT.names):
+        r.info[j] = int(info[0][f])
+    r.samples, r.regions, r.bins, r.chrom_lens = _np_ptr(keep[0]), _np_ptr(keep[1]), _np_ptr(keep[2]), _np_ptr(keep[4])
+    r.chrom_ids = C.cast(keep[3], C.c_void_p)
+    if res.get("snps") is not None:
+        keep += [np.ascontiguousarray(res["snps"], np.uint64), np.ascontiguousarray(res["snp_ref"], np.uint8)]
+        r.snps, r.snp_ref = _np_ptr(keep[5]), _np_ptr(keep[6])
+    return r, keep
+
+
+def density_text(which, res, names, window=1000):
+    """skh_density_text: one of the four texts of `ska density` (DENSITY_REGIONS, DENSITY_SUMMARY, DENSITY_BINS, DENSITY_SNPS) from what
+    Array.snp_density returns (host only)"""
+    load_library()
+    r, keep = _density_struct(res)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_density_text(int(which), C.byref(r), nm, len(names), int(window), C.byref(p), C.byref(n)))
+    return _take(p, n).decode()
+
+
+def density_mask_alignment(aln, res, names):
+    """skh_density_mask_alignment: `ska map`'s alignment (bytes, format aln) with every sample's regions overwritten by 'N' (host only)"""
+    load_library()
+    r, keep = _density_struct(res)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    buf = C.create_string_buffer(bytes(aln), len(aln))
+    _check(_lib.skh_density_mask_alignment(C.cast(buf, C.c_void_p), len(aln), C.byref(r), nm, len(names)))
+    return buf.raw
 
 
 def cov_histogram(fq1, fq2, k=31, rc=True, ctx=None):
@@ -635,6 +691,12 @@ class Context:
     def qc(self, skf_file, out_prefix, min_freq=0.9, mad=5.0):
         """`ska qc <skf> -o PREFIX` (skh_qc): PREFIX.qc.tsv, PREFIX.qc.summary.tsv and PREFIX.qc.flagged.txt"""
         _check(_lib.skh_qc(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), float(min_freq), float(mad)))
+
+    def density(self, reference, skf_file, out_prefix, window=1000, min_snps=5, snps=False, masked_aln=None):
+        """`ska density <reference> <skf> -o PREFIX` (skh_density): PREFIX.density.regions.tsv, .summary.tsv, .bins.tsv and, with snps, .snps.tsv;
+        masked_aln: also `ska map --repeat-mask`'s alignment with the regions overwritten by 'N' into that file"""
+        _check(_lib.skh_density(self.h, os.fsencode(reference), os.fsencode(skf_file), os.fsencode(out_prefix), int(window), int(min_snps), int(snps),
+                                os.fsencode(masked_aln) if masked_aln is not None else None))
 
     def screen(self, skf_file, panel, out_prefix, min_cover=0.9, min_identity=0.0, matrix=False):
         """`ska screen <skf> <panel> -o PREFIX` (skh_screen): PREFIX.screen.tsv, PREFIX.screen.summary.tsv and, with matrix, PREFIX.screen.matrix.tsv"""
@@ -1208,6 +1270,29 @@ class Array:
         for p in (pr, pi, pc):
             _lib.skx_free(p)
         return ids, rec, cells
+
+    def snp_density(self, reference, window=1000, min_snps=5, snps=False):
+        """skx_array_snp_density: per sample the dense-SNP regions along the FASTA reference at `reference`, this array left as it is -> a dict:
+        info (DENSITY_INFO_DT record), samples (DENSITY_SAMPLE_DT [S]), regions (DENSITY_REGION_DT, 0-based), bins (DENSITY_BIN_DT), chrom_ids,
+        chrom_lens (uint64 [C]) and, with snps, snps (uint64: sample << 34 | x << 2 | base, bit DENSITY_DENSE_BIT = dense) and snp_ref (uint8)"""
+        r = DensityResult()
+        _check(_lib.skx_array_snp_density(self.h, os.fsencode(reference), int(window), int(min_snps), DENSITY_WANT_SNPS if snps else 0, C.byref(r)))
+        info = np.array([tuple(int(x) for x in r.info)], DENSITY_INFO_DT)[0]
+
+        def take(p, n, dt):
+            return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dt).copy() if p and n else np.zeros(0, dt)
+        nC = int(info["n_chrom"])
+        out = {"info": info, "samples": take(r.samples, self.nsamples, DENSITY_SAMPLE_DT), "regions": take(r.regions, int(info["n_regions"]), DENSITY_REGION_DT),
+               "bins": take(r.bins, int(info["n_bins"]), DENSITY_BIN_DT), "chrom_lens": take(r.chrom_lens, nC, np.uint64), "chrom_ids": [],
+               "snps": take(r.snps, int(info["n_snps"]), np.uint64) if snps else None, "snp_ref": take(r.snp_ref, int(info["n_snps"]), np.uint8) if snps else None}
+        at = r.chrom_ids
+        for _ in range(nC):
+            s = C.string_at(at)
+            out["chrom_ids"].append(s.decode())
+            at += len(s) + 1
+        for p in (r.samples, r.regions, r.bins, r.chrom_ids, r.chrom_lens, r.snps, r.snp_ref):
+            _lib.skx_free(p)
+        return out
 
     def pair_sites(self, ij, min_freq=0.0, max_records=0, keys=True):
         """skx_array_pair_sites: the rows that make up the filter-ambiguous distance of each pair of ij ([n_pairs, 2], i < j), this array left as
