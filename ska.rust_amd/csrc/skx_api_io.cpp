@@ -45,6 +45,67 @@ extern "C" int skx_cov_histogram(skx_ctx *ctx, const char *fastq_fwd, const char
     });
 }
 
+// ------------------------------------------------------------------------------------------ a FASTA file onto an array (RefLookup, skx_internal.h)
+int RefLookup::read(const char *fasta, const char *too_long)
+{
+    SKX_TRY(read_sample_stream(fasta, nullptr, 0.0, hs));
+    if (hs.is_fastq) { set_error("Cannot create reference from FASTQ files"); return SKX_EINVAL; }                                // ska_ref.rs:206-208
+    L = hs.seq.size();
+    if (L > 0xFFFFFFF0ull) { set_error("%s", too_long); return SKX_EUNSUP; }
+    uint64_t b0 = 0, off = 0;
+    for (uint64_t i = 0; i < L; i++) if (hs.seq[i] == '\n') { cstart.push_back(b0); clen.push_back(i - b0); coff.push_back(off); off += i - b0; b0 = i + 1; }
+    coff.push_back(off);
+    return SKX_OK;
+}
+
+int RefLookup::windows(skx_array *a, const char *fasta, bool repeats)
+{
+    skx_ctx *ctx = a->ctx; hipStream_t st = ctx->stream;
+    SKX_TRY(d_seq.alloc(L + 16));
+    SKX_HIP(hipMemcpyAsync(d_seq.p, hs.seq.data(), L, hipMemcpyHostToDevice, st));
+    hflag.assign(L, 0);
+    if (L) {
+        SKX_TRY(ref_windows(ctx, d_seq.p, L, a->k, a->rc, wlo, whi, flag));
+        SKX_HIP(hipMemcpyAsync(hflag.data(), flag.p, L, hipMemcpyDeviceToHost, st));
+    }
+    SKX_HIP(hipStreamSynchronize(st));
+    SKX_HIP(hipGetLastError());
+    n_windows = 0;
+    for (uint64_t p = 0; p < L; p++) n_windows += hflag[p] != 0;
+    if (n_windows == 0) { set_error("%s has no valid sequence", fasta); return SKX_EEMPTY; }                                      // ska_ref.rs:255-257
+    if (repeats) {
+        // which windows: on the device (sorted with the engine's radix sort, neighbours compared)
+        SKX_TRY(ref_repeat_flags(ctx, wlo.p, a->k > 31 ? whi.p : nullptr, flag.p, L, rep));
+        hrep.assign(L, 0);
+        SKX_HIP(hipMemcpy(hrep.data(), rep.p, L, hipMemcpyDeviceToHost));
+    }
+    return SKX_OK;
+}
+
+int RefLookup::lookup(skx_array *a)
+{
+    hipStream_t st = a->ctx->stream;
+    const int h = (a->k - 1) / 2;
+    SKX_TRY(row.alloc(L)); SKX_TRY(is_rc.alloc(L));
+    if (a->k <= 31) {
+        DevBuf<uint64_t> sorted; DevBuf<uint32_t> perm;
+        const uint64_t *skeys = a->keys.p; const uint32_t *sperm = nullptr;
+        if (!a->engine_order) { SKX_TRY(sort_words_perm(a->keys.p, a->n_rows, sorted, perm, st)); skeys = sorted.p; sperm = perm.p; }
+        launch_map_lookup(wlo.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
+        SKX_HIP(hipStreamSynchronize(st));
+    } else {
+        DevBuf<uint64_t> tmp, sorted; DevBuf<uint32_t> perm; const u128 *w = nullptr;
+        if (a->n_rows) SKX_TRY(array_wide_words(a, tmp, &w));
+        const u128 *skeys = w; const uint32_t *sperm = nullptr;
+        if (!a->engine_order) { SKX_TRY(sort_wide_perm(w, a->n_rows, sorted, perm, st)); skeys = (const u128 *)sorted.p; sperm = perm.p; }
+        launch_map_lookup_wide(wlo.p, whi.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
+        SKX_HIP(hipStreamSynchronize(st));
+    }
+    SKX_TRY(select_mapped(row.p, L, mapped, &M, st));
+    SKX_HIP(hipGetLastError());
+    return SKX_OK;
+}
+
 // ------------------------------------------------------------------------------------------ ska map (N3)
 // generic_modes::map (generic_modes.rs:56-84): RefSka::new(k, reference, rc, ambig_mask, repeat_mask) (ska_ref.rs:189-311), map
 // (:508-533), write_aln | write_vcf (:622-765).  Device: reference windows, look-up of every window's split k-mer in the array,
@@ -59,35 +120,21 @@ extern "C" int skx_array_map(skx_array *a, const char *reference, int ambig_mask
     const int k = a->k, h = (k - 1) / 2, S = (int)a->names.size();
     if (a->n_kmers != a->n_rows || a->keys_absent) { set_error("split k-mers and variants are out of step (filtered without update_kmers)"); return SKX_EINVAL; }
     SKX_TRY(array_materialize(a));
-    HostStream hs;
-    SKX_TRY(read_sample_stream(reference, nullptr, 0.0, hs));
-    if (hs.is_fastq) { set_error("Cannot create reference from FASTQ files"); return SKX_EINVAL; }                                // ska_ref.rs:206-208
-    const uint64_t L = hs.seq.size();
-    if (L > 0xFFFFFFF0ull) { set_error("reference longer than 4 G bases"); return SKX_EUNSUP; }
+    RefLookup ref;
+    SKX_TRY(ref.read(reference, "reference longer than 4 G bases"));
     // chromosomes: start in the record stream, length, offset in the concatenated output
-    std::vector<uint64_t> cstart, clen, coff;
-    { uint64_t b0 = 0, off = 0; for (uint64_t i = 0; i < L; i++) if (hs.seq[i] == '\n') { cstart.push_back(b0); clen.push_back(i - b0); coff.push_back(off); off += i - b0; b0 = i + 1; } }
+    const HostStream &hs = ref.hs;
+    const std::vector<uint64_t> &cstart = ref.cstart, &clen = ref.clen, &coff = ref.coff;
+    const uint64_t L = ref.L;
     const size_t n_chrom = cstart.size();
     if (n_chrom > 1 && !format) skh_log(1, "ska::ska_ref", "Reference contained multiple contigs, in the output they will be concatenated");      // ska_ref.rs:641-645 write_aln
-    uint64_t total = 0; for (auto l : clen) total += l;
-    DevBuf<uint8_t> d_seq; SKX_TRY(d_seq.alloc(L + 16));
-    SKX_HIP(hipMemcpyAsync(d_seq.p, hs.seq.data(), L, hipMemcpyHostToDevice, st));
-    DevBuf<uint64_t> wlo, whi; DevBuf<uint8_t> flag;
-    SKX_TRY(ref_windows(ctx, d_seq.p, L, k, a->rc, wlo, whi, flag));
-    std::vector<uint8_t> hflag(L);
-    SKX_HIP(hipMemcpyAsync(hflag.data(), flag.p, L, hipMemcpyDeviceToHost, st));
-    SKX_HIP(hipStreamSynchronize(st));
-    uint64_t n_windows = 0; for (uint64_t p = 0; p < L; p++) n_windows += hflag[p] != 0;
-    if (n_windows == 0) { set_error("%s has no valid sequence", reference); return SKX_EEMPTY; }                                  // ska_ref.rs:255-257
+    const uint64_t total = coff[n_chrom];
+    SKX_TRY(ref.windows(a, reference, repeat_mask != 0));
+    const std::vector<uint8_t> &hflag = ref.hflag, &rep = ref.hrep;
     auto chrom_of = [&](uint64_t sp) { return (size_t)(std::upper_bound(cstart.begin(), cstart.end(), sp) - cstart.begin()) - 1; };
     // repeat coordinates (ska_ref.rs:259-293): every window whose split k-mer occurs more than once in the reference
     std::vector<uint64_t> repeat;
-    if (repeat_mask) {
-        // which windows: on the device (sorted with the engine's radix sort, neighbours compared); the coordinates below are bookkeeping
-        DevBuf<uint8_t> d_rep;
-        SKX_TRY(ref_repeat_flags(ctx, wlo.p, k > 31 ? whi.p : nullptr, flag.p, L, d_rep));
-        std::vector<uint8_t> rep(L, 0);
-        SKX_HIP(hipMemcpy(rep.data(), d_rep.p, L, hipMemcpyDeviceToHost));
+    if (repeat_mask) {                                                                                                             // (which windows: ref.windows; the coordinates are bookkeeping)
         uint64_t last_chrom = 0, last_end = 0, chrom_offset = 0;
         for (uint64_t p = 0; p < L; p++) {
             if (!hflag[p]) continue;
@@ -99,25 +146,9 @@ extern "C" int skx_array_map(skx_array *a, const char *reference, int ambig_mask
             last_chrom = c; last_end = end;
         }
     }
-    // look-up
-    DevBuf<uint32_t> row; DevBuf<uint8_t> is_rc;
-    SKX_TRY(row.alloc(L)); SKX_TRY(is_rc.alloc(L));
-    if (k <= 31) {
-        DevBuf<uint64_t> sorted; DevBuf<uint32_t> perm;
-        const uint64_t *skeys = a->keys.p; const uint32_t *sperm = nullptr;
-        if (!a->engine_order) { SKX_TRY(sort_words_perm(a->keys.p, a->n_rows, sorted, perm, st)); skeys = sorted.p; sperm = perm.p; }
-        launch_map_lookup(wlo.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
-        SKX_HIP(hipStreamSynchronize(st));
-    } else {
-        DevBuf<uint64_t> tmp, sorted; DevBuf<uint32_t> perm; const u128 *w = nullptr;
-        if (a->n_rows) SKX_TRY(array_wide_words(a, tmp, &w));
-        const u128 *skeys = w; const uint32_t *sperm = nullptr;
-        if (!a->engine_order) { SKX_TRY(sort_wide_perm(w, a->n_rows, sorted, perm, st)); skeys = (const u128 *)sorted.p; sperm = perm.p; }
-        launch_map_lookup_wide(wlo.p, whi.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
-        SKX_HIP(hipStreamSynchronize(st));
-    }
-    DevBuf<uint32_t> mapped; uint64_t M = 0;
-    SKX_TRY(select_mapped(row.p, L, mapped, &M, st));
+    SKX_TRY(ref.lookup(a));
+    const DevBuf<uint32_t> &row = ref.row, &mapped = ref.mapped; const DevBuf<uint8_t> &is_rc = ref.is_rc;
+    const uint64_t M = ref.M;
     if (M == 0) { set_error("No split k-mers mapped to reference"); return SKX_EINVAL; }                                          // ska_ref.rs:553-555
     std::vector<uint32_t> hm(M), mpos(M), mchrom(M);
     SKX_HIP(hipMemcpy(hm.data(), mapped.p, M * 4, hipMemcpyDeviceToHost));
@@ -180,7 +211,7 @@ extern "C" int skx_array_map(skx_array *a, const char *reference, int ambig_mask
                 std::string &t = parts[b];
                 for (uint64_t i = 0; i < nx; i++) {
                     const uint64_t idx = x0 + i;
-                    const size_t c = (size_t)(std::upper_bound(coff.begin(), coff.end(), idx) - coff.begin()) - 1;               // IdxCheck (idx_check.rs)
+                    const size_t c = (size_t)(std::upper_bound(coff.begin(), coff.begin() + (ptrdiff_t)n_chrom, idx) - coff.begin()) - 1;  // IdxCheck (idx_check.rs)
                     const uint64_t pos = idx - coff[c];
                     const uint8_t ref_base = hs.seq[cstart[c] + pos];
                     char alts[5]; int n_alt = 0; bool variant = false;

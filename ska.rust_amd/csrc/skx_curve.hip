@@ -4,8 +4,8 @@
 // and `ska align` once per prefix and per shuffle and count columns.
 //
 // The matrix is sample-major, so a row of the reference is a column here.  A thread owns 16 consecutive columns (one 16-byte load per sample, inside
-// the row's padding), a workgroup a tile of 4 096, and walks the samples of one order through order[p * S + t] -- the walk of markers_kernel
-// (skx_markers.hip) with a decision after every sample instead of every segment.  Per column one register: cells present in the low 16 bits, the OR
+// the row's padding), a workgroup a tile of 4 096, and walks the samples of one order through order[p * S + t] with four loads in flight
+// (ColumnLane and the walk of walk_columns, skx_cells.h, spelled out here across the LDS blocks), a decision after every sample.  Per column one register: cells present in the low 16 bits, the OR
 // of the unambiguous cells' codes above them.  After sample t the four flags of a lane's 16 columns are summed (two packed words: pan | core << 16,
 // variant | core_variant << 16; a tile holds 4 096 columns, so neither half overflows) over the wave -- each flag is a comparison whose lane mask is
 // counted in scalar registers, no shuffles -- and added by one lane to the step's two words in LDS.  The LDS block covers SKX_CURVE_LDS_STEPS steps; at its end (and at S) the workgroup adds it to the order's [S][4] 64-bit
@@ -16,6 +16,7 @@
 // Device memory beside the array: 36 bytes per (order, step) of a batch -- its orders (4) and counters (32) -- for at most
 // SKX_CURVE_BATCH_ORDERS orders and 2^22 (order, step) pairs a launch, and 4 S bytes of thresholds.
 #include "skx_internal.h"
+#include "skx_cells.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -39,23 +40,9 @@ struct CurveArgs {
     int *bad_byte;
 };
 
-// ASCII middle base -> bit 0: the cell is present; bits 16-19: its IUPAC set code (A 1, C 2, T 4, G 8) when it is a single base; bit 8: a byte
-// outside the alphabet ('-' and the 0 byte are 0)
-__device__ inline uint32_t curve_cell(uint32_t b)
-{
-    switch (b) {
-    case 0: case '-': return 0;
-    case 'A': return 1u | (1u << 16);  case 'C': return 1u | (2u << 16);  case 'T': return 1u | (4u << 16);  case 'G': return 1u | (8u << 16);
-    case 'M': case 'W': case 'Y': case 'H': case 'R': case 'S': case 'V': case 'K': case 'D': case 'B': case 'N': return 1u;
-    default: return 0x100u;
-    }
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void curve_kernel(CurveArgs a)
 {
-    __shared__ uint32_t s_lut[256];
+    __shared__ uint32_t s_lut[256];                                 // bit 0: present; bits 16-19: the set code of a single base (A 1, C 2, T 4, G 8); bit 8: outside the alphabet
     __shared__ uint32_t s_cnt[CURVE_STEPS][2];                      // per step of the block: pan | core << 16, variant | core_variant << 16
     __shared__ int s_ord[CURVE_STEPS + 4];                          // the block's samples and the four behind it (the loads in flight)
     __shared__ uint32_t s_thr[CURVE_STEPS];
@@ -63,14 +50,7 @@ __global__ __launch_bounds__(256) void curve_kernel(CurveArgs a)
     const uint64_t tile = a.orders_fastest ? blockIdx.x / a.n_orders : blockIdx.x % a.n_tiles;
     const uint64_t c0 = (tile * 256 + threadIdx.x) * 16;
     const int lane = threadIdx.x & 63;
-    // a thread past the last column walks column 0 behind a mask of zeros.  Rows are padded to the pitch (>= 256 bytes past n_cols), so the
-    // 16-byte load of a thread with c0 < n_cols stays inside the row; what it holds past n_cols is masked away.
-    const bool live = c0 < a.n_cols;
-    const uint8_t *col = a.matrix + (live ? c0 : 0);
-    const uint32_t n_valid = !live ? 0u : (a.n_cols - c0 >= 16 ? 16u : (uint32_t)(a.n_cols - c0));
-    u32x4 vm;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { const uint32_t nb = n_valid > 4u * w ? min(n_valid - 4u * w, 4u) : 0u; vm[w] = nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1u; }
+    const ColumnLane me(a.matrix, a.n_cols, c0);
     const uint32_t S = a.S;
     const int *order = a.orders + (uint64_t)p * S;
     unsigned long long *out = a.counts + (uint64_t)p * S * 4;
@@ -83,10 +63,12 @@ __global__ __launch_bounds__(256) void curve_kernel(CurveArgs a)
         }
     };
     uint32_t t0 = 0;                                                // the first step of the LDS block
-    // (past the last sample the last one is loaded again and never used: a load that is always issued keeps the count of loads in flight the
-    // same on every path, so a step waits for its own sample's load and not for the younger ones)
-    auto load = [&](uint32_t t) -> u32x4 { return *reinterpret_cast<const u32x4 *>(col + (uint64_t)s_ord[min(t, S - 1) - t0] * a.pitch); };
-    s_lut[threadIdx.x] = curve_cell(threadIdx.x);
+    // (the loads run four samples ahead, past a block's end into the next block's first samples, which are staged with the block; past S the last sample again)
+    auto load = [&](uint32_t t) -> u32x4 { return *reinterpret_cast<const u32x4 *>(me.col + (uint64_t)s_ord[min(t, S - 1) - t0] * a.pitch); };
+    {
+        const uint32_t c = cell_code(threadIdx.x);
+        s_lut[threadIdx.x] = c == CELL_OUTSIDE ? 0x100u : c == 0 ? 0u : 1u | (cell_one_base(c) ? c << 16 : 0u);
+    }
     stage(0);
     __syncthreads();
     uint32_t acc[16];
@@ -95,7 +77,7 @@ __global__ __launch_bounds__(256) void curve_kernel(CurveArgs a)
     for (int i = 0; i < 16; i++) acc[i] = 0;
 
     auto step = [&](uint32_t t, const u32x4 raw) {
-        const u32x4 cur = raw & vm;
+        const u32x4 cur = raw & me.vm;
         const uint32_t thr = s_thr[t - t0];
         // the wave's sums are formed in scalar registers: a comparison leaves its lanes as a 64-bit mask, whose bits are counted there
         uint32_t pc = 0, vc = 0;
@@ -114,8 +96,8 @@ __global__ __launch_bounds__(256) void curve_kernel(CurveArgs a)
             if (vc) atomicAdd(&s_cnt[t - t0][1], vc);
         }
     };
-    // four samples' loads in flight, each in registers of its own: a step waits for its sample's load alone
-    // (issued in this order, as the loop issues them: the wait at the loop's head then leaves the three younger loads in flight)
+    // walk_columns' walk (skx_cells.h) spelled out, its four buffers kept across the LDS blocks: with a walk of its own per block the kernel
+    // runs out of scalar registers and a step grows by 6 % (NOTEBOOK 2026-10-21, one column walk)
     u32x4 b0 = load(0);
     __builtin_amdgcn_sched_barrier(0);
     u32x4 b1 = load(1);

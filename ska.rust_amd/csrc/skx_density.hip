@@ -1,22 +1,19 @@
 // skx_density.hip -- `ska density`: dense-SNP regions per sample along a reference (skx_array_snp_density, include/skx.h; definition there and in
 // tests/density_model.py).  The reference has no counterpart: its users write `ska map`'s S x L alignment and run a separate tool over it.
 //
-// The windows, their look-up, the repeat flags and the compaction of the hits are `ska map`'s (ref_windows, launch_map_lookup[_wide],
-// ref_repeat_flags, select_mapped), called as skx_array_screen calls them.  A repeated window is no site, so a row is the row of at most one
-// site, and what a cell has to be compared with can be written per ROW: density_rows_kernel leaves want[row] -- the byte a matching cell holds:
-// the reference's middle base upper-cased, complemented where the reference strand is not the canonical one (screen_pack_kernel's argument:
-// RC_IUPAC keeps A, C, G, T among themselves, so no cell is translated), with bit 5 set where it was complemented so that a SNP's base can be
-// reported on the reference's strand; 0: the row is no site -- and xcat[row], the site's position in the concatenated reference.
+// The windows, their look-up, the repeat flags and the compaction of the hits are `ska map`'s (RefLookup, skx_internal.h).  A repeated window
+// is no site, so a row is the row of at most one site, and what a cell has to be compared with can be written per ROW: density_rows_kernel
+// leaves want[row] -- the byte a matching cell holds (want_byte, skx_cells.h), with bit 5 set where it was complemented so that a SNP's base
+// can be reported on the reference's strand; 0: the row is no site -- and xcat[row], the site's position in the concatenated reference.
 //
 // density_kernel streams the matrix (sample-major, so a row of the reference is a column here) in units of (SKX_DENSITY_TILE_ROWS columns,
 // SKX_DENSITY_SAMPLES samples), the sample blocks fastest along the grid so that the units in flight share their part of want
 // (qc_samples_kernel's shape).  A lane holds 16 columns: their 16 want bytes are loaded once, then the unit's samples are walked with one
-// 16-byte load each through four buffers, each in registers of its own, the load past the unit's end issued again so that the count of loads in
-// flight is the same on every path (NOTEBOOK 2026-10-20, qc).  The cells of columns that are no site are masked to the 0 byte before they are
+// 16-byte load each, four in flight (the walk of walk_columns, skx_cells.h, spelled out).  The cells of columns that are no site are masked to the 0 byte before they are
 // classed, which counts them as missing; a lane takes its number of such columns off again.  One template, two launches (skx_sites.hip):
 //   count   per sample and lane one word of three 10-bit fields (missing, ambiguous, one of ACGT) from an LDS table and the count of cells equal
-//           to want; summed over each half of the wave by DPP adds (qc's), added to the unit's [samples][4] block in LDS, and from there one
-//           64-bit atomic per (sample, count) and unit; the unit's number of SNPs is stored.
+//           to want; summed over each half of the wave by DPP adds (half_wave_sum), added to the unit's [samples][4] block in LDS, and from
+//           there one 64-bit atomic per (sample, count) and unit; the unit's number of SNPs is stored.
 //   write   after prim_scan_add_u32 over the units: units without a SNP return at once; a lane that finds SNPs takes their slots from a counter
 //           in LDS and stores one record a SNP at the unit's offset: sample << 34 | xcat << 2 | base.  xcat is read only there.
 // The records are unique per (sample, position), so their sorted list (prim_sort_keys_u64, 62 bits) does not depend on the order of arrival.
@@ -31,6 +28,7 @@
 // window), 5 bytes a row (rounded up to SKX_DENSITY_TILE_ROWS), 8 bytes a unit, 64 bytes a sample, 8 bytes a bin, and per SNP record 16 bytes
 // and the radix sort's own buffers while the list is sorted, 27 bytes after it, 20 bytes a region.
 #include "skx_internal.h"
+#include "skx_cells.h"
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -49,16 +47,6 @@ static_assert(SKX_DENSITY_TILE_ROWS / 4 / 2 <= 0x3FF, "half a wave's sum of a co
 static_assert(DN_SCAN % 256 == 0, "a workgroup of 256 threads strides over a scan block");
 static_assert(sizeof(skx_density_sample) == 8 * sizeof(uint64_t) && sizeof(skx_density_region) == 20 && sizeof(skx_density_bin) == 8, "the device writes these records");
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// the chromosome of position x of the concatenated reference: the last one that starts at or before x (coff ascending, coff[0] == 0)
-__device__ inline uint32_t chrom_of(const uint64_t *coff, uint32_t n_chrom, uint64_t x)
-{
-    uint32_t lo = 0, hi = n_chrom;
-    while (hi - lo > 1) { const uint32_t c = (lo + hi) >> 1; if (coff[c] <= x) lo = c; else hi = c; }
-    return lo;
-}
-
 // per hit window m (reference order) that is not repeated: want and xcat of its row.  The record stream holds one '\n' behind every chromosome, so
 // a middle base at stream position mid of chromosome c sits at mid - c of the concatenated reference
 __global__ __launch_bounds__(256) void density_rows_kernel(const uint32_t *mapped, const uint32_t *row, const uint8_t *is_rc, const uint8_t *rep, const uint8_t *seq, uint32_t h,
@@ -72,10 +60,8 @@ __global__ __launch_bounds__(256) void density_rows_kernel(const uint32_t *mappe
             site = true;
             const uint64_t mid = (uint64_t)p - h;
             const uint32_t c = chrom_of(cstart, n_chrom, mid);
-            const uint8_t b = seq[mid] & 0xDFu;                     // a window's letters are ACGT in either case
-            const uint8_t comp = b == 'A' ? 'T' : b == 'C' ? 'G' : b == 'G' ? 'C' : 'A';
             const uint32_t r = row[p];
-            want[r] = is_rc[p] ? (uint8_t)(comp | 0x20u) : b;
+            want[r] = want_byte(seq[mid], is_rc[p]) | (is_rc[p] ? 0x20u : 0u);
             xcat[r] = (uint32_t)(mid - c);
         }
     }
@@ -96,32 +82,10 @@ struct DensityArgs {
     int *bad_byte;
 };
 
-// ASCII middle base -> 1: '-' or the 0 byte; 1 << 10: present and none of A, C, G, T; 1 << 20: one of A, C, G, T; 0: a byte outside the alphabet
-__device__ inline uint32_t density_class(uint32_t b)
-{
-    switch (b) {
-    case 0: case '-': return 1u;
-    case 'A': case 'C': case 'G': case 'T': return 1u << 20;
-    case 'M': case 'W': case 'Y': case 'H': case 'R': case 'S': case 'V': case 'K': case 'D': case 'B': case 'N': return 1u << 10;
-    default: return 0u;
-    }
-}
-
-// the sum of v over lanes 0-31 in lane 31 and over lanes 32-63 in lane 63 (qc_half_wave_sum, skx_qc.hip)
-__device__ inline uint32_t density_half_wave_sum(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);      // row_shr:1 (a lane without a source adds the 0)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);      // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);      // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);      // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);      // row_bcast:15 into rows 1 and 3
-    return v;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(256) void density_kernel(DensityArgs a)
 {
-    __shared__ uint32_t s_lut[256];
+    __shared__ uint32_t s_lut[256];                                 // 1: '-' or the 0 byte; 1 << 10: present and none of A, C, G, T; 1 << 20: one of them; 0: outside the alphabet
     __shared__ uint32_t s_cnt[DN_B * 4];                            // count: missing, ambiguous, one of ACGT, equal to want
     __shared__ uint32_t s_unit;                                     // count: the unit's SNPs; write: the slots handed out
     const uint32_t have = WRITE ? a.unit_snps[blockIdx.x] : 0u;
@@ -131,13 +95,15 @@ __global__ __launch_bounds__(256) void density_kernel(DensityArgs a)
     const uint64_t c0 = (tile * 256 + threadIdx.x) * 16;
     const int lane = threadIdx.x & 63;
     const uint32_t s0 = sb * DN_B, s1 = min(a.S, s0 + DN_B);        // s0 < S: the grid holds no empty block
-    s_lut[threadIdx.x] = density_class(threadIdx.x);
+    {
+        const uint32_t c = cell_code(threadIdx.x);
+        s_lut[threadIdx.x] = c == CELL_OUTSIDE ? 0u : c == 0 ? 1u : cell_one_base(c) ? 1u << 20 : 1u << 10;
+    }
     if (!WRITE) for (uint32_t j = threadIdx.x; j < DN_B * 4; j += 256) s_cnt[j] = 0;
     if (threadIdx.x == 0) s_unit = 0;
     // the lane's 16 columns: what a matching cell holds (0x100: no site, no byte equals it), which strand, and the byte mask of the sites.  want
-    // covers whole tiles and is 0 past the last column; a lane past it walks column 0 behind a mask of zeros.  Rows are padded to the pitch
-    // (>= 256 bytes past n_cols), so the 16-byte load of a lane with c0 < n_cols stays inside the row
-    const uint8_t *col = a.matrix + (c0 < a.n_cols ? c0 : 0);
+    // covers whole tiles and is 0 past the last column, so the sites' mask stands in for ColumnLane's: only its column pointer is taken
+    const uint8_t *col = ColumnLane(a.matrix, a.n_cols, c0).col;
     uint32_t w[16], rc2 = 0, n_off = 0;
     u32x4 sm;
     {
@@ -156,7 +122,6 @@ __global__ __launch_bounds__(256) void density_kernel(DensityArgs a)
         }
     }
     __syncthreads();
-    // (past the unit's last sample that one is loaded again and never used)
     auto load = [&](uint32_t t) -> u32x4 { return *reinterpret_cast<const u32x4 *>(col + (uint64_t)min(t, s1 - 1) * a.pitch); };
     const uint32_t shift = 10u * ((uint32_t)lane % 3u);
     uint32_t bad = 0;
@@ -174,7 +139,7 @@ __global__ __launch_bounds__(256) void density_kernel(DensityArgs a)
             // every cell is of one class: the three fields sum to 16 unless a site's cell lies outside the alphabet
             bad |= (all & 0x3FFu) + ((all >> 10) & 0x3FFu) + (all >> 20) != 16u ? 1u : 0u;
             all -= n_off;                                           // (the masked cells read as missing: at least n_off of the field)
-            const uint32_t w1 = density_half_wave_sum(all), w2 = density_half_wave_sum(eq);
+            const uint32_t w1 = half_wave_sum(all), w2 = half_wave_sum(eq);
             const uint32_t x1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, 31), y1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, 63);
             const uint32_t x2 = (uint32_t)__builtin_amdgcn_readlane((int)w2, 31), y2 = (uint32_t)__builtin_amdgcn_readlane((int)w2, 63);
             const uint32_t v = lane < 3 ? ((x1 >> shift) & 0x3FFu) + ((y1 >> shift) & 0x3FFu) : x2 + y2;
@@ -200,6 +165,7 @@ __global__ __launch_bounds__(256) void density_kernel(DensityArgs a)
             }
         }
     };
+    // walk_columns' walk (skx_cells.h) spelled out: the shared form adds 10 vector and 58 scalar instructions to the loop (NOTEBOOK 2026-10-21, one column walk)
     u32x4 b0 = load(s0);
     __builtin_amdgcn_sched_barrier(0);
     u32x4 b1 = load(s0 + 1);
@@ -351,17 +317,13 @@ extern "C" int skx_array_snp_density(skx_array *a, const char *reference_fasta, 
     SKX_TRY(array_materialize(a));
     const uint64_t U = a->n_rows;
     if (U >= (1ull << 32)) { set_error("density: %llu rows; at most 2^32 - 1 are taken", (unsigned long long)U); return SKX_EUNSUP; }
-    HostStream hs;
+    RefLookup ref;
     {
         PhaseTimer pr("density.read_reference");
-        SKX_TRY(read_sample_stream(reference_fasta, nullptr, 0.0, hs));
+        SKX_TRY(ref.read(reference_fasta, "density: reference longer than 4 G bases"));
     }
-    if (hs.is_fastq) { set_error("Cannot create reference from FASTQ files"); return SKX_EINVAL; }                                // as `ska map` (ska_ref.rs:206-208)
-    const uint64_t L = hs.seq.size();
-    if (L > 0xFFFFFFF0ull) { set_error("density: reference longer than 4 G bases"); return SKX_EUNSUP; }
-    // chromosomes: start in the record stream (every record ends with '\n' there), length, start in the concatenated reference
-    std::vector<uint64_t> cstart, clen, coff;
-    { uint64_t b0 = 0, off = 0; for (uint64_t i = 0; i < L; i++) if (hs.seq[i] == '\n') { cstart.push_back(b0); clen.push_back(i - b0); coff.push_back(off); off += i - b0; b0 = i + 1; } coff.push_back(off); }
+    const HostStream &hs = ref.hs;
+    const std::vector<uint64_t> &cstart = ref.cstart, &clen = ref.clen, &coff = ref.coff;      // chromosomes: start in the record stream, length, start in the concatenated reference
     const uint64_t C = cstart.size();
     if (hs.ids.size() != C) { set_error("density: %s: %llu record ids for %llu records", reference_fasta, (unsigned long long)hs.ids.size(), (unsigned long long)C); return SKX_EINVAL; }
     {
@@ -369,50 +331,24 @@ extern "C" int skx_array_snp_density(skx_array *a, const char *reference_fasta, 
         for (auto &id : hs.ids) if (!seen.insert(id).second) { set_error("density: %s: chromosome id %s occurs more than once", reference_fasta, id.c_str()); return SKX_EINVAL; }
     }
     PhaseTimer pw("density.windows");
-    DevBuf<uint8_t> d_seq; SKX_TRY(d_seq.alloc(L + 16));
-    SKX_HIP(hipMemcpyAsync(d_seq.p, hs.seq.data(), L, hipMemcpyHostToDevice, st));
-    DevBuf<uint64_t> wlo, whi; DevBuf<uint8_t> flag, rep;
-    std::vector<uint8_t> hflag(L), hrep(L);
-    if (L) {
-        SKX_TRY(ref_windows(ctx, d_seq.p, L, k, a->rc, wlo, whi, flag));
-        SKX_HIP(hipMemcpyAsync(hflag.data(), flag.p, L, hipMemcpyDeviceToHost, st));
-    }
-    SKX_HIP(hipStreamSynchronize(st));
-    SKX_HIP(hipGetLastError());
-    uint64_t n_windows = 0, n_repeat = 0;
-    for (uint64_t p = 0; p < L; p++) n_windows += hflag[p] != 0;
-    if (n_windows == 0) { set_error("%s has no valid sequence", reference_fasta); return SKX_EEMPTY; }                            // as `ska map` (ska_ref.rs:255-257)
-    SKX_TRY(ref_repeat_flags(ctx, wlo.p, k > 31 ? whi.p : nullptr, flag.p, L, rep));
-    SKX_HIP(hipMemcpy(hrep.data(), rep.p, L, hipMemcpyDeviceToHost));
-    for (uint64_t p = 0; p < L; p++) n_repeat += hflag[p] && hrep[p];
+    SKX_TRY(ref.windows(a, reference_fasta, true));
+    const std::vector<uint8_t> &hrep = ref.hrep;
+    const uint64_t n_windows = ref.n_windows;
+    uint64_t n_repeat = 0;
+    for (uint64_t p = 0; p < ref.L; p++) n_repeat += ref.hflag[p] && hrep[p];
     std::vector<uint64_t> binoff(C);
     uint64_t n_bins = 0;
     for (uint64_t c = 0; c < C; c++) { binoff[c] = n_bins; n_bins += (clen[c] + W - 1) / W; }
     pw.stop();
 
-    // look-up and compaction, as skx_array_map does them (an array without rows has no hit)
-    DevBuf<uint32_t> row, mapped; DevBuf<uint8_t> is_rc; uint64_t M = 0;
+    // look-up and compaction (an array without rows has no hit)
     if (U) {
         PhaseTimer pl("density.lookup");
-        SKX_TRY(row.alloc(L)); SKX_TRY(is_rc.alloc(L));
-        if (k <= 31) {
-            DevBuf<uint64_t> sorted; DevBuf<uint32_t> perm;
-            const uint64_t *skeys = a->keys.p; const uint32_t *sperm = nullptr;
-            if (!a->engine_order) { SKX_TRY(sort_words_perm(a->keys.p, U, sorted, perm, st)); skeys = sorted.p; sperm = perm.p; }
-            launch_map_lookup(wlo.p, flag.p, d_seq.p, L, h, skeys, sperm, U, row.p, is_rc.p, st);
-            SKX_HIP(hipStreamSynchronize(st));
-        } else {
-            DevBuf<uint64_t> tmp, sorted; DevBuf<uint32_t> perm; const u128 *w = nullptr;
-            SKX_TRY(array_wide_words(a, tmp, &w));
-            const u128 *skeys = w; const uint32_t *sperm = nullptr;
-            if (!a->engine_order) { SKX_TRY(sort_wide_perm(w, U, sorted, perm, st)); skeys = (const u128 *)sorted.p; sperm = perm.p; }
-            launch_map_lookup_wide(wlo.p, whi.p, flag.p, d_seq.p, L, h, skeys, sperm, U, row.p, is_rc.p, st);
-            SKX_HIP(hipStreamSynchronize(st));
-        }
-        SKX_TRY(select_mapped(row.p, L, mapped, &M, st));
-        SKX_HIP(hipGetLastError());
+        SKX_TRY(ref.lookup(a));
     }
-    wlo.release(); whi.release(); flag.release();
+    ref.wlo.release(); ref.whi.release(); ref.flag.release();
+    DevBuf<uint32_t> &row = ref.row, &mapped = ref.mapped; DevBuf<uint8_t> &is_rc = ref.is_rc, &rep = ref.rep, &d_seq = ref.d_seq;
+    const uint64_t M = ref.M;
 
     // the results that do not depend on a kernel
     skx_density_result res{};

@@ -274,6 +274,27 @@ int select_mapped(const uint32_t *row, uint64_t len, DevBuf<uint32_t> &mapped, u
 int sort_words_perm(const uint64_t *words, uint64_t n, DevBuf<uint64_t> &sorted, DevBuf<uint32_t> &perm, hipStream_t st);
 int sort_unique_wide(const u128 *in, uint64_t n, DevBuf<uint64_t> &out, uint64_t *n_out, hipStream_t st);
 int sort_wide_perm(const u128 *words, uint64_t n, DevBuf<uint64_t> &sorted, DevBuf<uint32_t> &perm, hipStream_t st);
+// A FASTA file mapped onto an array, as `ska map`, `ska screen` and `ska density` need it (skx_api_io.cpp, next to skx_array_map): the three
+// steps in the order of their refusals; what a caller refuses or times in between stays with the caller.
+//   read     the file into hs; refuses FASTQ and more than 4 G bases (too_long: the caller's whole message for that); the records' start in the
+//            record stream (every record ends with '\n' there), length, and start in the concatenated reference (coff: one more entry, the total)
+//   windows  upload, ref_windows, the flags back on the host; refuses a file without a window ("... has no valid sequence"); repeats: the
+//            repeat flags too (density always, map under --repeat-mask).  Nothing is launched for an empty stream (ref_windows would launch an
+//            empty grid): the refusal is the same
+//   lookup   row[p] and is_rc[p] of every window's split k-mer (k <= 31 or above, sorted first where the array is not in engine order), and the
+//            positions of the hits in order: mapped[0 .. M).  It takes an array without rows (M = 0, which map then refuses with its own message);
+//            screen and density do not call it for one and keep M = 0.  It ends with hipGetLastError, for map too (its own copy did not ask)
+// The buffers live as long as the struct: for map the device repeat flags (L bytes) now stay to the end of the call
+struct RefLookup {
+    HostStream hs;
+    std::vector<uint64_t> cstart, clen, coff;
+    uint64_t L = 0, n_windows = 0, M = 0;
+    DevBuf<uint8_t> d_seq, flag, rep, is_rc; DevBuf<uint64_t> wlo, whi; DevBuf<uint32_t> row, mapped;
+    std::vector<uint8_t> hflag, hrep;                               // flag and rep on the host (hrep: only with repeats)
+    int read(const char *fasta, const char *too_long);
+    int windows(skx_array *a, const char *fasta, bool repeats);
+    int lookup(skx_array *a);
+};
 // the engine's own device primitives (skx_prims.hip): stable radix sorts (`bits` significant key bits, 8 a pass; the input is left as it is),
 // inclusive scans, order-keeping selections, unique on sorted keys, exclusive OR-scan within runs of equal keys.  Each returns with the stream idle.
 int prim_sort_keys_u64(const uint64_t *in, uint64_t *out, uint64_t n, int bits, hipStream_t st);

@@ -20,6 +20,7 @@
 // times (less what the caches keep), whatever the number of groups; device memory beside the array is 12 U bytes of state, 12 bytes a workgroup
 // (4 096 columns), 16 bytes a group and 68 bytes a record while they are sorted.  No per-(group, row) table exists.
 #include "skx_internal.h"
+#include "skx_cells.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -45,21 +46,6 @@ struct MarkerArgs {
     int *bad_byte;
 };
 
-// ASCII middle base -> IUPAC set code (A 1, C 2, T 4, G 8); 0 for '-' and the 0 byte, 0xFF for a byte outside the alphabet
-__device__ inline uint32_t marker_code(uint32_t b)
-{
-    switch (b) {
-    case 0: case '-': return 0;
-    case 'A': return 1;  case 'C': return 2;  case 'M': return 3;  case 'T': return 4;
-    case 'W': return 5;  case 'Y': return 6;  case 'H': return 7;  case 'G': return 8;
-    case 'R': return 9;  case 'S': return 10; case 'V': return 11; case 'K': return 12;
-    case 'D': return 13; case 'B': return 14; case 'N': return 15;
-    default: return 0xFF;
-    }
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // acc[i] of a thread's 16 columns: cells present in the low 16 bits (at most 65 535 samples), the OR of their codes from bit 16
 __device__ inline void absorb(const u32x4 cur, const uint8_t *lut, uint32_t (&acc)[16], uint32_t &bad)
 {
@@ -84,17 +70,20 @@ __device__ inline uint32_t bases_outside(uint32_t f01, uint32_t f23, uint32_t to
 template <bool WRITE>
 __global__ __launch_bounds__(256) void markers_kernel(MarkerArgs a)
 {
-    __shared__ uint8_t s_lut[256];
+    __shared__ uint8_t s_lut[256];                                  // the IUPAC set code of cell_code; 0xFF: a byte outside the alphabet
     __shared__ uint32_t s_records;                                  // count pass: the workgroup's records; write pass: how many it has placed
-    s_lut[threadIdx.x] = (uint8_t)marker_code(threadIdx.x);
+    {
+        const uint32_t c = cell_code(threadIdx.x);
+        s_lut[threadIdx.x] = (uint8_t)(c == CELL_OUTSIDE ? 0xFFu : c);
+    }
     if (threadIdx.x == 0) s_records = 0;
     __syncthreads();
     const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
     const int lane = threadIdx.x & 63;
-    // a thread past the last column walks column 0 and decides nothing: the wave's shuffles stay whole.  Rows are padded to the pitch
-    // (>= 256 bytes past n_cols), so the 16-byte load of a thread with c0 < n_cols stays inside the row.
-    const bool live = c0 < a.n_cols;
-    const uint8_t *col = a.matrix + (live ? c0 : 0);
+    // a thread past the last column walks column 0 and decides nothing (ColumnLane, skx_cells.h); a bit of `valid` a column below n_cols
+    const ColumnLane me(a.matrix, a.n_cols, c0);
+    const bool live = me.live;
+    const uint8_t *col = me.col;
     const uint32_t valid = !live ? 0u : (a.n_cols - c0 >= 16 ? 0xFFFFu : (1u << (uint32_t)(a.n_cols - c0)) - 1u);
     uint32_t acc[16], tot[16], f01[16], f23[16];
     uint32_t bad = 0;

@@ -4,9 +4,7 @@
 // The matrix is sample-major, so a row of the reference is a column here.  Two launches, integer atomics only:
 //
 // qc_rows_kernel reads the matrix once.  A thread owns 16 consecutive columns (one 16-byte load per sample, inside the row's padding), a workgroup
-// 4 096, and walks the samples through four load buffers, each in registers of its own (as compiled, three or four loads are in flight ahead of a
-// step: the fourth of the first round is sunk into the loop, NOTEBOOK 2026-10-20, qc) (the walk of curve_kernel, skx_curve.hip, without an order
-// list).  Per column five 16-bit counters in three registers -- n | c[A] << 16, c[C] | c[T] << 16, c[G] | bad << 16 -- fed by three words of an
+// 4 096, and walks the samples with four loads in flight (ColumnLane and walk_columns, skx_cells.h).  Per column five 16-bit counters in three registers -- n | c[A] << 16, c[C] | c[T] << 16, c[G] | bad << 16 -- fed by three words of an
 // LDS table per cell (one address, three adds, no comparison).  After the last sample a column's counters become its 16-bit descriptor (D_* below),
 // stored 32 bytes a lane, and the three row totals are counted as lane masks in scalar registers and added through LDS to 64-bit counters.
 //
@@ -24,6 +22,7 @@
 //
 // Device memory beside the array: 2 bytes a row (rounded up to SKX_QC_TILE_ROWS), 48 bytes a sample, 28 bytes of totals and the bad-byte flag.
 #include "skx_internal.h"
+#include "skx_cells.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -41,36 +40,8 @@ static_assert(SKX_QC_TILE_ROWS / 4 / 2 <= 0x3FF, "half a wave's sum of a count f
 // a row's descriptor
 enum : uint32_t { D_PRESENT = 1u, D_SINGLE = 2u, D_CORE = 4u, D_VARIANT = 8u, D_PRIVATE_SHIFT = 4, D_MAJOR_SHIFT = 8 };
 
-// ASCII middle base -> IUPAC set code (A 1, C 2, T 4, G 8; '-' and the 0 byte are 0); 0x100: a byte outside the alphabet
-__device__ inline uint32_t qc_code(uint32_t b)
-{
-    switch (b) {
-    case 0: case '-': return 0;
-    case 'A': return 1;  case 'C': return 2;  case 'M': return 3;  case 'T': return 4;  case 'W': return 5;  case 'Y': return 6;  case 'H': return 7;
-    case 'G': return 8;  case 'R': return 9;  case 'S': return 10; case 'V': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14;
-    case 'N': return 15;
-    default: return 0x100u;
-    }
-}
 // a 4-bit set of bases in fields of five bits: A at bit 0, C at 5, T at 10, G at 15
 __device__ inline uint32_t qc_spread(uint32_t m) { return (m & 1u) | ((m & 2u) << 4) | ((m & 4u) << 8) | ((m & 8u) << 12); }
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// what a thread of either kernel owns: 16 columns from c0; one past the last column walks column 0 behind a mask of zeros.  Rows are padded to
-// the pitch (>= 256 bytes past n_cols), so the 16-byte load of a thread with c0 < n_cols stays inside the row; what it holds past n_cols is
-// masked away
-struct QcLane {
-    const uint8_t *col; u32x4 vm;
-    __device__ QcLane(const uint8_t *matrix, uint64_t n_cols, uint64_t c0)
-    {
-        const bool live = c0 < n_cols;
-        col = matrix + (live ? c0 : 0);
-        const uint32_t n_valid = !live ? 0u : (n_cols - c0 >= 16 ? 16u : (uint32_t)(n_cols - c0));
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const uint32_t nb = n_valid > 4u * w ? min(n_valid - 4u * w, 4u) : 0u; vm[w] = nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1u; }
-    }
-};
 
 struct QcRowsArgs {
     const uint8_t *matrix; uint64_t pitch, n_cols;
@@ -86,23 +57,21 @@ __global__ __launch_bounds__(256) void qc_rows_kernel(QcRowsArgs a)
     __shared__ uint32_t s_tot[3];
     const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
     const int lane = threadIdx.x & 63;
-    const QcLane me(a.matrix, a.n_cols, c0);
+    const ColumnLane me(a.matrix, a.n_cols, c0);
     const uint32_t S = a.S;
     {
-        const uint32_t c = qc_code(threadIdx.x);
-        s_lut[0][threadIdx.x] = (c != 0 && c != 0x100u ? 1u : 0u) | (c == 1 ? 1u << 16 : 0u);
+        const uint32_t c = cell_code(threadIdx.x);
+        s_lut[0][threadIdx.x] = (cell_present(c) ? 1u : 0u) | (c == 1 ? 1u << 16 : 0u);
         s_lut[1][threadIdx.x] = (c == 2 ? 1u : 0u) | (c == 4 ? 1u << 16 : 0u);
-        s_lut[2][threadIdx.x] = (c == 8 ? 1u : 0u) | (c == 0x100u ? 1u << 16 : 0u);
+        s_lut[2][threadIdx.x] = (c == 8 ? 1u : 0u) | (c == CELL_OUTSIDE ? 1u << 16 : 0u);
         if (threadIdx.x < 3) s_tot[threadIdx.x] = 0;
     }
     __syncthreads();
     uint32_t acc0[16], acc1[16], acc2[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) { acc0[i] = 0; acc1[i] = 0; acc2[i] = 0; }
-    // (past the last sample the last one is loaded again and never used: a load that is always issued keeps the count of loads in flight the
-    // same on every path, so a step waits for its own sample's load and not for the younger ones)
     auto load = [&](uint32_t t) -> u32x4 { return *reinterpret_cast<const u32x4 *>(me.col + (uint64_t)min(t, S - 1) * a.pitch); };
-    auto step = [&](const u32x4 raw) {
+    auto step = [&](uint32_t, const u32x4 raw) {
         const u32x4 cur = raw & me.vm;
 #pragma unroll
         for (int i = 0; i < 16; i++) {
@@ -110,22 +79,7 @@ __global__ __launch_bounds__(256) void qc_rows_kernel(QcRowsArgs a)
             acc0[i] += s_lut[0][b]; acc1[i] += s_lut[1][b]; acc2[i] += s_lut[2][b];      // at most 65 535 samples: no half overflows
         }
     };
-    u32x4 b0 = load(0);
-    __builtin_amdgcn_sched_barrier(0);
-    u32x4 b1 = load(1);
-    __builtin_amdgcn_sched_barrier(0);
-    u32x4 b2 = load(2);
-    __builtin_amdgcn_sched_barrier(0);
-    u32x4 b3 = load(3);
-    for (uint32_t t = 0; t < S; t += 4) {                           // (b0 holds sample t; every bound is the same for the whole workgroup)
-        step(b0); b0 = load(t + 4);
-        if (t + 1 < S) step(b1);
-        b1 = load(t + 5);
-        if (t + 2 < S) step(b2);
-        b2 = load(t + 6);
-        if (t + 3 < S) step(b3);
-        b3 = load(t + 7);
-    }
+    walk_columns(0, S, load, step);
     uint32_t bad = 0, n_present = 0, n_core = 0, n_core_variant = 0, d[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) {
@@ -168,18 +122,6 @@ struct QcSamplesArgs {
     unsigned long long *counts;                                     // [S][6] in the order of skx_qc_sample
 };
 
-// the sum of v over lanes 0-31 in lane 31 and over lanes 32-63 in lane 63: four shifts inside each row of 16 lanes, then the last lane of rows 0
-// and 2 added to rows 1 and 3
-__device__ inline uint32_t qc_half_wave_sum(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);      // row_shr:1 (a lane without a source adds the 0)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);      // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);      // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);      // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);      // row_bcast:15 into rows 1 and 3
-    return v;
-}
-
 __global__ __launch_bounds__(256) void qc_samples_kernel(QcSamplesArgs a)
 {
     __shared__ uint32_t s_lut[2][256];                              // present | ambiguous << 5; the base in fields of five bits | present << 20
@@ -188,11 +130,11 @@ __global__ __launch_bounds__(256) void qc_samples_kernel(QcSamplesArgs a)
     const uint64_t tile = blockIdx.x / a.n_sblocks;
     const uint64_t c0 = (tile * 256 + threadIdx.x) * 16;
     const int lane = threadIdx.x & 63;
-    const QcLane me(a.matrix, a.n_cols, c0);
+    const ColumnLane me(a.matrix, a.n_cols, c0);
     const uint32_t s0 = sb * QC_B, s1 = min(a.S, s0 + QC_B);       // s0 < S: the grid holds no empty block
     {
-        const uint32_t c = qc_code(threadIdx.x);
-        const bool present = c != 0 && c != 0x100u, plain = c == 1 || c == 2 || c == 4 || c == 8;
+        const uint32_t c = cell_code(threadIdx.x);
+        const bool present = cell_present(c), plain = cell_one_base(c);
         s_lut[0][threadIdx.x] = (present ? 1u : 0u) | (present && !plain ? 1u << 5 : 0u);
         s_lut[1][threadIdx.x] = (plain ? qc_spread(c) : 0u) | (present ? 1u << 20 : 0u);
         for (uint32_t j = threadIdx.x; j < QC_B * 6; j += 256) s_cnt[j] = 0;
@@ -211,7 +153,6 @@ __global__ __launch_bounds__(256) void qc_samples_kernel(QcSamplesArgs a)
         }
     }
     __syncthreads();
-    // (past the unit's last sample that one is loaded again and never used, as in qc_rows_kernel)
     auto load = [&](uint32_t t) -> u32x4 { return *reinterpret_cast<const u32x4 *>(me.col + (uint64_t)min(t, s1 - 1) * a.pitch); };
     const uint32_t shift = 10u * ((uint32_t)lane % 3u);
     auto step = [&](uint32_t t, const u32x4 raw) {
@@ -225,13 +166,14 @@ __global__ __launch_bounds__(256) void qc_samples_kernel(QcSamplesArgs a)
         }
         // a cell adds to one base's field at most, so the four fields sum to 16 at most and no partial sum of the product carries
         const uint32_t n_private = (((pv & 0xFFFFFu) * 0x8421u) >> 15) & 0x1Fu, n_minor = (((mn & 0xFFFFFu) * 0x8421u) >> 15) & 0x1Fu;
-        const uint32_t w1 = qc_half_wave_sum((all & 0x1Fu) | ((all >> 5) << 10) | ((mn >> 20) << 20));      // kmers, ambiguous, singletons
-        const uint32_t w2 = qc_half_wave_sum((pv >> 20) | (n_private << 10) | (n_minor << 20));             // core_present, private_alleles, minor_alleles
+        const uint32_t w1 = half_wave_sum((all & 0x1Fu) | ((all >> 5) << 10) | ((mn >> 20) << 20));      // kmers, ambiguous, singletons
+        const uint32_t w2 = half_wave_sum((pv >> 20) | (n_private << 10) | (n_minor << 20));             // core_present, private_alleles, minor_alleles
         const uint32_t x1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, 31), y1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, 63);
         const uint32_t x2 = (uint32_t)__builtin_amdgcn_readlane((int)w2, 31), y2 = (uint32_t)__builtin_amdgcn_readlane((int)w2, 63);
         const uint32_t v = (((lane < 3 ? x1 : x2) >> shift) & 0x3FFu) + (((lane < 3 ? y1 : y2) >> shift) & 0x3FFu);
         if (lane < 6 && v) atomicAdd(&s_cnt[(t - s0) * 6 + lane], v);
     };
+    // walk_columns' walk (skx_cells.h) spelled out: the shared form did not keep this kernel's time (NOTEBOOK 2026-10-21, one column walk)
     u32x4 b0 = load(s0);
     __builtin_amdgcn_sched_barrier(0);
     u32x4 b1 = load(s0 + 1);

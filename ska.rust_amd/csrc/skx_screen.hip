@@ -2,11 +2,10 @@
 // include/skx.h; definition there and in tests/screen_model.py).  The reference has no counterpart: its users run `ska map` on the panel
 // (generic_modes.rs:56-84) and count columns of an S x panel-length alignment, or `ska weed --reverse` and `ska nk` once per record.
 //
-// The windows, their look-up and the compaction of the hits are `ska map`'s (ref_windows, launch_map_lookup[_wide], select_mapped).  What is
+// The windows, their look-up and the compaction of the hits are `ska map`'s (RefLookup, skx_internal.h).  What is
 // new is the reduction from (hit window, sample) cells to three integers per (record, sample) without the cells ever being stored.
 // screen_pack_kernel turns the hit list into what the walk needs per window: its row, its record and the byte a matching cell holds -- the
-// record's middle base upper-cased, complemented where the reference strand is not the canonical one (RC_IUPAC is a bijection on the
-// alphabet that keeps A, C, G, T among themselves, so cell == complement(base) says what RC_IUPAC(cell) == base says, and present and
+// record's middle base upper-cased, complemented where the reference strand is not the canonical one (want_byte, skx_cells.h; present and
 // ambiguous are the same on either strand).  screen_kernel: a workgroup takes SKX_SCREEN_TILE consecutive hit windows and
 // SKX_SCREEN_SAMPLES samples; a lane is a sample.  The tile's rows, records and bytes are staged in LDS and read as broadcasts into scalar
 // registers; a lane's byte of window j is matrix[s * pitch + row[j]] -- the matrix is sample-major, so the 64 lanes of a wave read 64
@@ -22,6 +21,7 @@
 // Device memory beside the array: `ska map`'s window buffers (25 bytes a panel byte at k <= 31, 33 above), 9 bytes a hit window and
 // 12 bytes a (record, sample) pair.
 #include "skx_internal.h"
+#include "skx_cells.h"
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -45,11 +45,7 @@ __global__ __launch_bounds__(256) void screen_pack_kernel(const uint32_t *mapped
     if (m >= M) return;
     const uint32_t p = mapped[m];
     const uint64_t mid = (uint64_t)p - h;
-    uint32_t lo = 0, hi = n_records;                                // the last record that starts at or before mid
-    while (hi - lo > 1) { const uint32_t c = (lo + hi) >> 1; if (cstart[c] <= mid) lo = c; else hi = c; }
-    const uint8_t b = seq[mid] & 0xDFu;                             // a window's letters are ACGT in either case
-    const uint8_t comp = b == 'A' ? 'T' : b == 'C' ? 'G' : b == 'G' ? 'C' : 'A';
-    hrow[m] = row[p]; hrec[m] = lo; hwant[m] = is_rc[p] ? comp : b;
+    hrow[m] = row[p]; hrec[m] = chrom_of(cstart, n_records, mid); hwant[m] = want_byte(seq[mid], is_rc[p]);
 }
 
 struct ScreenArgs {
@@ -60,26 +56,18 @@ struct ScreenArgs {
     int *bad_byte;
 };
 
-// ASCII middle base -> bit 0: present; bit 1: present and none of A, C, G, T; bit 8: a byte outside the alphabet ('-' and the 0 byte are 0)
-__device__ inline uint32_t screen_cell(uint32_t b)
-{
-    switch (b) {
-    case 0: case '-': return 0;
-    case 'A': case 'C': case 'G': case 'T': return 1u;
-    case 'M': case 'W': case 'Y': case 'H': case 'R': case 'S': case 'V': case 'K': case 'D': case 'B': case 'N': return 3u;
-    default: return 0x100u;
-    }
-}
-
 __global__ __launch_bounds__(256) void screen_kernel(ScreenArgs a)
 {
-    __shared__ uint32_t s_lut[256];
+    __shared__ uint32_t s_lut[256];                                 // bit 0: present; bit 1: present and none of A, C, G, T; bit 8: outside the alphabet
     __shared__ uint32_t s_row[SCREEN_TILE];
     __shared__ uint32_t s_rec[SCREEN_TILE];
     __shared__ uint32_t s_want[SCREEN_TILE];
     const uint64_t m0 = (uint64_t)blockIdx.x * SCREEN_TILE;
     const uint32_t n = (uint32_t)min((uint64_t)SCREEN_TILE, a.M - m0);          // >= 1: the grid has no empty tile
-    s_lut[threadIdx.x] = screen_cell(threadIdx.x);
+    {
+        const uint32_t c = cell_code(threadIdx.x);
+        s_lut[threadIdx.x] = c == CELL_OUTSIDE ? 0x100u : c == 0 ? 0u : cell_one_base(c) ? 1u : 3u;
+    }
     // (past the tile's end the last window again: every index the walk forms names a staged window)
     for (uint32_t j = threadIdx.x; j < SCREEN_TILE; j += 256) {
         const uint64_t m = m0 + min(j, n - 1);
@@ -144,17 +132,13 @@ extern "C" int skx_array_screen(skx_array *a, const char *panel_fasta, uint64_t 
     if (a->total_samples && a->total_samples != S) { set_error("screen: needs every sample of the array on one device"); return SKX_EUNSUP; }
     if (S == 0) { set_error("screen: the array has no samples"); return SKX_EINVAL; }
     SKX_TRY(array_materialize(a));
-    HostStream hs;
+    RefLookup ref;
     {
         PhaseTimer pr("screen.read_panel");
-        SKX_TRY(read_sample_stream(panel_fasta, nullptr, 0.0, hs));
+        SKX_TRY(ref.read(panel_fasta, "screen: panel longer than 4 G bases"));
     }
-    if (hs.is_fastq) { set_error("Cannot create reference from FASTQ files"); return SKX_EINVAL; }                                // as `ska map` (ska_ref.rs:206-208)
-    const uint64_t L = hs.seq.size();
-    if (L > 0xFFFFFFF0ull) { set_error("screen: panel longer than 4 G bases"); return SKX_EUNSUP; }
-    // records: start in the record stream and length (every record ends with '\n' there)
-    std::vector<uint64_t> cstart, clen;
-    { uint64_t b0 = 0; for (uint64_t i = 0; i < L; i++) if (hs.seq[i] == '\n') { cstart.push_back(b0); clen.push_back(i - b0); b0 = i + 1; } }
+    const HostStream &hs = ref.hs;
+    const std::vector<uint64_t> &cstart = ref.cstart, &clen = ref.clen;         // records: start in the record stream and length
     const uint64_t R = cstart.size();
     if (hs.ids.size() != R) { set_error("screen: %s: %llu record ids for %llu records", panel_fasta, (unsigned long long)hs.ids.size(), (unsigned long long)R); return SKX_EINVAL; }
     {
@@ -162,52 +146,25 @@ extern "C" int skx_array_screen(skx_array *a, const char *panel_fasta, uint64_t 
         for (auto &id : hs.ids) if (!seen.insert(id).second) { set_error("screen: %s: record id %s occurs more than once", panel_fasta, id.c_str()); return SKX_EINVAL; }
     }
     PhaseTimer pw("screen.windows");
-    DevBuf<uint8_t> d_seq; SKX_TRY(d_seq.alloc(L + 16));
-    SKX_HIP(hipMemcpyAsync(d_seq.p, hs.seq.data(), L, hipMemcpyHostToDevice, st));
-    DevBuf<uint64_t> wlo, whi; DevBuf<uint8_t> flag;
-    std::vector<uint8_t> hflag(L);
-    if (L) {
-        SKX_TRY(ref_windows(ctx, d_seq.p, L, k, a->rc, wlo, whi, flag));
-        SKX_HIP(hipMemcpyAsync(hflag.data(), flag.p, L, hipMemcpyDeviceToHost, st));
-    }
-    SKX_HIP(hipStreamSynchronize(st));
-    SKX_HIP(hipGetLastError());
+    SKX_TRY(ref.windows(a, panel_fasta, false));
     // a window is flagged at its last letter p; its middle base, p - h, says which record it belongs to
     std::vector<skx_screen_record> rec(R);
-    uint64_t n_windows = 0;
     for (uint64_t c = 0; c < R; c++) {
         uint64_t w = 0;
-        for (uint64_t p = cstart[c]; p < cstart[c] + clen[c]; p++) w += hflag[p] != 0;
+        for (uint64_t p = cstart[c]; p < cstart[c] + clen[c]; p++) w += ref.hflag[p] != 0;
         rec[c].length = clen[c]; rec[c].windows = w; rec[c].rows_hit = 0;
-        n_windows += w;
     }
-    if (n_windows == 0) { set_error("%s has no valid sequence", panel_fasta); return SKX_EEMPTY; }                                // as `ska map` (ska_ref.rs:255-257)
     if (R * S > (1ull << 31)) { set_error("screen: %llu records x %llu samples; at most 2^31 (record, sample) pairs are taken", (unsigned long long)R, (unsigned long long)S); return SKX_EUNSUP; }
     pw.stop();
 
-    // look-up and compaction, as skx_array_map does them (an array without rows has no hit)
-    DevBuf<uint32_t> row, mapped; DevBuf<uint8_t> is_rc; uint64_t M = 0;
+    // look-up and compaction (an array without rows has no hit)
     if (a->n_rows) {
         PhaseTimer pl("screen.lookup");
-        SKX_TRY(row.alloc(L)); SKX_TRY(is_rc.alloc(L));
-        if (k <= 31) {
-            DevBuf<uint64_t> sorted; DevBuf<uint32_t> perm;
-            const uint64_t *skeys = a->keys.p; const uint32_t *sperm = nullptr;
-            if (!a->engine_order) { SKX_TRY(sort_words_perm(a->keys.p, a->n_rows, sorted, perm, st)); skeys = sorted.p; sperm = perm.p; }
-            launch_map_lookup(wlo.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
-            SKX_HIP(hipStreamSynchronize(st));
-        } else {
-            DevBuf<uint64_t> tmp, sorted; DevBuf<uint32_t> perm; const u128 *w = nullptr;
-            SKX_TRY(array_wide_words(a, tmp, &w));
-            const u128 *skeys = w; const uint32_t *sperm = nullptr;
-            if (!a->engine_order) { SKX_TRY(sort_wide_perm(w, a->n_rows, sorted, perm, st)); skeys = (const u128 *)sorted.p; sperm = perm.p; }
-            launch_map_lookup_wide(wlo.p, whi.p, flag.p, d_seq.p, L, h, skeys, sperm, a->n_rows, row.p, is_rc.p, st);
-            SKX_HIP(hipStreamSynchronize(st));
-        }
-        SKX_TRY(select_mapped(row.p, L, mapped, &M, st));
-        SKX_HIP(hipGetLastError());
+        SKX_TRY(ref.lookup(a));
     }
-    wlo.release(); whi.release();
+    ref.wlo.release(); ref.whi.release();
+    const DevBuf<uint32_t> &row = ref.row, &mapped = ref.mapped; const DevBuf<uint8_t> &is_rc = ref.is_rc, &d_seq = ref.d_seq;
+    const uint64_t M = ref.M;
 
     const size_t n_cells = (size_t)(R * S);
     skx_screen_cell *out_cells = (skx_screen_cell *)calloc(n_cells ? n_cells : 1, sizeof(skx_screen_cell));

@@ -18,6 +18,7 @@
 //
 // No atomics and no sort: the order (pair, row) is the layout.
 #include "skx_internal.h"
+#include "skx_cells.h"                                              // u32x4
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -38,8 +39,6 @@ struct SitesArgs {
     const uint64_t *pair_start;                                     // [n_pairs] where a pair's records begin
     skx_pair_site *rec; uint64_t cap;
 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // A, C, G or T (65, 67, 71, 84: 64 + bit 1, 3, 7, 20)
 __device__ inline uint32_t one_base(uint32_t b) { return (uint32_t)((b >> 5) == 2u) & (0x0010008Au >> (b & 31u)); }
