@@ -552,6 +552,49 @@ typedef struct {
     uint64_t *snps; uint8_t *snp_ref;
 } skx_density_result;
 int  skx_array_snp_density(skx_array *a, const char *reference_fasta, uint64_t window, uint32_t min_snps, int flags, skx_density_result *out);
+/* `ska mask`: regions of a reference taken out of an array, per sample or for every sample, in place -- what makes the regions of `ska density`
+ * (or a BED of phage, mobile-element or repeat coordinates) usable by every command that reads a .skf.  The reference has no counterpart: its
+ * `ska weed` removes split k-mers by sequence, never by position and never per sample.
+ * Definition (tests/mask_model.py states the same).
+ * Sites.  Reference, windows and sites are `ska density`'s (above): `ska map`'s windows; a window is a site when its split k-mer is a row and
+ *     occurs exactly once among the reference's windows.  Repeated windows are never sites, so a row is the row of at most one site.  is_rc plays
+ *     no part: a cell is only ever made missing.
+ * Intervals.  (sample or SKX_MASK_ALL_SAMPLES, chrom = the index of the FASTA record, start, end), 0-based and inclusive, in positions of a
+ *     window's middle base.  Per (sample, chromosome), and per chromosome for ALL, intervals that overlap or touch (start <= the other's end + 1)
+ *     are merged first: the result does not depend on how the caller cut them.  n_intervals_merged counts the merged ones.
+ * Step 1.  Every row whose site lies in an ALL interval is removed (rows_all_samples).
+ * Step 2.  For each remaining row whose site lies in an interval of sample s (sites_in_regions[s] counts it, present or not): if the cell
+ *     (row, s) is present -- neither '-' nor the 0 byte -- it becomes '-', the row's stored count drops by one (never below 0) and
+ *     cells_masked[s] counts it.
+ * Step 3.  A row that lost a cell in step 2 and has no present cell left is removed (rows_emptied): delete_samples' update_counts(false) rule,
+ *     applied to the rows the call touched.  Keys, variants and counts are compacted in the array's row order; names, k, rc and the sample count
+ *     stay.  A row that is no site, or whose site lies in no interval, keeps every cell and its count -- also one that held no present cell before.
+ * Whole call.  sites, rows_in, rows_all_samples, rows_emptied, rows_out = rows_in - rows_all_samples - rows_emptied.  Everything is an integer:
+ *     the same bytes whatever the order of arrival.  Masking a second time with the same intervals changes nothing.
+ * samples: S records of the caller's, or NULL.  The call works in place, as skx_array_weed does; an array held as pieces or lazily is
+ * materialised first; both key widths, engine-ordered or not.  Every refusal comes before the first cell is changed: `a` keeps its content.
+ * SKX_EINVAL with a message that begins "mask:" for NULL arguments, an interval with start > end, an end past its chromosome, a sample or
+ * chromosome index out of range, a chromosome id that occurs twice; "Cannot create reference from FASTQ files", SKX_EEMPTY "<file> has no valid
+ * sequence" and "split k-mers and variants are out of step ..." as skx_array_map; SKX_EUNSUP with "mask:" for an array that holds only a part
+ * of its samples.  n == 0, no site, no rows, or every row removed (an array of 0 rows comes back and can be saved) is no error.
+ * Device side (csrc/skx_mask.hip).  The sites are compacted in reference order to (position in the concatenated reference, row); every merged
+ * interval finds its stretch of that list by binary search; the host scans the lengths in 64 bits; mask_items_kernel takes SKX_MASK_CHUNK
+ * consecutive (interval, site) items a workgroup -- the ALL intervals first (keep[row] = 0, no cell read), then the per-sample ones (cell, count
+ * by a 32-bit atomic, the sample's two sums per wave).  Intervals are merged per sample and a row has one site, so no cell is visited twice.
+ * When a cell was masked the rows' statistics are counted again from the cells (one read of the matrix); rows go through skx_array_weed's
+ * compaction.  Device memory beside the array: `ska map`'s window buffers and the repeat sort's, 9 bytes a hit window, 8 bytes a site, 24 bytes
+ * a merged interval, 16 bytes a sample, a byte a row, and the compaction's second matrix when a row goes. */
+enum { SKX_MASK_CHUNK = 1024 };                  /* items a workgroup of mask_items_kernel takes, as built */
+#define SKX_MASK_ALL_SAMPLES 0xFFFFFFFFu
+typedef struct { uint32_t sample; uint32_t chrom; uint32_t start, end; } skx_mask_interval;
+typedef struct { uint64_t sites_in_regions, cells_masked; } skx_mask_sample;
+typedef struct { uint64_t sites, rows_in, rows_all_samples, rows_emptied, rows_out, n_intervals_merged; } skx_mask_info;
+int  skx_array_mask_regions(skx_array *a, const char *reference_fasta, const skx_mask_interval *iv, uint64_t n,
+                            skx_mask_sample *samples, skx_mask_info *info);
+/* the records of a FASTA reference as skx_array_map, skx_array_snp_density and skx_array_mask_regions number them (host only): *ids = the *n ids
+ * (the header up to white space), each NUL-terminated, one after the other; *lens = their lengths in bases.  Both malloc'd (skx_free).  "Cannot
+ * create reference from FASTQ files" and a reference longer than 4 G bases are refused as there. */
+int  skx_reference_records(const char *reference_fasta, char **ids, uint64_t **lens, uint64_t *n);
 /* the `k` a .skf file states in its first fields, without loading it (0: not found there, or the file cannot be read): lets a caller that
  * would try 64-bit keys first and 128-bit keys next (lib.rs:635-661) go to the right width at once */
 int  skx_skf_peek_k(const char *path);

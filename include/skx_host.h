@@ -145,6 +145,36 @@ int skh_density_mask_alignment(char *aln, uint64_t len, const skx_density_result
  * .dense) / density.text / density.masked_aln. */
 int skh_density(skx_ctx *ctx, const char *reference_fasta, const char *skf_file, const char *out_prefix, uint64_t window, uint32_t min_snps, int snps,
                 const char *masked_aln);
+/* ---- `ska mask` (no counterpart in the reference; the counts are defined in include/skx.h, the files and the text restated in
+ * tests/mask_model.py).  The two readers take a file's text (host only) and hand over malloc'd intervals (skx_free; *n may be 0) in the file's
+ * order, 0-based and inclusive as skx_array_mask_regions takes them.  Both accept CRLF, blank lines and lines that start with '#', and refuse
+ * with SKX_EINVAL and a message "mask: regions line N: ..." / "mask: bed line N: ..." (N from 1): a line with too few fields, a sample or
+ * chromosome that is not among names / chrom_ids (the first of two equal names wins), a start or an end that is not an unsigned decimal number
+ * of 32 bits, an end past its chromosome, and
+ * skh_mask_read_regions  `ska density`'s OUT.density.regions.tsv or any tab-separated file of its shape: the first line that is neither blank
+ *                        nor a comment is the header and is skipped; then sample, chromosome, start, end, 1-based and inclusive; further
+ *                        columns are ignored.  Refused too: start < 1, end < start.
+ * skh_mask_read_bed      chromosome, start (0-based), end (exclusive), no header; every interval is an ALL interval.  Refused too: end <= start. */
+int skh_mask_read_regions(const char *text, uint64_t len, const char *const *names, uint64_t n_samples, const char *const *chrom_ids, const uint64_t *chrom_lens,
+                          uint64_t n_chrom, skx_mask_interval **out, uint64_t *n);
+int skh_mask_read_bed(const char *text, uint64_t len, const char *const *chrom_ids, const uint64_t *chrom_lens, uint64_t n_chrom, skx_mask_interval **out, uint64_t *n);
+/* <PREFIX>.mask.summary.tsv from what skx_array_mask_regions returned for the intervals iv[n] (host only): header "sample\tintervals\t
+ * interval_bases\tsites_in_regions\tcells_masked", a line per sample in the array's order (its intervals and their bases after merging), then
+ * the lines "all_samples_intervals", "all_samples_bases", "sites", "rows_in", "rows_all_samples", "rows_emptied", "rows_out", each with its
+ * value behind a tab.  SKX_EINVAL for NULL arguments and an interval that names a sample that is not there or ends before it starts.  *buf is
+ * malloc'd (skx_free). */
+int skh_mask_text(const skx_mask_sample *samples, const skx_mask_info *info, const skx_mask_interval *iv, uint64_t n, const char *const *names, uint64_t n_samples,
+                  char **buf, uint64_t *len);
+/* `ska mask <REFERENCE> <SKF_FILE> -o OUT.skf (--regions FILE | --dense [--window W] [--min-snps T]) [--bed FILE] [--summary PREFIX]`: the file is
+ * loaded once, unfiltered (skh_load_array); the intervals are those of regions_file (skh_mask_read_regions) or, with dense != 0, the regions of
+ * skx_array_snp_density on the loaded array at window / min_snps -- the same file as `ska density` followed by `ska mask --regions` -- and those
+ * of bed_file (skh_mask_read_bed); one call of skx_array_mask_regions; the array is saved as skh_save_skf saves it (".skf" appended unless
+ * there) and, with summary_prefix, <PREFIX>.mask.summary.tsv written.  SKX_EINVAL before anything is loaded for NULL arguments, none of the
+ * three sources, regions_file together with dense, W or T out of range (with dense), and an output that is the input file: the input is never
+ * overwritten.  Otherwise the refusals are the readers' and the ABI's.  Phases: mask.load / mask.density / mask.read_intervals / mask.regions
+ * (inside it mask.read_reference, .windows, .lookup, .kernels, .compact) / mask.save / mask.text. */
+int skh_mask(skx_ctx *ctx, const char *reference_fasta, const char *skf_file, const char *out_file, const char *regions_file, int dense, uint64_t window,
+             uint32_t min_snps, const char *bed_file, const char *summary_prefix);
 /* `ska distance <skf>` (lib.rs:710-727 = load + generic_modes::distance), same one-pass load */
 int skh_distance_skf_tsv(skx_ctx *ctx, const char *skf_file, double min_freq, int filt_ambig, char **buf, uint64_t *len);
 /* what `ska distance` writes besides its table (any of the two names may be NULL; NULL for the struct = nothing): `tree` = the file of

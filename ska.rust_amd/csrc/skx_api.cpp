@@ -799,7 +799,7 @@ extern "C" int skx_array_filter(skx_array *a, uint64_t min_count, int filter_amb
 // ------------------------------------------------------------------------------------------ skf life-cycle (N1)
 
 // flags -> scan -> compaction with the keys following the rows
-static int array_keep_rows(skx_array *a, DevBuf<uint8_t> &keep, uint64_t *removed)
+int skx::array_keep_rows(skx_array *a, DevBuf<uint8_t> &keep, uint64_t *removed)
 {
     hipStream_t st = a->ctx->stream;
     const uint64_t U = a->n_rows;

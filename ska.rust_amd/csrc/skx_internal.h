@@ -486,6 +486,8 @@ int array_lazy_rows(skx_array *a, uint8_t *out, uint64_t pitch, uint32_t j_base 
 int pieces_stats_pass(skx_array *a, uint64_t min_count, DevBuf<unsigned long long> *tally = nullptr);
 // one batch of skx_build_and_merge: takes the dictset, returns the batch's array (append pass, else rows + a lazily held array, else the eager merge)
 int merge_batch(skx_ctx *ctx, skx_dictset *d, const char *const *names, skx_array **out);
+// keep[r] = 1: the row stays -> scan and compaction of matrix, statistics and counts, the keys following the rows (skx_api.cpp: weed, delete, mask)
+int array_keep_rows(skx_array *a, DevBuf<uint8_t> &keep, uint64_t *removed);
 inline uint64_t pitch_for(uint64_t cols) { return ((cols + 255) / 256) * 256 + 256; }
 inline bool key_less(const skx_key &x, const skx_key &y) { return x.hi != y.hi ? x.hi < y.hi : x.lo < y.lo; }
 inline bool key_eq(const skx_key &x, const skx_key &y) { return x.hi == y.hi && x.lo == y.lo; }

@@ -149,6 +149,15 @@ const std::vector<Cmd> &commands()
           {"--min-snps", "<T>", "Number of consecutive SNPs of a sample inside a window that makes them dense, 2 to 65535; a convention, not a calibration [default: 5]"},
           {"--snps", "", "Also write <OUTPUT>.density.snps.tsv: every SNP (sample, chromosome, position, ref, alt) and whether it is dense"},
           {"--masked-aln", "<FILE>", "Also write `ska map --repeat-mask`'s alignment with every sample's regions overwritten by 'N': what a tree builder takes"}}},
+        {"mask", "(MI355X engine) Take regions of a reference out of a .skf, per sample (the regions of `ska density`) or for every sample (a BED file), so that every command runs without them", "ska mask [OPTIONS] -o <OUTPUT> <--regions <FILE>|--dense|--bed <FILE>> <REFERENCE> <SKF_FILE>",
+         {{"<REFERENCE>", "", "Reference FASTA file, as for `ska map` and `ska density`"}, {"<SKF_FILE>", "", "Split-kmer (.skf) file to operate on; it is never overwritten"}},
+         {{"-o", "<OUTPUT>", "Output .skf file: the input with the cells of the regions made missing ('-') and the rows left without a sample removed"},
+          {"--regions", "<FILE>", "Per-sample regions: <PREFIX>.density.regions.tsv of `ska density`, or any tab-separated file with a header line and sample, chromosome, start, end (1-based, inclusive)"},
+          {"--dense", "", "Per-sample regions: those `ska density` finds on this file, from the same load; the same output as `ska density` followed by --regions"},
+          {"--window", "<W>", "With --dense: reference positions T SNPs of a sample must lie inside to count as dense, 1 to 2147483648; a convention, not a calibration [default: 1000]"},
+          {"--min-snps", "<T>", "With --dense: number of consecutive SNPs of a sample inside a window that makes them dense, 2 to 65535; a convention, not a calibration [default: 5]"},
+          {"--bed", "<FILE>", "Regions to take out of every sample (phage, mobile elements, repeats): BED with chromosome, 0-based start, exclusive end; their split k-mers are removed"},
+          {"--summary", "<PREFIX>", "Also write <PREFIX>.mask.summary.tsv: per sample its intervals, their bases, the sites inside them and the cells masked, then the rows removed"}}},
     };
     return C;
 }

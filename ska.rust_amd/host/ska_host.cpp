@@ -552,7 +552,7 @@ const char *VALUE_OPTS[] = {"-o", "-k", "-f", "--threads", "--min-count", "--min
                             "-r", "--reference", "--missing", "-d", "--depth", "-n", "--indel-kmers",
                             "--tree", "--clusters", "--cluster-snps", "--cluster-mismatches", "--query", "--query-file", "--query-skf", "--max-snps", "--max-mismatches", "--closest", "--mst-clusters", "--levels", "--sites", "--sites-max",
                             "--groups", "--min-group-size", "--samples", "--samples-file", "--min-in", "--max-out", "--kind",
-                            "--permutations", "--seed", "--order-file", "--min-cover", "--min-identity", "--mad", "--window", "--min-snps", "--masked-aln", nullptr};
+                            "--permutations", "--seed", "--order-file", "--min-cover", "--min-identity", "--mad", "--window", "--min-snps", "--masked-aln", "--regions", "--bed", "--summary", nullptr};
 bool takes_value(const std::string &s) { for (int i = 0; VALUE_OPTS[i]; i++) if (s == VALUE_OPTS[i]) return true; return false; }
 }
 int skh::fail(const char *msg) { fprintf(stderr, "error: %s\n", msg); return 2; }
@@ -596,7 +596,8 @@ const char *skh::clap_arg(const char *flag)
         {"--min-in", "--min-in <P>"}, {"--max-out", "--max-out <Q>"},
         {"--permutations", "--permutations <P>"}, {"--seed", "--seed <N>"}, {"--order-file", "--order-file <FILE>"},
         {"--min-cover", "--min-cover <C>"}, {"--min-identity", "--min-identity <I>"}, {"--mad", "--mad <M>"},
-        {"--window", "--window <W>"}, {"--min-snps", "--min-snps <T>"}, {"--masked-aln", "--masked-aln <FILE>"}};
+        {"--window", "--window <W>"}, {"--min-snps", "--min-snps <T>"}, {"--masked-aln", "--masked-aln <FILE>"},
+        {"--regions", "--regions <FILE>"}, {"--bed", "--bed <FILE>"}, {"--summary", "--summary <PREFIX>"}};
     for (auto &sp : SPELLING) if (!strcmp(flag, sp[0])) return sp[1];
     return flag;
 }
@@ -1096,6 +1097,29 @@ int validate_cli(const std::string &cmd, const Args &a, bool multi)
             if (strtoull(a.get("--min-snps").c_str(), nullptr, 10) > 65535) return clap_invalid(a.get("--min-snps"), "--min-snps <T>", "must be between 2 and 65535 (inclusive)");
         }
     }
+    else if (cmd == "mask") {
+        // the engine's own mode, refused as `ska density` refuses: a missing requirement, a conflict, a value that does not parse
+        if (a.pos.size() < 2) return clap_missing("mask", a.pos.empty() ? "<REFERENCE>\n  <SKF_FILE>" : "<SKF_FILE>");
+        if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("mask")); return 2; }
+        if (!a.has("-o")) return clap_missing("mask", "-o <OUTPUT>");
+        if (a.has("--gpus") || multi) return clap_conflict("mask", "--gpus", "<SKF_FILE>");
+        if (a.has("--regions") && a.has("--dense")) return clap_conflict("mask", "--regions", "--dense");
+        if (!a.has("--regions") && !a.has("--dense") && !a.has("--bed")) return clap_missing("mask", "<--regions <FILE>|--dense|--bed <FILE>>");
+        for (const char *o : {"--window", "--min-snps"})
+            if (a.has(o) && !a.has("--dense")) {
+                fprintf(stderr, "error: the following required arguments were not provided:\n  --dense\n\nUsage: %s\n\nFor more information, try '--help'.\n", skh_usage_line("mask"));
+                return 2;
+            }
+        for (const char *o : {"-o", "--regions", "--bed", "--summary"}) if (a.has(o) && a.get(o).empty()) return clap_invalid("", clap_arg(o), "a value is required");
+        if (a.has("--window")) {
+            if (int e = clap_uint(a.get("--window"), "--window <W>", 1, "must be between 1 and 2147483648 (inclusive)", true)) return e;
+            if (strtoull(a.get("--window").c_str(), nullptr, 10) > (1ull << 31)) return clap_invalid(a.get("--window"), "--window <W>", "must be between 1 and 2147483648 (inclusive)");
+        }
+        if (a.has("--min-snps")) {
+            if (int e = clap_uint(a.get("--min-snps"), "--min-snps <T>", 2, "must be between 2 and 65535 (inclusive)", true)) return e;
+            if (strtoull(a.get("--min-snps").c_str(), nullptr, 10) > 65535) return clap_invalid(a.get("--min-snps"), "--min-snps <T>", "must be between 2 and 65535 (inclusive)");
+        }
+    }
     else if (cmd == "lo") {                                                                                      // cli.rs:395-425
         if (a.pos.size() < 2) return clap_missing("lo", a.pos.empty() ? "<INPUT_SKF>\n  <OUTPUT>" : "<OUTPUT>");
         if (a.pos.size() > 2) { fprintf(stderr, "error: unexpected argument '%s' found\n\nUsage: %s\n\nFor more information, try '--help'.\n", a.pos[2].c_str(), skh_usage_line("lo")); return 2; }
@@ -1157,6 +1181,7 @@ extern "C" int skh_main(int argc, char **argv)
             {"screen", " -o --min-cover --min-identity --matrix --gpus "},
             {"qc", " -o --min-freq --mad --gpus "},
             {"density", " -o --window --min-snps --snps --masked-aln --gpus "},
+            {"mask", " -o --regions --dense --window --min-snps --bed --summary --gpus "},
             {"lo", " -r --reference -m --missing -d --depth -n --indel-kmers --threads "}};
         for (auto &kc : KNOWN)
             if (cmd == kc.cmd)
@@ -1271,6 +1296,14 @@ extern "C" int skh_main(int argc, char **argv)
             fprintf(stderr, "error: %s\n", skx_last_error());                                                     // a panel or a file that cannot be taken: exit code 1
             rcode = 1;
         }
+    } else if (cmd == "mask") {                                                                                   // the engine's own: skh_mask
+        const std::string regions = a.get("--regions"), bed = a.get("--bed"), summary = a.get("--summary");
+        if (skh_mask(ctx, a.pos[0].c_str(), a.pos[1].c_str(), a.get("-o").c_str(), a.has("--regions") ? regions.c_str() : nullptr, a.has("--dense"),
+                     strtoull(a.get("--window", "1000").c_str(), nullptr, 10), (uint32_t)strtoull(a.get("--min-snps", "5").c_str(), nullptr, 10),
+                     a.has("--bed") ? bed.c_str() : nullptr, a.has("--summary") ? summary.c_str() : nullptr) != SKX_OK) {
+            fprintf(stderr, "error: %s\n", skx_last_error());                                                     // a reference or a file that cannot be taken: exit code 1
+            rcode = 1;
+        }
     } else if (cmd == "qc") {                                                                                     // the engine's own: skh_qc
         if (skh_qc(ctx, a.pos[0].c_str(), a.get("-o").c_str(), strtod(a.get("--min-freq", "0.9").c_str(), nullptr), strtod(a.get("--mad", "5").c_str(), nullptr)) != SKX_OK)
             rcode = engine_fail();
@@ -1337,7 +1370,7 @@ extern "C" int skh_main(int argc, char **argv)
         if (r == SKX_EEMPTY) rcode = 1;                                                                          // extremities.rs: std::process::exit(1)
         else if (r != SKX_OK) rcode = engine_fail();
     } else {
-        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers, curve, screen, qc, density)");
+        rcode = fail("unknown subcommand (this engine provides build, align, map, distance, nk, merge, delete, weed, cov, lo, markers, curve, screen, qc, density, mask)");
     }
     const double t_done = since();
     if (dbg) fprintf(stderr, "[skx] main: %s done after %.2f s\n", cmd.c_str(), t_done);

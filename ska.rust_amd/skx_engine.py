@@ -42,6 +42,10 @@ DENSITY_SAMPLE_DT = np.dtype([(f, "<u8") for f in ("sites", "callable", "ambiguo
 DENSITY_BIN_DT = np.dtype([("snps", "<u4"), ("dense_snps", "<u4")])                                                                             # skx_density_bin
 DENSITY_INFO_DT = np.dtype([(f, "<u8") for f in ("windows", "repeat_windows", "sites", "n_chrom", "n_bins", "n_snps", "n_regions")])             # skx_density_info
 DENSITY_REGIONS, DENSITY_SUMMARY, DENSITY_BINS, DENSITY_SNPS = 0, 1, 2, 3   # SKH_DENSITY_* (include/skx_host.h)
+MASK_CHUNK, MASK_ALL_SAMPLES = 1024, 0xFFFFFFFF                             # SKX_MASK_* (include/skx.h): the items a workgroup of skx_array_mask_regions' kernel takes
+MASK_INTERVAL_DT = np.dtype([(f, "<u4") for f in ("sample", "chrom", "start", "end")])                                                          # skx_mask_interval
+MASK_SAMPLE_DT = np.dtype([("sites_in_regions", "<u8"), ("cells_masked", "<u8")])                                                              # skx_mask_sample
+MASK_INFO_DT = np.dtype([(f, "<u8") for f in ("sites", "rows_in", "rows_all_samples", "rows_emptied", "rows_out", "n_intervals_merged")])       # skx_mask_info
 PAIR_SITE_DT = np.dtype([("row", "<u8"), ("pair", "<u4"), ("base_i", "u1"), ("base_j", "u1"), ("reserved", "u1", (2,))])      # skx_pair_site
 TREE_JOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4")])                                                                        # skx_tree_join
 
@@ -164,6 +168,7 @@ skx_array_curve skh_curve skh_curve_orders skh_curve_tsv
 skx_array_screen skh_screen skh_screen_text
 skx_array_sample_qc skh_qc skh_qc_text
 skx_array_snp_density skh_density skh_density_text skh_density_mask_alignment
+skx_array_mask_regions skx_reference_records skh_mask skh_mask_text skh_mask_read_regions skh_mask_read_bed
 skh_newick_joins skh_parsimony_newick skh_parsimony_branches""".split()
 
 _lib = None
@@ -233,6 +238,12 @@ def load_library():
     lib.skh_density_text.argtypes = [i, C.POINTER(DensityResult), C.POINTER(cp), u64, u64, pp, C.POINTER(u64)]
     lib.skh_density_mask_alignment.argtypes = [vp, u64, C.POINTER(DensityResult), C.POINTER(cp), u64]
     lib.skh_density.argtypes = [vp, cp, cp, cp, u64, C.c_uint32, i, cp]
+    lib.skx_array_mask_regions.argtypes = [vp, cp, vp, u64, vp, vp]
+    lib.skx_reference_records.argtypes = [cp, pp, pp, C.POINTER(u64)]
+    lib.skh_mask_read_regions.argtypes = [cp, u64, C.POINTER(cp), u64, C.POINTER(cp), vp, u64, pp, C.POINTER(u64)]
+    lib.skh_mask_read_bed.argtypes = [cp, u64, C.POINTER(cp), vp, u64, pp, C.POINTER(u64)]
+    lib.skh_mask_text.argtypes = [vp, vp, vp, u64, C.POINTER(cp), u64, pp, C.POINTER(u64)]
+    lib.skh_mask.argtypes = [vp, cp, cp, cp, cp, i, u64, C.c_uint32, cp, cp]
     lib.skh_newick_joins.argtypes = [cp, C.POINTER(cp), i, vp, C.POINTER(i)]
     lib.skh_parsimony_newick.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
     lib.skh_parsimony_branches.argtypes = [C.POINTER(cp), vp, i, i, vp, pp, C.POINTER(u64)]
@@ -429,6 +440,72 @@ def density_text(which, res, names, window=1000):
     p, n = C.c_void_p(), C.c_uint64()
     _check(_lib.skh_density_text(int(which), C.byref(r), nm, len(names), int(window), C.byref(p), C.byref(n)))
     return _take(p, n).decode()
+
+
+def _mask_intervals(intervals):
+    """[(sample | MASK_ALL_SAMPLES, chrom, start, end)] or a MASK_INTERVAL_DT array -> a contiguous MASK_INTERVAL_DT array"""
+    if isinstance(intervals, np.ndarray) and intervals.dtype == MASK_INTERVAL_DT:
+        return np.ascontiguousarray(intervals)
+    return np.array([tuple(int(x) for x in q) for q in intervals], MASK_INTERVAL_DT)
+
+
+def _take_intervals(p, n):
+    out = np.frombuffer(C.string_at(p, n.value * MASK_INTERVAL_DT.itemsize), MASK_INTERVAL_DT).copy() if n.value else np.zeros(0, MASK_INTERVAL_DT)
+    _lib.skx_free(p)
+    return out
+
+
+def mask_read_regions(text, names, chrom_ids, chrom_lens):
+    """skh_mask_read_regions: the text (bytes) of a regions file -> MASK_INTERVAL_DT array, 0-based inclusive (host only)"""
+    load_library()
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    ids = (C.c_char_p * max(len(chrom_ids), 1))(*[x.encode() for x in chrom_ids])
+    lens = np.ascontiguousarray(chrom_lens, np.uint64)
+    buf = C.create_string_buffer(bytes(text), len(text)) if len(text) else None           # (exactly len bytes: no terminator is promised)
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_mask_read_regions(C.cast(buf, C.c_char_p), len(text), nm, len(names), ids, _np_ptr(lens), len(chrom_ids), C.byref(p), C.byref(n)))
+    return _take_intervals(p, n)
+
+
+def mask_read_bed(text, chrom_ids, chrom_lens):
+    """skh_mask_read_bed: the text (bytes) of a BED file -> MASK_INTERVAL_DT array of ALL intervals, 0-based inclusive (host only)"""
+    load_library()
+    ids = (C.c_char_p * max(len(chrom_ids), 1))(*[x.encode() for x in chrom_ids])
+    lens = np.ascontiguousarray(chrom_lens, np.uint64)
+    buf = C.create_string_buffer(bytes(text), len(text)) if len(text) else None
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_mask_read_bed(C.cast(buf, C.c_char_p), len(text), ids, _np_ptr(lens), len(chrom_ids), C.byref(p), C.byref(n)))
+    return _take_intervals(p, n)
+
+
+def mask_text(samples, info, intervals, names):
+    """skh_mask_text: PREFIX.mask.summary.tsv from what Array.mask_regions returned for `intervals` (host only)"""
+    load_library()
+    sm = np.ascontiguousarray(samples, MASK_SAMPLE_DT)
+    inf = np.ascontiguousarray(info, MASK_INFO_DT).reshape(1)
+    iv = _mask_intervals(intervals)
+    nm = (C.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    p, n = C.c_void_p(), C.c_uint64()
+    _check(_lib.skh_mask_text(_np_ptr(sm) if len(sm) else None, _np_ptr(inf), _np_ptr(iv) if len(iv) else None, len(iv), nm, len(names), C.byref(p), C.byref(n)))
+    out = C.string_at(p, n.value).decode()
+    _lib.skx_free(p)
+    return out
+
+
+def reference_records(path):
+    """skx_reference_records: (ids, lengths as uint64) of a FASTA reference's records (host only)"""
+    load_library()
+    pi, pl, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _check(_lib.skx_reference_records(os.fsencode(path), C.byref(pi), C.byref(pl), C.byref(n)))
+    lens = np.frombuffer(C.string_at(pl, n.value * 8), np.uint64).copy() if n.value else np.zeros(0, np.uint64)
+    ids, at = [], pi.value
+    for _ in range(n.value):
+        s = C.string_at(at)
+        ids.append(s.decode())
+        at += len(s) + 1
+    _lib.skx_free(pi)
+    _lib.skx_free(pl)
+    return ids, lens
 
 
 def density_mask_alignment(aln, res, names):
@@ -691,6 +768,13 @@ class Context:
     def qc(self, skf_file, out_prefix, min_freq=0.9, mad=5.0):
         """`ska qc <skf> -o PREFIX` (skh_qc): PREFIX.qc.tsv, PREFIX.qc.summary.tsv and PREFIX.qc.flagged.txt"""
         _check(_lib.skh_qc(self.h, os.fsencode(skf_file), os.fsencode(out_prefix), float(min_freq), float(mad)))
+
+    def mask(self, reference, skf_file, out_file, regions=None, dense=False, window=1000, min_snps=5, bed=None, summary=None):
+        """`ska mask <reference> <skf> -o OUT.skf` (skh_mask): the intervals of a regions file or of `ska density` on the loaded array (dense), and of
+        a BED file, taken out of the array, which is saved as out_file; with summary, <summary>.mask.summary.tsv"""
+        enc = lambda x: None if x is None else os.fsencode(x)
+        _check(_lib.skh_mask(self.h, os.fsencode(reference), os.fsencode(skf_file), os.fsencode(out_file), enc(regions), int(dense), int(window), int(min_snps),
+                             enc(bed), enc(summary)))
 
     def density(self, reference, skf_file, out_prefix, window=1000, min_snps=5, snps=False, masked_aln=None):
         """`ska density <reference> <skf> -o PREFIX` (skh_density): PREFIX.density.regions.tsv, .summary.tsv, .bins.tsv and, with snps, .snps.tsv;
@@ -1293,6 +1377,15 @@ class Array:
         for p in (r.samples, r.regions, r.bins, r.chrom_ids, r.chrom_lens, r.snps, r.snp_ref):
             _lib.skx_free(p)
         return out
+
+    def mask_regions(self, reference, intervals, want_samples=True):
+        """skx_array_mask_regions, in place: intervals = [(sample | MASK_ALL_SAMPLES, chrom, start, end)], 0-based inclusive, or a MASK_INTERVAL_DT
+        array -> (per-sample counts as MASK_SAMPLE_DT [S] or None, the call's counts as a MASK_INFO_DT record)"""
+        iv = _mask_intervals(intervals)
+        sm = np.zeros(max(self.nsamples, 1), MASK_SAMPLE_DT)
+        info = np.zeros(1, MASK_INFO_DT)
+        _check(_lib.skx_array_mask_regions(self.h, os.fsencode(reference), _np_ptr(iv) if len(iv) else None, len(iv), _np_ptr(sm) if want_samples else None, _np_ptr(info)))
+        return (sm[:self.nsamples] if want_samples else None), info[0]
 
     def pair_sites(self, ij, min_freq=0.0, max_records=0, keys=True):
         """skx_array_pair_sites: the rows that make up the filter-ambiguous distance of each pair of ij ([n_pairs, 2], i < j), this array left as
