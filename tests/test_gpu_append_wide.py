@@ -40,19 +40,35 @@ def check_equal(E, ga, oa):
     assert list(ga.sample_kmers()) == [int(x) for x in (oa.export()[1] != ord("-")).sum(axis=0)]
 
 
-# (k, genome length): the kernel is instantiated per (dword pair of the key shift, dword of the part bits); these sizes give every pair
-# that the host can choose -- rem = 2 (k - 1) - logQ, logQ from the number of rows:
-#   (33, 3 000) rem 64: shift 59, part bits in dword 2      (33, 70 000) rem 59: shift 64, part bits start at bit 63
-#   (33, 150 000) rem 58: shift 65, part bits in dword 1     (47, 5 000) rem 91: shift 32, part bits start at bit 95
-#   (63, 4 000) rem 113: shift 10, part bits in dword 3      (41, 20 000) rem 77     (55, 9 000) rem 106
-@pytest.mark.parametrize("k,length", [(33, 3000), (33, 70_000), (33, 150_000), (47, 5000), (63, 4000), (41, 20_000), (55, 9000), (35, 40_000)])
+# (k, genome length): the kernel is instantiated per (QS: dword pair of the key shift, PD: dword of the part bits), both from rem = 2 (k - 1) - logQ,
+# logQ from the number of rows.  Measured from the pass's SKX_DEBUG line and asserted below, the same for both rc -- with A readers a region:
+#   (33, 3 000) rem 62, A 4       (33, 70 000) rem 59, A 1      (33, 150 000) rem 58, A 1      (47, 5 000) rem 90, A 2
+#   (63, 4 000) rem 113, A 1 024  (41, 20 000) rem 76, A 2      (55, 9 000) rem 105, A 2       (35, 40 000) rem 64, A 1
+# that is four of the five pairs: (0, 2), rem 91..95, is not among them, and no case with several readers has part bits that reach into the next
+# dword.  Both, and the seams rem 59 | 60 and 91 | 92 from either side: test_gpu_append_wide_shapes.py.
+WIDE_FORMS = {
+    # (k, length): (logQ, rem, QS, PD)
+    (33, 3000): (2, 62, 1, 2), (33, 70_000): (5, 59, 1, 1), (33, 150_000): (6, 58, 2, 1), (47, 5000): (2, 90, 1, 2),
+    (63, 4000): (11, 113, 0, 3), (41, 20_000): (4, 76, 1, 2), (55, 9000): (3, 105, 0, 3), (35, 40_000): (4, 64, 1, 2),
+}
+
+
+@pytest.mark.parametrize("k,length", list(WIDE_FORMS))
 @pytest.mark.parametrize("rc", [True, False])
-def test_wide_append_every_shift_shape(E, k, length, rc):
+def test_wide_append_every_shift_shape(E, k, length, rc, capfd, monkeypatch):
+    from test_gpu_append_wide_shapes import form_of, wide_lines
+    monkeypatch.setenv("SKX_DEBUG", "1")
     rng = np.random.default_rng(1000 * k + length)
     samples = related(rng, length, 5, 20)
     samples.append(samples[0][:1] + rand_records(rng, 2, 400))        # a sample that holds part of the rows only
+    capfd.readouterr()
     ga, oa = build_both(E, samples, k, rc)
+    lines = wide_lines(capfd.readouterr().err)
+    with capfd.disabled():
+        print(f"\n    k={k} length={length} rc={int(rc)} want (logQ, rem, QS, PD)={WIDE_FORMS[k, length]}: {lines}", flush=True)
     assert E.default_context().merge_path() == "append128"
+    assert len(lines) == 1 and lines[0][5] == "ok"
+    assert (lines[0][0],) + form_of(k, lines[0][0])[:3] == WIDE_FORMS[k, length]
     check_equal(E, ga, oa)
 
 
