@@ -131,6 +131,11 @@ void launch_sketch_count(const uint32_t *sketch, int logB, uint32_t *zeros, hipS
 
 void launch_hist(const ExtractArgs &a, hipStream_t st);
 void launch_scatter(const ExtractArgs &a, hipStream_t st);
+// the launchers' own policy, host arithmetic (the build's plan reports it: skx_debug_build_plan, the SKX_DEBUG line of a build)
+void extract_parts(ExtractArgs &a);                  // a.parts / a.tiles_part from a.n_samples and a.tiles_max (both key widths)
+bool extract_hi(int bits, int logB);                 // 64-bit keys: extract_kernel's HI form
+uint32_t dedupe_shape_words(uint32_t cap);           // 64-bit keys: words of the dedupe launch shape that holds `cap`
+bool dedupe_hi(uint32_t cap, int rem_bits, int sb);  // 64-bit keys: dedupe_mb_kernel's HI form for a launch of `cap` words
 
 // exclusive scan of u32 counts into u64 offsets (+ total at out[n]); also max of the counts
 // off[r] = r * capacity (fixed-capacity regions of the single-pass path)

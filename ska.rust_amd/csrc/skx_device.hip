@@ -474,7 +474,7 @@ static inline size_t extract_lds(const ExtractArgs &a, bool scatter)
     return ((size_t)8 << a.logB) + 16 + 80 + (stage > codes ? stage : codes);
 }
 // fewer than eight samples with enough tiles each: 8 / n ranges of tiles per sample
-static inline void extract_parts(ExtractArgs &a)
+void extract_parts(ExtractArgs &a)
 {
     a.parts = 0; a.tiles_part = 0;
     if (a.n_samples >= 1 && a.n_samples < 8 && a.tiles_max >= 64) { a.parts = 8 / a.n_samples; a.tiles_part = (a.tiles_max + a.parts - 1) / a.parts; if (a.parts < 2) a.parts = 0; }
@@ -490,10 +490,11 @@ static void launch_extract_t(const ExtractArgs &a_, hipStream_t st)
     (void)hipFuncSetAttribute((const void *)extract_kernel<SCATTER, TILE, HI, PPT, SPLIT, RMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((extract_kernel<SCATTER, TILE, HI, PPT, SPLIT, RMAX>), dim3((unsigned)g), dim3(TILE / PPT), lds, st, a);
 }
+bool extract_hi(int bits, int logB) { return bits + 4 - 32 - logB >= 0; }
 template <bool SCATTER>
 static void launch_extract(const ExtractArgs &a, hipStream_t st)
 {
-    const bool hi = a.hp.bits + 4 - 32 - a.logB >= 0;
+    const bool hi = extract_hi(a.hp.bits, a.logB);
     if (a.logB <= 10) {          // 12 288 positions x 768 threads, half-tile staging: two workgroups per CU, 12-word chunks
         if (hi) launch_extract_t<SCATTER, 12288, true, 16, SCATTER, 2>(a, st); else launch_extract_t<SCATTER, 12288, false, 16, SCATTER, 2>(a, st);
     } else if (a.logB == 11) {   // the same with three buckets per thread (6-word chunks; the wider cursor array costs 3 VGPRs and a small spill)
@@ -943,14 +944,18 @@ __global__ __launch_bounds__(NT) void dedupe_mb_kernel(uint64_t *words, const ui
     if (threadIdx.x == 0) ucnt[region] = s_rows[ITEMS * NW];
     DD_PROF(8);
 }
+// HI: every field the kernel extracts (micro-bucket, sub-range) starts at bit rem_bits + 4 - (<= log2 cap) or higher
+bool dedupe_hi(uint32_t cap, int rem_bits, int sb)
+{
+    int lc = 0; while ((1u << lc) < cap) lc++;
+    return rem_bits + 4 - lc >= 32 && rem_bits + 4 - sb >= 32;
+}
 template <int ITEMS, int NT>
 static void launch_dedupe_items(uint64_t *words, const uint64_t *off, const uint32_t *raw, uint32_t *ucnt, uint64_t n_blocks, uint32_t cap,
                                 int rem_bits, int *overflow, uint16_t *sidx, int sb, size_t lds, hipStream_t st,
                                 const uint32_t *big, uint32_t big_from, int big_mode)
 {
-    // every field the kernel extracts (micro-bucket, sub-range) starts at bit rem_bits + 4 - (<= log2 cap) or higher
-    int lc = 0; while ((1u << lc) < cap) lc++;
-    if (rem_bits + 4 - lc >= 32 && rem_bits + 4 - sb >= 32) {
+    if (dedupe_hi(cap, rem_bits, sb)) {
         (void)hipFuncSetAttribute((const void *)dedupe_mb_kernel<ITEMS, true, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((dedupe_mb_kernel<ITEMS, true, NT>), dim3((unsigned)n_blocks), dim3(NT), lds, st, words, off, raw, ucnt, cap, rem_bits, overflow, sidx, sb, big, big_from, big_mode);
     } else {
@@ -961,7 +966,7 @@ static void launch_dedupe_items(uint64_t *words, const uint64_t *off, const uint
 // launch shapes of the counting sort: words per region = threads x words per thread.
 // 512 threads while three regions (<= 4 096 words, 49 KB) share a CU; beyond that the LDS footprint fixes two regions per
 // CU and 1 024 threads keep 32 waves on it (800 x 6 Mbp, 3 840-word regions: <6, 1024> 26.4 ms, <8, 512> 20.9 ms).
-static uint32_t dedupe_shape_words(uint32_t cap)
+uint32_t dedupe_shape_words(uint32_t cap)
 {
     return cap <= 512u * 4 ? 512u * 4 : cap <= 512u * 7 ? 512u * 7 : cap <= 512u * 8 ? 512u * 8 : cap <= 1024u * 5 ? 1024u * 5 : 1024u * 6;
 }
@@ -969,11 +974,13 @@ static void launch_dedupe_shape(uint64_t *words, const uint64_t *off, const uint
                                 int rem_bits, int *overflow, uint16_t *sidx, int sb, hipStream_t st, const uint32_t *big, uint32_t big_from, int big_mode)
 {
     size_t lds = (size_t)cap * 8 + 32 + (size_t)cap * 4 + 16;  // elements + four sentinels + two u32 arrays of cap/2 (+ sentinel)
-    if (cap <= 512u * 4) launch_dedupe_items<4, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);
-    else if (cap <= 512u * 7) launch_dedupe_items<7, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);
-    else if (cap <= 512u * 8) launch_dedupe_items<8, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);
-    else if (cap <= 1024u * 5) launch_dedupe_items<5, 1024>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);
-    else launch_dedupe_items<6, 1024>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);    // host keeps regions <= 6144 words
+    switch (dedupe_shape_words(cap)) {      // (one statement of the boundaries: what the build's plan reports is what is launched)
+    case 512u * 4: launch_dedupe_items<4, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode); break;
+    case 512u * 7: launch_dedupe_items<7, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode); break;
+    case 512u * 8: launch_dedupe_items<8, 512>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode); break;
+    case 1024u * 5: launch_dedupe_items<5, 1024>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode); break;
+    default: launch_dedupe_items<6, 1024>(words, off, raw, ucnt, n_blocks, cap, rem_bits, overflow, sidx, sb, lds, st, big, big_from, big_mode);    // host keeps regions <= 6144 words
+    }
 }
 uint32_t dedupe_spill_grid()
 {

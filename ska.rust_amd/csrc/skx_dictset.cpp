@@ -36,13 +36,17 @@ static void launch_dedupe_stage(skx_ctx *ctx, skx_dictset *d, uint32_t cap, int 
 // kernels report as not fitting is an internal error (`what` names the layout in its message).
 // typical (0: unknown, one launch shape): a size all but ~5 in 10 000 regions stay below, which may need a smaller launch shape than the
 // regions' capacity does (launch_dedupe_mb; 64-bit keys only)
+// LDS capacity (words) of the per-region counting sort for regions of up to lds_cap words: 12 B per word, <= 160 KiB
+static uint32_t dedupe_launch_cap(uint32_t lds_cap, bool wide)
+{
+    return std::max<uint32_t>(512, (uint32_t)std::min<uint64_t>(((uint64_t)lds_cap + 255) / 256 * 256, lds_sort_max(wide)));
+}
 static int dedupe_regions(skx_ctx *ctx, skx_dictset *d, uint32_t lds_cap, uint32_t typical, const char *what)
 {
     hipStream_t st = ctx->stream;
     const bool wide = d->wide();
     const uint64_t nreg = (uint64_t)d->n << d->logB;
-    // LDS capacity (words) of the per-region counting sort: 12 B per word, <= 160 KiB
-    const uint32_t cap = std::max<uint32_t>(512, (uint32_t)std::min<uint64_t>(((uint64_t)lds_cap + 255) / 256 * 256, lds_sort_max(wide)));
+    const uint32_t cap = dedupe_launch_cap(lds_cap, wide);
     if (wide) typical = 0;
     DevBuf<int> d_flag; SKX_TRY(d_flag.alloc(1));
     DevBuf<uint32_t> d_big;
@@ -170,14 +174,19 @@ static int dictset_sort_flat(skx_ctx *ctx, skx_dictset *d)
     return set_flat_sorted(ctx, d, lists, sizes);
 }
 
+// windows per region are Poisson around len / B: all but ~5 in 10 000 regions stay below mean + 3.3 sigma
+static uint32_t typical_region(uint64_t maxlen, int logB)
+{
+    const double mean_r = (double)(maxlen >> logB) + 1.0;
+    return (uint32_t)(mean_r + 3.3 * std::sqrt(mean_r) + 1.0);
+}
 // raw regions -> the sorted form, whichever the regions' size asks for (`layout`: fixed-capacity or exact, for the error message)
-static int sort_regions(skx_dictset *d, const char *layout)
+static int sort_regions(skx_dictset *d, const char *layout, bool *flat = nullptr)
 {
     skx_ctx *ctx = d->ctx;
+    if (flat) *flat = d->region_cap > lds_sort_max(d->wide());
     if (d->region_cap > lds_sort_max(d->wide())) return dictset_sort_flat(ctx, d);
-    // windows per region are Poisson around len / B: all but ~5 in 10 000 regions stay below mean + 3.3 sigma
-    const double mean_r = (double)(d->maxlen >> d->logB) + 1.0;
-    SKX_TRY(dedupe_regions(ctx, d, d->region_cap, (uint32_t)(mean_r + 3.3 * std::sqrt(mean_r) + 1.0), layout));
+    SKX_TRY(dedupe_regions(ctx, d, d->region_cap, typical_region(d->maxlen, d->logB), layout));
     d->sorted = true; d->sketch.release();                      // sorted dictionaries: no sketch
     return SKX_OK;
 }
@@ -212,6 +221,12 @@ RegionLayout skx::region_layout(uint64_t maxlen, int k)
     const int need = std::max(0, ilog2_ceil((maxlen + per_region - 1) / per_region));
     const int base_logB = wide ? 11 : 10;
     if (need - 5 > MAX_LOGB) return {-1, 0};
+    // SKX_KNOBS=region_logb=N (tests): a small sample in the layout of a long one -- the extraction kernels' 2^11 .. 2^13-region forms
+    // are otherwise reached from 160 Mbp up
+    if (const long forced = knob("region_logb", -1); forced >= 0) {
+        const int logB = (int)std::min<long>(forced, std::min(2 * (k - 1), MAX_LOGB));
+        return {logB, region_capacity(maxlen, logB)};
+    }
     const int logB = std::max(0, std::min({need > base_logB ? std::max(base_logB, need - 5) : need, 2 * (k - 1), MAX_LOGB}));
     return {logB, region_capacity(maxlen, logB)};
 }
@@ -321,6 +336,61 @@ static int fetch_raw_totals(skx_ctx *ctx, skx_dictset *d)
     return SKX_OK;
 }
 
+// What a build of n assemblies, the longest of maxlen bytes, is launched with: the regions, the extraction kernels' tiles and their
+// dealing to XCDs, and what the per-region sort of regions of lds_cap words (the fixed capacity, or the largest region of the exact
+// layout) would be launched with.  The 64-bit kernels' HI forms are 0 for 128-bit keys, which have one form.
+namespace {
+struct BuildPlan {
+    RegionLayout lay; int tile_bases = 0, tiles_max = 0, parts = 0, tiles_part = 0; bool extract_hi = false;
+    struct Sort { uint32_t cap = 0, shape = 0, typical = 0, shape_typ = 0; bool hi = false, hi_typ = false, flat = false; } sort;
+};
+}  // namespace
+static BuildPlan::Sort sort_plan(uint64_t maxlen, int k, int logB, uint32_t lds_cap)
+{
+    const bool wide = k > 31;
+    BuildPlan::Sort s;
+    s.flat = lds_cap > lds_sort_max(wide);
+    s.cap = dedupe_launch_cap(lds_cap, wide);
+    s.typical = wide ? 0 : typical_region(maxlen, logB);
+    if (wide) { s.shape = s.shape_typ = s.cap; return s; }
+    const int rem_bits = make_hash_params(k).bits - logB, sb = std::min(4, rem_bits);      // (d->hp.bits - d->logB and d->sb of the launch)
+    s.shape = dedupe_shape_words(s.cap); s.shape_typ = std::min(s.shape, dedupe_shape_words(s.typical));
+    s.hi = dedupe_hi(s.cap, rem_bits, sb); s.hi_typ = dedupe_hi(s.shape_typ < s.shape ? s.shape_typ : s.cap, rem_bits, sb);
+    return s;
+}
+static BuildPlan build_plan(uint64_t maxlen, int n, int k)
+{
+    BuildPlan p;
+    p.lay = region_layout(maxlen, k);
+    if (p.lay.logB < 0) return p;
+    const bool wide = k > 31;
+    p.tile_bases = wide ? extract_tile_bases_wide() : extract_tile_bases(p.lay.logB);
+    p.tiles_max = (int)((maxlen + p.tile_bases - 1) / p.tile_bases);
+    ExtractArgs a{}; a.n_samples = n; a.tiles_max = p.tiles_max;
+    extract_parts(a);
+    p.parts = a.parts; p.tiles_part = a.tiles_part;
+    p.extract_hi = !wide && extract_hi(make_hash_params(k).bits, p.lay.logB);      // (a.hp.bits of the launch: new_dictset)
+    p.sort = sort_plan(maxlen, k, p.lay.logB, p.lay.cap);
+    return p;
+}
+// a test hook of the library (not in include/skx.h): the plan for a batch of n_samples assemblies, the longest of maxlen bytes -- out[0] logB
+// (-1: left to the sort-based form, nothing else is set), [1] region capacity, [2] tile bases, [3] tiles_max, [4] parts, [5] tiles_part,
+// [6] extraction takes its HI form, [7] capacity of the dedupe launch, [8] its shape (words), [9] the typical region, [10] the shape the
+// typical region is sorted in, [11] / [12] the dedupe kernel's HI form in the capacity's / the typical shape's launch, [13] the fixed
+// capacity is beyond the per-region sort (sorted dictionaries come from the flat sort)
+extern "C" int skx_debug_build_plan(uint64_t maxlen, int n_samples, int k, int64_t *out)
+{
+    if (!out || n_samples <= 0 || check_k(k) != SKX_OK) { set_error("bad arguments"); return SKX_EINVAL; }
+    const BuildPlan p = build_plan(maxlen, n_samples, k);
+    for (int i = 0; i < 14; i++) out[i] = 0;
+    out[0] = p.lay.logB;
+    if (p.lay.logB < 0) return SKX_OK;
+    out[1] = p.lay.cap; out[2] = p.tile_bases; out[3] = p.tiles_max; out[4] = p.parts; out[5] = p.tiles_part; out[6] = p.extract_hi;
+    out[7] = p.sort.cap; out[8] = p.sort.shape; out[9] = p.sort.typical; out[10] = p.sort.shape_typ; out[11] = p.sort.hi; out[12] = p.sort.hi_typ;
+    out[13] = p.sort.flat;
+    return SKX_OK;
+}
+
 static int dictset_build_device(skx_ctx *ctx, const Batch &b, skx_dictset **out)
 {
     const int n = b.n(), k = b.k;
@@ -328,7 +398,8 @@ static int dictset_build_device(skx_ctx *ctx, const Batch &b, skx_dictset **out)
     for (auto p : b.quals) if (p) return build_reads(ctx, b, out);
     uint64_t maxlen = 0;
     for (auto l : b.lens) maxlen = std::max(maxlen, l);
-    const RegionLayout lay = region_layout(maxlen, k);
+    const BuildPlan plan = build_plan(maxlen, n, k);
+    const RegionLayout lay = plan.lay;
     if (lay.logB < 0) return build_reads(ctx, b, out);
 
     std::unique_ptr<skx_dictset> d = new_dictset(ctx, n, k, b.rc, lay.logB);
@@ -340,9 +411,8 @@ static int dictset_build_device(skx_ctx *ctx, const Batch &b, skx_dictset **out)
     SKX_TRY(d_seqs.alloc(n)); SKX_TRY(d_lens.alloc(n)); SKX_TRY(d_flag.alloc(1));
     SKX_HIP(hipMemcpyAsync(d_seqs.p, b.seqs.data(), n * sizeof(void *), hipMemcpyHostToDevice, st));
     SKX_HIP(hipMemcpyAsync(d_lens.p, b.lens.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    const int tile_bases = wide ? extract_tile_bases_wide() : extract_tile_bases(lay.logB);
     ExtractArgs a{};                                            // (no quality streams here: quals, min_qual and qual_filter stay zero)
-    a.seqs = d_seqs.p; a.lens = d_lens.p; a.n_samples = n; a.tiles_max = (int)((maxlen + tile_bases - 1) / tile_bases);
+    a.seqs = d_seqs.p; a.lens = d_lens.p; a.n_samples = n; a.tiles_max = plan.tiles_max;
     a.k = k; a.rc = b.rc; a.logB = lay.logB; a.hp = d->hp; a.wh = d->wh; a.overflow = d_flag.p;
 
     // single pass with fixed-capacity regions first; the exact two-pass layout if a region overflows
@@ -358,7 +428,23 @@ static int dictset_build_device(skx_ctx *ctx, const Batch &b, skx_dictset **out)
     // chunks whole -- and get their sorted form from the flat sort.
     const bool sort_now = over || knob("sorted_dicts");
     if (!over && (!sort_now || lds_cap > lds_sort_max(wide))) SKX_TRY(fetch_raw_totals(ctx, d.get()));
-    if (sort_now) SKX_TRY(sort_regions(d.get(), over ? "exact-layout" : "fixed-capacity"));
+    uint32_t largest = lds_cap;                                 // (the exact layout's scan left it; the fixed layout's is fetched for the debug line alone)
+    if (getenv("SKX_DEBUG") && !over) {
+        std::vector<uint32_t> raw(nreg);
+        SKX_HIP(hipMemcpyAsync(raw.data(), d->raw.p, nreg * 4, hipMemcpyDeviceToHost, st));
+        SKX_HIP(hipStreamSynchronize(st));
+        largest = *std::max_element(raw.begin(), raw.end());
+    }
+    bool went_flat = false;                                     // (what sort_regions did, for the debug line)
+    if (sort_now) SKX_TRY(sort_regions(d.get(), over ? "exact-layout" : "fixed-capacity", &went_flat));
+    if (getenv("SKX_DEBUG")) {
+        const BuildPlan::Sort sp = sort_plan(maxlen, k, lay.logB, lds_cap);
+        fprintf(stderr, "[skx] build: n=%d k=%d longest=%llu logB=%d cap=%u tile=%d tiles_max=%d parts=%d tiles_part=%d extract_hi=%d layout=%s largest=%u end=%s",
+                n, k, (unsigned long long)maxlen, lay.logB, lay.cap, plan.tile_bases, plan.tiles_max, plan.parts, plan.tiles_part, (int)plan.extract_hi,
+                over ? "exact" : "fixed", largest, !sort_now ? "extracted" : went_flat ? "flat" : "per-region");
+        if (sort_now && !went_flat) fprintf(stderr, " sort_cap=%u shape=%u typical=%u shape_typ=%u dedupe_hi=%d/%d", sp.cap, sp.shape, sp.typical, sp.shape_typ, (int)sp.hi, (int)sp.hi_typ);
+        fprintf(stderr, "\n");
+    }
     *out = d.release();
     return SKX_OK;
 }

@@ -70,7 +70,10 @@ def test_dict_adversarial(E, k):
     edge = [core[:k - 1], core[:k], core[:k + 1], b"N" + core[:k], core[:k] + b"N", core[:k] + b"N" + core[:k],
             core[:k + 1] + b"N" + core[:k + 1], b"A" * (3 * k), b"AT" * (2 * k), b"ACGT" * k, b"", b"N" * 50,
             b"acgtn" * 20, bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=4096 - k // 2).tolist()),
-            bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=8200).tolist())]
+            bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=8200).tolist()),
+            # (the two above were sized for tiles of 4 096 and 8 192; the 64-bit tile is 12 288 positions now, the 128-bit one 8 192)
+            bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=12288 - k // 2).tolist()),
+            bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=12288 + 8).tolist())]
     for rc in (True, False):
         check_dicts(E, [base + edge, edge + base, [core[:k + 1]]], k, rc)
 
@@ -933,8 +936,10 @@ def test_skf_device_decoder_takes_any_valid_element_stream(E, tmp_path, monkeypa
 @pytest.mark.parametrize("k,length", [(31, 2_000_000), (31, 5_000_000), (31, 6_000_000), (31, 6_600_000), (31, 12_000_000), (31, 25_000_000),
                                       (41, 2_000_000), (41, 5_000_000), (41, 12_000_000)])
 def test_dict_every_bucket_configuration(E, k, length):
-    """One sample per bucket count / kernel configuration (512, 1 024, 2 048 x 2 dedupe shapes, 4 096, 8 192 buckets: tile size,
-    half-tile staging, cursor array and dedupe instantiation all change with it), dictionary bit-exact against the oracle."""
+    """One sample per layout these lengths reach today: 2^9 and 2^10 regions (2^10 and 2^11 for 128-bit keys) with the <5, 1024> and <6, 1024>
+    dedupe shapes, then -- from 5 Mbp on the regions grow instead of their number -- 2^10 regions beyond the per-region sort and the flat sort.
+    Dictionary bit-exact against the oracle.  (The 2^11 .. 2^13-region extract instantiations and the other dedupe shapes:
+    tests/test_gpu_extract_edges.py.)"""
     rng = np.random.default_rng(length % 1000 + 7)
     g = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=length, dtype=np.uint8)]
     g[rng.integers(0, length, size=50)] = ord("N")                       # a few window breaks
